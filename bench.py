@@ -10,13 +10,16 @@ Workload (default): the configuration BASELINE.json's metric is quoted on - d=8,
 fp64, 2^21 Sobol candidates per GPU (= configs[2]'s per-GPU shard: 8 ranks score 2^24), LCB(explore=4), the
 reference's acquisition (point_selector.py:197-207).  `--acq ei` / `--acq qei` time the acquisitions the north star
 names; configs[1] (N=512, M=2^20), configs[3] (--dtype f32 --d 16 --n-obs 8192 --m-per-gpu 524288) and configs[4]
-(--acq qei --n-obs 2048 --m-per-gpu 1048576) stay reachable by flags; the default run also reports, under "also": EI on
-the same workload, the same workload through the int8-sliced variance screen, configs[1], and configs[0] (the reference's
-own sizes, on the fixture the reference produced, with the oracle timed beside it).
+(--acq qei --n-obs 2048 --m-per-gpu 1048576) stay reachable by flags.
+A plain run sets up, warms up, times the steps and prints the headline line (with the rooflines of the kernels the timed
+steps bracketed).  `--full` adds what takes runs of its own: the scoring-only time, the CPU baseline (cpu_baseline) and,
+under "also", EI on the same workload, the same workload through the int8-sliced variance screen, configs[1], and
+configs[0] (the reference's own sizes, on the fixture the reference produced, with the oracle timed beside it).
+`--dump-outputs DIR` writes what the last timed step computed (result record, alpha, a fixed sample of U) as DIR/*.npy.
 For N>1 the candidate set grows with N (contiguous shards): weak scaling; the reported value is the whole-job
 rate M_total / max-over-ranks step time.
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     N>1 without WORLD_SIZE in the environment: this process starts the N ranks itself (child processes under
     torch.distributed.run on 127.0.0.1) and exits with their status; under torchrun (WORLD_SIZE set) it is one rank.
 Prints ONE JSON line on rank 0.
@@ -54,11 +57,20 @@ def parse_args(argv=None):
     ap.add_argument("--acq", choices=["lcb", "ei", "qei"], default="lcb",
                     help="lcb: the reference's acquisition; ei: closed-form Expected Improvement; qei: q=8 Monte-Carlo "
                          "qEI with 512 fixed base samples (BASELINE configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps, also measure what takes runs of its own: the scoring-only time, "
+                         "the CPU baseline and the other configurations / routes under 'also' (--no-cpu-baseline and "
+                         "--no-also drop either)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64): best_value, argmax_index, "
+                         "nan_count, alpha, a fixed sample of the upper triangle of U (U_sample, U_sample_rows, "
+                         "U_sample_cols) and perm when the factorisation is reordered")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="target wall time of the cpu_baseline leg (the sample size is chosen from a short probe)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="fix the cpu_baseline sample instead (candidates)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra configs[1] / EI measurements after the timed run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-also", action="store_true",
+                    help="with --full: skip the extra configs[1] / EI measurements after the timed run")
     ap.add_argument("--backend", default="nccl", help="process-group backend; gloo only to rehearse N>1 on one GPU")
     ap.add_argument("--all-on-device", type=int, default=-1,
                     help="rehearsal only: put every rank on this GPU index instead of LOCAL_RANK")
@@ -75,7 +87,10 @@ def parse_args(argv=None):
                     help="f32: fp64 factorisation, fp32 screening of all candidates + fp64 re-scoring of the survivors "
                          "(BASELINE configs[3] shape); i8: the same with the variance product from int8 slices on the "
                          "integer matrix cores (|dsigma| ~ 1e-10)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def _free_port():
@@ -302,6 +317,30 @@ def host_threads():
     return int(threads)
 
 
+U_SAMPLE = 1 << 20   # entries of U in the dump: 8 MB of float64 (the whole of U is 128 MB at the headline N = 4096)
+
+
+def dump_outputs(gp, best, out_dir):
+    """What the last timed step left its caller, as float64 .npy files in out_dir: the reduced result record, the weights
+    alpha, a fixed (seed 0, with replacement) sample of the upper triangle of the inverse factor U (its strictly lower part
+    is zero) with the row and column of every entry, and the factorisation's order when it is not the arrival order."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    N = gp.N
+    rng = np.random.default_rng(0)
+    a, b = rng.integers(0, N, U_SAMPLE), rng.integers(0, N, U_SAMPLE)
+    rows, cols = np.minimum(a, b), np.maximum(a, b)
+    ri, ci = (torch.from_numpy(v).to(gp.device) for v in (rows, cols))
+    out = dict(best_value=[best[0]], argmax_index=[best[1]], nan_count=[best[2]], alpha=gp.alpha[:N].cpu().numpy(),
+               U_sample=gp.U[ri, ci].cpu().numpy(), U_sample_rows=rows, U_sample_cols=cols)
+    if gp.perm is not None:
+        out["perm"] = gp.perm[:N].cpu().numpy()
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(v, dtype=np.float64))
+
+
 def _pmc_ard_entry(N, d):
     """The committed counter pass of the likelihood grid at this shape (profiles/pmc_ard.json, profiles/collect_ard.sh) and
     whether ard.hip has changed since."""
@@ -443,20 +482,23 @@ def main():
         dt = max(float(v) for v in allt.cpu())
     ms_step = dt / args.steps * 1e3
     value = M_total / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(gp, best, args.dump_outputs)
 
     roofline = kstar_roofline = qei_roofline = None
     if events:
         roofline, kstar_roofline, qei_roofline = kernel_rooflines(gp, N, d, args.dtype, qei, args.event_stride)
 
-    # time of the scoring part alone (factorisation excluded), for the record
-    fence()
-    reps = max(2, args.steps // 4)
-    t1 = time.perf_counter()
-    for _ in range(reps):
-        score_async()
-        gp.read_result(gp.status[:4])
-    torch.cuda.synchronize(dev)
-    ms_score = (time.perf_counter() - t1) / reps * 1e3
+    if args.full:
+        # time of the scoring part alone (factorisation excluded), for the record
+        fence()
+        reps = max(2, args.steps // 4)
+        t1 = time.perf_counter()
+        for _ in range(reps):
+            score_async()
+            gp.read_result(gp.status[:4])
+        torch.cuda.synchronize(dev)
+        ms_score = (time.perf_counter() - t1) / reps * 1e3
 
     def timed_steps(fn, reps, g):
         """1 untimed + `reps` timed calls of fn() (each ends with the read-back of the result record); the kernels of the
@@ -906,17 +948,18 @@ def main():
                                     f"{ {'f32': 'fp64 factorisation + fp32 screen + fp64 re-score of the survivors', 'i8': 'fp64 factorisation and means + int8-sliced variance screen + fp64 re-score of the survivors', 'i8c': 'fp64 factorisation and means + coarse int8 variance screen (three digits per operand, six slice products) + fp64 re-score of the survivors', 'f64b': 'fp64 throughout: mean of every candidate, UPPER bound of its acquisition from the variance reduction of the first N/16 observations of the farthest-point-ordered factorisation (N/4 for the survivors), fp64 re-score of every candidate whose bound reaches the best exact value (branch and bound, exact)'}.get(args.dtype, 'fp64') }; "
                                     f"step = factorise + score all candidates + reduce"),
                        "candidates_total": M_total, "parallelism": f"candidate-sharded x{world}"},
-            "ms_per_step_scoring_only": ms_score,
-            "value_excl_factorisation": (hi - lo) * world / (ms_score * 1e-3),
             "argmax_index": best[1], "roofline": roofline, "kstar_roofline": kstar_roofline,
             # one entry per rank (len = ranks_seen): the slowest one is ms_per_step
             "ms_per_step_by_rank": {"min": min(per_rank_ms), "max": max(per_rank_ms), "ranks": len(per_rank_ms)},
             "multi_gpu_note": ("value is measured on the ranks of THIS run only (n_gpus / ranks_seen); any 8-GPU figure quoted "
                                "elsewhere for a 1-GPU run is that number times 8 - an extrapolation, not a measurement"),
         }
+        if args.full:
+            out["ms_per_step_scoring_only"] = ms_score
+            out["value_excl_factorisation"] = (hi - lo) * world / (ms_score * 1e-3)
         if qei_roofline is not None:
             out["qei_roofline"] = qei_roofline
-        if world == 1 and not args.no_cpu_baseline and not qei:
+        if args.full and world == 1 and not args.no_cpu_baseline and not qei:
             cb, idx_cpu, ns = cpu_baseline(X, y, Xs_local, ls, args.acq, args.cpu_seconds, args.cpu_sample, f_best,
                                            "f32" if f32 else "f64", winner=best[1] - lo)
             score_fn = {"f32": gp.score_f32, "i8": gp.score_i8, "i8c": gp.score_i8c, "f64b": gp.score_bound}.get(
@@ -936,7 +979,7 @@ def main():
             out["cpu_baseline"] = cb
         if f32 or i8 or bnd:
             out["screen"] = gp.last_screen   # survivors of the screen, tolerance / threshold and its check, fallback flag
-        if world == 1 and not args.no_also:
+        if args.full and world == 1 and not args.no_also:
             out["also"] = also()
         print(json.dumps(out), flush=True)
     if use_pg:

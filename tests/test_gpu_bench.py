@@ -33,7 +33,7 @@ def test_two_self_launched_ranks_pick_the_point_one_rank_picks_over_the_same_can
 
 @pytest.mark.gpu
 def test_default_line_is_the_metric_configuration_and_matches_the_cpu_port():
-    line = _bench("--steps", "2", "--warmup", "1", "--cpu-seconds", "4")
+    line = _bench("--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "4")
     assert "N=4096" in line["config"]["workload"] and "d=8" in line["config"]["workload"]
     assert line["config"]["candidates_total"] == 1 << 21 and line["dtype"] == "f64"
     assert line["cpu_baseline"]["argmax_match_on_sample"] is True
@@ -94,7 +94,7 @@ def test_default_line_is_the_metric_configuration_and_matches_the_cpu_port():
 
 @pytest.mark.gpu
 def test_int8_sliced_mode_as_the_main_workload():
-    line = _bench("--dtype", "i8", "--n-obs", "1024", "--m-per-gpu", "262144", "--steps", "2", "--warmup", "1",
+    line = _bench("--full", "--dtype", "i8", "--n-obs", "1024", "--m-per-gpu", "262144", "--steps", "2", "--warmup", "1",
                   "--cpu-seconds", "3")
     assert line["dtype"] == "i8" and line["roofline"]["kernel"] == "sigma_i8_kernel" and 0.1 < line["roofline"]["frac"] <= 1.0
     assert line["cpu_baseline"]["argmax_match_on_sample"] is True and not line["screen"]["fallback"]
@@ -102,7 +102,7 @@ def test_int8_sliced_mode_as_the_main_workload():
 
 @pytest.mark.gpu
 def test_coarse_int8_screen_as_the_main_workload():
-    line = _bench("--dtype", "i8c", "--n-obs", "1024", "--m-per-gpu", "262144", "--steps", "2", "--warmup", "1",
+    line = _bench("--full", "--dtype", "i8c", "--n-obs", "1024", "--m-per-gpu", "262144", "--steps", "2", "--warmup", "1",
                   "--cpu-seconds", "3", "--no-also")
     assert line["dtype"] == "i8c" and line["roofline"]["kernel"] == "sigma_i8c_kernel" and 0.05 < line["roofline"]["frac"] <= 1.0
     assert line["roofline"]["unit"].startswith("TOP/s") and line["cpu_baseline"]["argmax_match_on_sample"] is True
@@ -111,7 +111,7 @@ def test_coarse_int8_screen_as_the_main_workload():
 
 @pytest.mark.gpu
 def test_prefix_bound_screen_as_the_main_workload():
-    line = _bench("--dtype", "f64b", "--n-obs", "1024", "--m-per-gpu", "262144", "--steps", "2", "--warmup", "1",
+    line = _bench("--full", "--dtype", "f64b", "--n-obs", "1024", "--m-per-gpu", "262144", "--steps", "2", "--warmup", "1",
                   "--cpu-seconds", "3", "--no-also")
     assert line["dtype"] == "f64" and "prefix-bound" in line["config"]["workload"] or "bound" in line["config"]["workload"]
     assert line["roofline"]["kernel"] == "sigma_acq_kernel" and 0.05 < line["roofline"]["frac"] <= 1.0
@@ -130,3 +130,52 @@ def test_qei_as_the_main_workload_has_its_rooflines():
     assert line["qei_roofline"]["bound"] == "hbm" and 0.0 < line["qei_roofline"]["frac"] <= 1.0
     assert line["qei_roofline"]["launches"] == line["roofline"]["launches"] == 2
     assert line["kstar_roofline"]["bound"] == "hbm" and line["kstar_roofline"]["launches"] == 2
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_alone_and_its_dump_is_the_timed_step(tmp_path):
+    """A plain run (no --full) times its steps and prints the headline line, nothing measured beside it; --dump-outputs
+    writes what the last timed step computed, checked here against the oracle on the same seeded inputs."""
+    import numpy as np
+
+    from bayesian_optimisation_amd.synthetic import ard_length_scales, rff_objective, sobol_points
+    from oracle import gp_oracle as O
+
+    N, M, d = 384, 65536, 8
+    line = _bench("--n-obs", str(N), "--m-per-gpu", str(M), "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert line["metric"] == "candidate acquisitions/sec" and line["unit"] == "candidates/s" and line["higher_is_better"]
+    assert line["dtype"] == "f64" and line["steps"] == 3 and line["warmup"] == 1
+    assert line["value"] == pytest.approx(M / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert not {"cpu_baseline", "also", "ms_per_step_scoring_only"} & set(line)
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(out) == {"best_value", "argmax_index", "nan_count", "alpha", "U_sample", "U_sample_rows", "U_sample_cols"}
+    assert all(v.dtype == np.float64 for v in out.values()) and sum(v.nbytes for v in out.values()) <= 64 << 20
+    assert int(out["argmax_index"][0]) == line["argmax_index"] and out["nan_count"][0] == 0
+    ls = ard_length_scales(d)
+    X = sobol_points(0, N, d)
+    y = rff_objective(X, ls)
+    _, L, alpha = O.factorise(X, y, ls)
+    assert np.max(np.abs(out["alpha"] - alpha)) <= 1e-8 * np.abs(alpha).max()
+    r, c = out["U_sample_rows"].astype(int), out["U_sample_cols"].astype(int)
+    assert np.all(r <= c)
+    W = np.linalg.inv(L)                                       # U = L^-T: U[i, j] = W[j, i]
+    assert np.max(np.abs(out["U_sample"] - W[c, r])) <= 1e-8 * np.abs(W).max()
+    mu, sig = O.posterior_chol(X, y, sobol_points(N, M, d), ls, L=L, alpha=alpha)
+    acq = O.lcb(mu, sig, 4)
+    assert abs(out["best_value"][0] - acq.max()) <= 1e-8 * max(1.0, float(np.abs(y).max()))
+    top2 = np.sort(acq)[-2:]
+    if top2[1] - top2[0] > 1e-7:
+        assert line["argmax_index"] == int(np.flatnonzero(acq == acq.max())[0])
+
+
+def test_bench_options():
+    """--full and --dump-outputs are off unless given; --steps is the number of timed steps and must be at least 1."""
+    sys.path.insert(0, REPO)
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
