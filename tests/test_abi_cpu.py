@@ -109,6 +109,39 @@ def test_size_contracts_are_checked_on_the_host():
     assert lib.gpbo_cholinv_f64(p, 2 * 32896, 32896, p, None, None) == -1   # beyond the plan's cap: factorise takes the chain
 
 
+def test_batched_grid_workspace_contract_is_checked_on_the_host():
+    """The one-launch ARD grid (csrc/ard.hip) at the BASELINE surrogate sizes: one byte short of the workspace query, or a
+    workspace that is not 256-byte aligned, is GPBO_ERR_WORKSPACE in both likelihood modes; N beyond 32768 and G = 0 are
+    GPBO_ERR_ARG.  The query is positive, never shrinks as G grows, and does not overflow at its largest sizes.  (The
+    contract only: not the slot count or the cap behind it.)  Every call here is refused before anything is launched."""
+    import ctypes as C
+
+    lib = _lib.load()
+    buf = (C.c_char * 1024)()
+    p = C.c_void_p((C.addressof(buf) + 255) & ~255)   # never dereferenced
+    ws = lib.gpbo_nlml_grid_batched_workspace_bytes
+    entries = (lib.gpbo_nlml_grid_batched_f64, lib.gpbo_nlml_grid_batched_logdet_f64)
+    for N in (2048, 4096, 8192):
+        for G in (1, 64, 1100):
+            need = ws(N, G)
+            assert need > 0
+            for fn in entries:
+                assert fn(p, p, N, 2, p, G, 1e-4, p, p, need - 1, None) == -3, (N, G)
+                for off in (8, 128):
+                    assert fn(p, p, N, 2, p, G, 1e-4, p, C.c_void_p(p.value + off), need, None) == -3, (N, G, off)
+    for fn in entries:
+        assert fn(p, p, 32769, 2, p, 8, 1e-4, p, p, 1 << 62, None) == -1
+        assert fn(p, p, 2048, 2, p, 0, 1e-4, p, p, 1 << 62, None) == -1
+    assert ws(32769, 8) == -1 and ws(2048, 0) == -1
+    for N in (1, 65, 2048, 2049, 4096, 4097, 8192, 32768):
+        prev = 0
+        for G in (1, 2, 31, 32, 127, 128, 508, 509, 512, 513, 1100, 1 << 20, 1 << 30):
+            b = ws(N, G)
+            assert b >= prev and b >= 8 * G, (N, G, b, prev)   # (G cells of length scales at least: no wrap-around)
+            prev = b
+    assert 8 << 30 <= ws(32768, 1 << 30) < 1 << 62
+
+
 def test_library_path_override(monkeypatch):
     """GPBO_LIB=/path/to/variant.so makes _lib load that file: A/B tools never overwrite the installed library."""
     import importlib
