@@ -96,6 +96,9 @@ SIGNATURES = {
     "gpbo_nlml_grid_batched_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _f64, _p, _p, _i64, _p]),
     "gpbo_nlml_grid_batched_logdet_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _f64, _p, _p, _i64, _p]),
     "gpbo_nlml_cell_f64": (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p, _p]),
+    "gpbo_nlml_grad_workspace_bytes": (_i64, [_i64, _i32]),
+    "gpbo_nlml_grad_f64": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p]),
+    "gpbo_nlml_grad_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _p]),
     "gpbo_gemm_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
                                 _i32, _i32, _p]),
 }

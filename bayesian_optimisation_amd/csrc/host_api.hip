@@ -7,6 +7,7 @@
 // allocated, filled, used and released inside the call, on the library's own stream.
 //   gpbo_select_next_host_f64  = update_surrogate() after the length scales are chosen + the acquisition arg-max
 //   gpbo_nlml_grid_host_f64    = tune_kernel()'s likelihood grid
+//   gpbo_nlml_grad_host_f64    = the likelihood and its gradient in the log length scales (ard="gradient")
 #include "gpbo_internal.h"
 
 #include <vector>
@@ -266,4 +267,30 @@ extern "C" int gpbo_nlml_grid_host_f64(const double *X, const double *y, int64_t
 extern "C" int gpbo_nlml_grid_logdet_host_f64(const double *X, const double *y, int64_t N, int32_t d,
                                               const double *ls_cells, int64_t G, double jitter, double *out) {
     return nlml_grid_host(X, y, N, d, ls_cells, G, jitter, out, 1);
+}
+
+extern "C" int gpbo_nlml_grad_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls,
+                                       double jitter, double *out) {
+    if (!X || !y || !ls || !out || N < 1 || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
+    for (int k = 0; k < d; ++k)
+        if (!(ls[k] > 0.0)) return GPBO_ERR_ARG;
+    const int64_t Np = gpbo_padded_n(N);
+    const int64_t wfact = gpbo_factorise_workspace_bytes(Np), wgrad = gpbo_nlml_grad_workspace_bytes(Np, d);
+    if (wgrad < 0) return GPBO_ERR_ARG;
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N);
+    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
+    double *dout = A.alloc<double>(1 + d);
+    int32_t *dinfo = A.alloc<int32_t>(1);
+    char *dwork = A.alloc<char>(wfact), *dwg = A.alloc<char>(wgrad);
+    if (!A.ok) return GPBO_ERR_WORKSPACE;
+    void *st = reinterpret_cast<void *>(A.stream);
+    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N)) return GPBO_ERR_LAUNCH;
+    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter, 0.0, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    if (rc != GPBO_OK) return rc;
+    rc = gpbo_nlml_grad_f64(dU, dalpha, dy, dX, N, Np, d, ls, dinfo, dout, dwg, wgrad, st);
+    if (rc != GPBO_OK) return rc;
+    if (!A.d2h(out, dout, sizeof(double) * (1 + d)) || !A.sync()) return GPBO_ERR_LAUNCH;
+    return GPBO_OK;
 }

@@ -833,6 +833,77 @@ class DeviceGP:
             self._keep_ard = (Xd, yd, cells)   # alive until the stream has consumed them
         return out
 
+    # -- ML-II length-scale fitting (ard="gradient"; csrc/ard_grad.hip) --------------------------------------------
+    def _fit_buffers(self, Np: int, d: int):
+        """The fit's own factor buffers (K, U, alpha, info, workspaces): the surrogate's K / U / alpha stay untouched."""
+        torch = self.torch
+        fb = getattr(self, "_fit_bufs", None)
+        if fb is None or fb["Np"] != Np or fb["d"] < d:
+            self._fit_bufs = None
+            wf = int(self.lib.gpbo_factorise_workspace_bytes(Np))
+            wg = int(self.lib.gpbo_nlml_grad_workspace_bytes(Np, d))
+            if wg < 0:
+                raise _lib.GpboError("gpbo_nlml_grad_workspace_bytes: invalid sizes")
+            f64 = dict(dtype=torch.float64, device=self.device)
+            fb = dict(Np=Np, d=d, K=torch.empty((Np, Np), **f64), U=torch.empty((Np, Np), **f64),
+                      alpha=torch.empty(Np, **f64), out=torch.empty(1 + d, **f64),
+                      info=torch.zeros(1, dtype=torch.int32, device=self.device),
+                      work_fact=torch.empty((wf + 7) // 8, **f64), wf=wf, work_grad=torch.empty((wg + 7) // 8, **f64), wg=wg)
+            self._fit_bufs = fb
+        return fb
+
+    def _fit_bytes(self) -> int:
+        fb = getattr(self, "_fit_bufs", None)
+        if fb is None:
+            return 0
+        return sum(t.numel() * t.element_size() for t in fb.values() if isinstance(t, self.torch.Tensor))
+
+    def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL):
+        """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I - the "logdet" likelihood and its gradient - from a
+        factorisation into the fit's own buffers (the surrogate held by this object is not touched).  NaN in every
+        output when K is not positive definite.  d <= 16."""
+        torch = self.torch
+        Xd, yd = self._dev(X), self._dev(y).reshape(-1)
+        if Xd.dim() != 2:
+            raise ValueError("X must be (N, d)")
+        N, d = int(Xd.shape[0]), int(Xd.shape[1])
+        if d > _lib.MAX_D:
+            raise ValueError(f"the likelihood gradient supports d <= {_lib.MAX_D}, got {d}")
+        if yd.numel() != N:
+            raise ValueError("y must have one value per row of X")
+        ls_h = np.ascontiguousarray(np.asarray(ls, dtype=np.float64).reshape(-1))
+        if ls_h.size != d:
+            raise ValueError(f"length scales: expected {d} values, got {ls_h.size}")
+        if not np.all(ls_h > 0):
+            raise ValueError("length scales must be positive")
+        Np = int(self.lib.gpbo_padded_n(N))
+        with torch.cuda.device(self.device):
+            fb = self._fit_buffers(Np, d)
+            lsp = ls_h.ctypes.data_as(C.c_void_p)
+            st = self.lib.gpbo_factorise_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, float(jitter), 0.0, Np,
+                                             self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
+                                             self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
+            _lib.check(st, "gpbo_factorise_f64")
+            st = self.lib.gpbo_nlml_grad_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N, Np,
+                                             d, lsp, self._ptr(fb["info"]), self._ptr(fb["out"]), self._ptr(fb["work_grad"]),
+                                             fb["wg"], self._stream())
+            _lib.check(st, "gpbo_nlml_grad_f64")
+            out = fb["out"][: 1 + d].cpu().numpy()   # synchronises
+        return float(out[0]), out[1:].copy()
+
+    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, **opts):
+        """ML-II fit of the ARD length scales inside [lower, upper] from ls0 (ard_fit.fit_length_scales: projected L-BFGS
+        in log ls, every evaluation one factorisation + one gradient launch).  Returns the FitResult.  The fit's buffers
+        are released afterwards when larger than ARD_KEEP_WORKSPACE_BYTES."""
+        from .ard_fit import fit_length_scales
+
+        Xd, yd = self._dev(X), self._dev(y).reshape(-1)   # uploaded once for all evaluations
+        try:
+            return fit_length_scales(lambda ls: self.nlml_and_grad(Xd, yd, ls, jitter), ls0, lower, upper, **opts)
+        finally:
+            if self._fit_bytes() > self.ARD_KEEP_WORKSPACE_BYTES:
+                self._fit_bufs = None
+
     # -- dense covariance blocks for inspection (small problems only) --------------------------------------
     def cov_meas_host(self) -> np.ndarray:
         """cov_meas (point_selector.py:79) in the caller's order of the observations."""

@@ -1,7 +1,7 @@
 """The drop-in class bound through the host-pointer C entry points only: NumPy + ctypes, no PyTorch.
 
 This is the ctypes stub a maintainer of the reference would write against include/gpbo.h
-(gpbo_select_next_host_f64, gpbo_nlml_grid_host_f64): the arrays the reference already holds
+(gpbo_select_next_host_f64, gpbo_nlml_grid_host_f64, gpbo_nlml_grad_host_f64): the arrays the reference already holds
 (/root/reference/select_parameters.py:149-153, 285-289) go in as host pointers, `mean_func`, `cov_func`,
 `acq_func_eval` and the selected index come back.  Every call allocates and frees its device buffers inside the
 library, which costs a few milliseconds per step against the tensor-resident `PointSelector`; the numbers are the
@@ -48,6 +48,22 @@ def nlml_grid(X, y, ls_cells, jitter: float = JITTER_KERNEL, lib=None, likelihoo
     return out
 
 
+def nlml_and_grad(X, y, ls, jitter: float = JITTER_KERNEL, lib=None):
+    """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I on host arrays: gpbo_nlml_grad_host_f64 (factorisation and
+    gradient kernel in one call).  NaN in every output when K is not positive definite.  d <= 16."""
+    lib = lib or _lib.load()
+    X, y = _f64(X), _f64(y).reshape(-1)
+    N, d = X.shape
+    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
+    if ls.size != d or y.size != N:
+        raise ValueError("shapes: X (N, d), y (N,), ls (d,)")
+    out = np.empty(1 + d)
+    _lib.note_hip_use()
+    _lib.check(lib.gpbo_nlml_grad_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), float(jitter), _ptr(out)),
+               "gpbo_nlml_grad_host_f64")
+    return float(out[0]), out[1:].copy()
+
+
 def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
                 dense: bool = True, want_cov_meas: bool = False, chunk: int = 0, lib=None) -> dict:
     """One surrogate step on host arrays.  Returns dict(best_val, best_idx, nan_count, info, mu, sigma, acq, cov_meas)."""
@@ -84,7 +100,8 @@ def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_
 
 
 class _GridOnly:
-    """What PointSelector.tune_kernel needs from its surrogate object: the likelihood grid."""
+    """What PointSelector.tune_kernel needs from its surrogate object: the likelihood grid (ard="grid") or the likelihood
+    and its gradient (ard="gradient")."""
 
     def __init__(self, lib):
         self.lib = lib
@@ -92,12 +109,21 @@ class _GridOnly:
     def nlml_grid(self, X, y, ls_cells, jitter: float = JITTER_KERNEL, likelihood: str = "reference"):
         return nlml_grid(X, y, ls_cells, jitter, self.lib, likelihood)
 
+    def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL):
+        return nlml_and_grad(X, y, ls, jitter, self.lib)
+
+    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, **opts):
+        from .ard_fit import fit_length_scales
+
+        X, y = _f64(X), _f64(y).reshape(-1)
+        return fit_length_scales(lambda ls: self.nlml_and_grad(X, y, ls, jitter), ls0, lower, upper, **opts)
+
 
 class PointSelectorHost(PointSelector):
     """`PointSelector` with the same attribute protocol (point_selector.py:13-207), on the host-pointer entry points."""
 
-    def __init__(self, verbose: bool = False, chunk: int = 0, likelihood: str = "reference"):
-        super().__init__(device=None, verbose=verbose, shard_candidates=False, likelihood=likelihood)
+    def __init__(self, verbose: bool = False, chunk: int = 0, likelihood: str = "reference", ard: str = "grid"):
+        super().__init__(device=None, verbose=verbose, shard_candidates=False, likelihood=likelihood, ard=ard)
         self.lib = _lib.load()
         self._gp = _GridOnly(self.lib)
         self._chunk = int(chunk)

@@ -28,7 +28,9 @@ Differences from the reference, all deliberate:
     calls go through the exact prefix bound), `kernel_params` may be preset (then no
     ARD search runs), optional multi-GPU candidate sharding when torch.distributed is initialised,
     `incremental=True` / `state_path=...` (append new observations to the previous factorisation in O(N^2)
-    while the length scales stay the same, within one process or across jobs through a state file).
+    while the length scales stay the same, within one process or across jobs through a state file), and
+    `ard="gradient"` (fit the length scales by maximising the marginal likelihood with its gradient instead of the grid
+    search; INTEGRATION.md "ARD fit modes").
 There is no CPU implementation behind this class.
 """
 from __future__ import annotations
@@ -59,7 +61,8 @@ def _plot_hooks():
 
 class PointSelector:
     def __init__(self, device=None, verbose: bool = False, shard_candidates: bool = True, precision: str = "fp64",
-                 incremental: bool = False, state_path=None, dense_outputs: bool = True, likelihood: str = "reference"):
+                 incremental: bool = False, state_path=None, dense_outputs: bool = True, likelihood: str = "reference",
+                 ard: str = "grid"):
         # attribute protocol of point_selector.py:15-40
         self.feature_domain = None
         self.predicted_pts = None
@@ -92,6 +95,13 @@ class PointSelector:
         if likelihood not in ("reference", "logdet"):
             raise ValueError("likelihood must be 'reference' (the reference's np.log(np.linalg.det(K))) or 'logdet'")
         self._likelihood = likelihood
+        # ard="grid" (default): tune_kernel searches the length-scale grid as the reference does (point_selector.py:104-163);
+        # "gradient" (not in the reference): ML-II fit of all d length scales at once inside the box the search axes span,
+        # projected L-BFGS on the fp64 log-det likelihood and its gradient (ard_fit.py, csrc/ard_grad.hip)
+        if ard not in ("grid", "gradient"):
+            raise ValueError("ard must be 'grid' (the reference's grid search) or 'gradient' (ML-II fit of the length scales)")
+        self._ard = ard
+        self.last_fit = None           # ard="gradient": the last fit (ard_fit.FitResult.as_dict())
         # dense_outputs=False (not in the reference): a caller that needs the next point only.  mean_func / cov_func /
         # acq_func_eval stay None and the acquisition calls return the same multi-index through the exact prefix bound
         # (DeviceGP.score_bound: fp64 branch and bound, the full pass when the bound does not separate the candidates).
@@ -315,6 +325,9 @@ class PointSelector:
         plot2, plot1 = _plot_hooks()
         if self._gp is None:
             self._gp = DeviceGP(self._device)
+        if self._ard == "gradient":
+            self._fit_kernel(X, y)
+            return
         if self._ls_cells is not None:
             # explicit cell list (any d): the reference's likelihood in every cell, first minimum wins
             if self._ls_cells.shape[1] != X.shape[1]:
@@ -366,6 +379,39 @@ class PointSelector:
                     plot1(nlogml, self.kernel_params, self.length_scales, self.name, self.iteration)
                 except Exception:  # noqa: BLE001
                     pass
+
+    def _fit_kernel(self, X, y):
+        """tune_kernel with ard="gradient": the box is each feature's [min, max] of its search axis (of the cell list's
+        column with set_length_scale_cells), the start the middle of every axis - the reference's choice when it does not
+        tune (point_selector.py:63-73) - and the objective always the fp64 log-det likelihood: the reference's
+        log(det K) is -inf beyond N ~ 100 and has no gradient.  kernel_params keeps the shape the grid route gives for
+        that d; hyperparam_obj (point_selector.py:30) receives the accepted likelihood values.  With several ranks every
+        rank fits the same problem with the same deterministic kernels: no collective."""
+        d = X.shape[1]
+        if self._ls_cells is not None:
+            if self._ls_cells.shape[1] != d:
+                raise ValueError(f"length-scale cells have {self._ls_cells.shape[1]} columns, the observations {d}")
+            lower, upper = self._ls_cells.min(axis=0), self._ls_cells.max(axis=0)
+            ls0 = np.array(self._ls_cells[len(self._ls_cells) // 2])
+            shape = (d,)
+        else:
+            if d > 2 or len(self.length_scales) == 2:
+                axes = [np.asarray(a, dtype=np.float64).reshape(-1) for a in self.length_scales]
+                shape = (len(axes),)
+            else:
+                axes = [np.asarray(self.length_scales, dtype=np.float64).reshape(-1)]
+                shape = (1, 1)                                            # np.array([axis[min_idx]]), as at :161
+            if len(axes) != d:
+                raise ValueError(f"length_scales must hold one axis per feature ({d}), got {len(axes)}")
+            lower = np.array([a.min() for a in axes])
+            upper = np.array([a.max() for a in axes])
+            ls0 = np.array([a[len(a) // 2] for a in axes])
+        res = self._gp.fit_length_scales(X, y, ls0, lower, upper)
+        self.kernel_params = np.asarray(res.ls, dtype=np.float64).reshape(shape)
+        self.hyperparam_obj = [float(v) for v in res.trace]
+        self.nlogml = np.asarray(res.trace, dtype=np.float64)
+        self.last_fit = res.as_dict()
+        self._log(f"ARD fit: {res.reason} after {res.n_iter} steps / {res.n_eval} evaluations, nlml {res.nlml:.12g}")
 
     # ------------------------------------------------------------------------------------------
     def _finish(self, key, kind, **kw):

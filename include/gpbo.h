@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1: + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -396,6 +396,23 @@ int gpbo_nlml_grid_batched_logdet_f64(const double *X, const double *y, int64_t 
  * log det K = -2 sum log U_ii, y^T K^-1 y = y . alpha; NaN when info != 0 (the reference's log of a negative det). */
 int gpbo_nlml_cell_f64(const double *U, const double *alpha, const double *y, int64_t N, int64_t Np,
                        const int32_t *info, float *out, void *stream);
+
+/* ML-II length-scale fitting (not in the reference: point_selector.py:30 / :33 declare `hyperparam_obj` and `gradient_steps`
+ * for a gradient fit that was never built).  From a factorisation of K = K0 + jitter I made by gpbo_factorise_f64 with
+ * (jitter1, jitter2) = (jitter, 0) - U, alpha, info - and the same X [N x d] (device), y, ls_host:
+ *   out[0]     = NLML = 1/2 (y . alpha + log det K + N log 2 pi), log det K = -2 sum log U_ii (the "logdet" likelihood)
+ *   out[1 + k] = dNLML / dlog ls_k = 1/2 sum_ij W_ij K0_ij (x_ik - x_jk)^2 / ls_k^2,   W = K^-1 - alpha alpha^T
+ * out: [1 + d] doubles, device; all NaN when info != 0.  K^-1 = U U^T is never formed: its lower block triangle is
+ * produced 64 x 64 tile by tile on the matrix cores and consumed in registers (csrc/ard_grad.hip).  The sum is reduced in
+ * a fixed order (no atomics): two calls give the same bits.  Np = gpbo_padded_n(N), 1 <= d <= GPBO_MAX_D, ls > 0;
+ * work: gpbo_nlml_grad_workspace_bytes(Np, d) bytes (negative: invalid sizes), 16-byte aligned.
+ * gpbo_nlml_grad_host_f64: factorisation + gradient on host arrays in one call (device buffers inside the call). */
+int64_t gpbo_nlml_grad_workspace_bytes(int64_t Np, int32_t d);
+int gpbo_nlml_grad_f64(const double *U, const double *alpha, const double *y, const double *X, int64_t N, int64_t Np,
+                       int32_t d, const double *ls_host, const int32_t *info, double *out, void *work, int64_t work_bytes,
+                       void *stream);
+int gpbo_nlml_grad_host_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
+                            double jitter, double *out_host);
 
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;
