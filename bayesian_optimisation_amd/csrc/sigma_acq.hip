@@ -10,7 +10,7 @@
 //
 // Workgroup = 512 threads = 8 waves, owns 256 candidates end to end:
 //   for each 128-column block jb of V:   k runs over [0, 128*(jb+1))  (U is upper triangular)
-//       16-deep k tiles: KsT tile [16 x 256] and U tile [16 x 128] go global -> LDS directly (global_load_lds,
+//       16-deep k tiles: KsT tile [16 x 256] and U tile [16 x 128] go global -> LDS directly (LDS-DMA loads,
 //       three-stage ring, one barrier in the middle of each k tile), MFMA 4x4 tiles of 16x16 per wave;
 //       inside the diagonal block, 16x16 tiles of U that lie wholly below the diagonal are skipped
 //   epilogue: row-sum of squares -> sigma -> mean from the per-slice partials -> LCB / EI -> optional
@@ -58,8 +58,20 @@ typedef const __attribute__((address_space(1))) void glb_void_t;
 
 // 16 bytes per lane, global -> LDS without a VGPR round trip.  The LDS destination is the wave-uniform
 // address `l` plus lane*16; the global source is per lane.
-__device__ __forceinline__ void glds16(const double *g, double *l) {
-    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)l, 16, 0, 0);
+// `g` (the tile base) is wave-uniform as well and `off` a 32-bit BYTE offset per lane: the piece is a buffer load through a
+// descriptor made of the tile base (buffer_load_dwordx4 v_off, s[desc], 0 offen lds) and needs no vector instruction to form
+// a 64-bit address; the global_load_lds form cost one v_lshl_add_u64 per piece, all six into the same register pair.
+#ifndef GPBO_SIGMA_DMA_GLOBAL
+#define GPBO_SIGMA_DMA_GLOBAL 0   // 1: the global_load_lds form (A/B builds)
+#endif
+__device__ __forceinline__ void glds16(const double *g, unsigned off, double *l) {
+#if GPBO_SIGMA_DMA_GLOBAL
+    __builtin_amdgcn_global_load_lds((glb_void_t *)(reinterpret_cast<const char *>(g) + off), (lds_void_t *)l, 16, 0, 0);
+#else
+    // raw buffer, stride 0, 2^32 - 1 bytes from the tile base (every offset of a tile is below 2^32: GPBO_CHUNK_MAX, Np <= 2^20)
+    const __amdgpu_buffer_rsrc_t desc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g), 0, -1, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(desc, (lds_void_t *)l, 16, (int)off, 0, 0, 0);
+#endif
 }
 
 __device__ __forceinline__ bool better(double v2, int64_t i2, double v, int64_t i) { return gpbo_better(v2, i2, v, i); }
@@ -74,7 +86,7 @@ __device__ __forceinline__ double acquisition(int kind, double mu, double sigma,
 // blocks of two 8-candidate batches - to 8 more accumulators, and V itself never leaves the registers (round 4 wrote the
 // 2.1 GB of V per launch for qei_kernel to read back).  `vbuf` then receives the partial Gram blocks:
 // [S * WQ partials][ldk / 8 batches][8 x 8].
-template <int VARIANT, bool GRAM = false>  // VARIANT 0 = product; 1, 2 = timing-only diagnostics (GPBO_SIGMA_VARIANT), wrong results
+template <int VARIANT, bool GRAM = false>  // VARIANT 0 = product; others = timing-only diagnostics (GPBO_SIGMA_VARIANT), wrong results
 __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
     const double *__restrict__ KsT, int64_t ldk, const double *__restrict__ U, int Np,
     const double *__restrict__ mu_part, int nsl, int64_t Mc, double prior_var, int acq_kind, double p0, double p1,
@@ -86,6 +98,10 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
     int ntile, int ncb /* > 0: only the first ncb column blocks of V (the prefix-bound screen: |v|^2 over the first
                           128 ncb observations is a LOWER bound of |v|^2, the variance from it an upper bound) */) {
     __shared__ double smem[3 * STAGE];
+    // diagnostics: TV = the timing variant (1 = no barrier and no DMA, 2 = no tile skipping on the diagonal, 3 = no barrier,
+    // 4 = no DMA); VARIANT 6 = the product loop with per-tile stamps, 8 + v = timing variant v with per-tile stamps
+    constexpr bool STAMP = VARIANT == 6 || VARIANT >= 8;
+    constexpr int TV = VARIANT >= 8 ? VARIANT - 8 : (VARIANT == 6 ? 0 : VARIANT);
     // Column split (few candidates, e.g. the re-scoring behind a screen): workgroup (x, s) of S takes the column
     // blocks s, 2S-1-s, 2S+s, 4S-1-s, ... (boustrophedon rounds: block jb costs jb+1 k tiles, so pairing a cheap
     // with an expensive one balances the S workgroups) and leaves its partial row sums for split_finish_kernel.
@@ -111,7 +127,7 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
     const int l15 = lane & 15, l4 = lane >> 4;
     const int64_t cand0 = (int64_t)tile_x * BM;
 
-    // staging: global -> LDS directly (global_load_lds_dwordx4, 1 KiB per wave instruction, no VGPRs).
+    // staging: global -> LDS directly (buffer_load_dwordx4 ... lds, 1 KiB per wave instruction, no VGPRs).
     // LDS image rows are padded, and every wave instruction's 1 KiB lies inside one row:
     //   A tile (K*^T): 16 rows x BM/128 pieces, B tile (U): 16 rows x BN/128 pieces; wave w takes pieces w + 8r
     // The tile base pointers are wave-uniform and advance incrementally (scalar adds); each lane's share of a
@@ -119,18 +135,18 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
     const double *a_base = KsT + cand0;
     constexpr int AP = BM / 128, BP = BN / 128;  // 1 KiB pieces per row
     constexpr int NPA = BK * AP / NW, NPB = BK * BP / NW;  // 1-KiB pieces per wave per tile
-    unsigned voffA[NPA], voffB[NPB];        // element offsets inside a tile (row * ld + piece * 128 + lane * 2)
+    unsigned voffA[NPA], voffB[NPB];        // byte offsets inside a tile, 8 (row * ld + piece * 128 + lane * 2) < 2^32
     int ldsA[NPA], ldsB[NPB];               // LDS element offsets of the pieces inside a stage
 #pragma unroll
     for (int r = 0; r < NPA; ++r) {
         const int u = wid + NW * r, row = u / AP, piece = u % AP;
-        voffA[r] = (unsigned)(row * (unsigned)ldk + piece * 128 + lane * 2);
+        voffA[r] = (unsigned)(row * (unsigned)ldk + piece * 128 + lane * 2) * 8u;
         ldsA[r] = row * LDA + piece * 128;
     }
 #pragma unroll
     for (int r = 0; r < NPB; ++r) {
         const int u = wid + NW * r, row = u / BP, piece = u % BP;
-        voffB[r] = (unsigned)(row * (unsigned)Np + piece * 128 + lane * 2);
+        voffB[r] = (unsigned)(row * (unsigned)Np + piece * 128 + lane * 2) * 8u;
         ldsB[r] = A_TILE + row * LDB + piece * 128;
     }
     d4_t acc[MI][NI];
@@ -153,9 +169,9 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
     auto stage_next = [&]() {
         double *St = smem + pbuf * STAGE;
 #pragma unroll
-        for (int r = 0; r < NPA; ++r) glds16(pa + voffA[r], St + ldsA[r]);
+        for (int r = 0; r < NPA; ++r) glds16(pa, voffA[r], St + ldsA[r]);
 #pragma unroll
-        for (int r = 0; r < NPB; ++r) glds16(pb + voffB[r], St + ldsB[r]);
+        for (int r = 0; r < NPB; ++r) glds16(pb, voffB[r], St + ldsB[r]);
         pbuf = (pbuf == 2) ? 0 : pbuf + 1;
         if (++pk == (pj + 1) * (BN / BK)) {  // next column block of this workgroup: k restarts
             pj = jb_of(++pr);
@@ -198,7 +214,7 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
     // below U's diagonal are branched over (wave-uniform).  LDS reads, barrier and DMA are the same in both.
     auto tile_body = [&](auto full_tag, int jb, int kt) {
         constexpr bool FULL = decltype(full_tag)::value;
-        if (VARIANT == 6 && vbuf && tid == 0) {  // diagnostic: cycle stamp per tile (timing build only)
+        if (STAMP && vbuf && tid == 0) {  // diagnostic: cycle stamp per tile (timing build only)
             vbuf[(int64_t)blockIdx.x * 1024 + dbg_it] = (double)__builtin_amdgcn_s_memtime();
             if (dbg_it == 0 || (jb == nJ - 1 && kt == nJ * (BN / BK) - 1))  // 100 MHz wall clock at both ends (S = 1)
                 vbuf[(int64_t)blockIdx.x * 1024 + (dbg_it == 0 ? 1000 : 1001)] = (double)__builtin_amdgcn_s_memrealtime();
@@ -210,7 +226,7 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
         //  keep almost the same amount of work: column tile WQ ni + wq is needed iff it is >= kt')
         int ni_min = (kt - jb * (BN / BK) - wq + WQ - 1) / WQ;
         ni_min = ni_min < 0 ? 0 : ni_min;
-        if (VARIANT == 2) ni_min = 0;
+        if (TV == 2) ni_min = 0;
         auto mfma8 = [&](const double (&af)[MI], const double (&bf)[NI], int nlo) {
 #pragma unroll
             for (int ni = nlo; ni < nlo + NI / 2; ++ni) {
@@ -232,14 +248,33 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
         __builtin_amdgcn_sched_barrier(0);
         mfma8(a1, b1, NI / 2);
         __builtin_amdgcn_sched_barrier(0);
-        if (VARIANT != 1 && VARIANT != 3) {
+        if (TV != 1 && TV != 3) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // own share of tile t+1 has landed
             __builtin_amdgcn_s_barrier();
         }
         // tile t+2 goes into the stage tile t-1 occupied (free since this barrier).  Issuing the six DMAs keeps a
-        // wave from feeding the matrix pipe for a few hundred cycles and the two waves of a SIMD leave the
+        // wave from feeding the matrix pipe for a while and the two waves of a SIMD leave the
         // barrier together: column group 0 issues here, column group 1 at the end of the tile.
-        const bool do_stage = pj < nJ && VARIANT != 1 && VARIANT != 4;
+        //
+        // What a full k tile costs beyond its 8,192 cycles of MFMA issue, split with the timing variants (MI355X, N = 4096,
+        // 2^21 candidates, launches of eight column groups; stamped builds, cycles per tile | launch time, un-stamped):
+        //                                      global_load_lds pieces     buffer_load ... lds pieces (today)
+        //   product loop                       8,752 | 30.66 ms           8,536 | 29.94 ms
+        //   no barrier (3)                     8,616 | 30.36              8,488 | 30.09
+        //   no DMA (4)                         8,456 | 29.69              8,456 | 29.60
+        //   no barrier, no DMA (1)             8,440 | 29.64              8,456 | 29.57
+        // With global_load_lds the DMA issue was the larger share (296 cycles against 136 for the barrier): every piece took a
+        // v_lshl_add_u64 for its 64-bit address, all six into ONE register pair (each had to wait until the load in front of
+        // it had read that pair), on the vector issue port that the SIMD partner's MFMAs need.  As buffer loads the pieces
+        // take scalar instructions only (glds16): -216 cycles per tile, 506.8 -> 494.2 ms per step on one box, same bits.
+        // The rest is 80 cycles of DMA issue, a barrier that now costs nothing (the loop is no faster without it) and 264
+        // cycles that remain with neither (the fragment reads and their address arithmetic).
+        // Tried beside it on the same box, all slower, per step: the six pieces spread over the MFMA groups of the half tile,
+        // one or two per group (global form 517 / 520 ms against 507; buffer form 508 / 501 against 494: a piece issued among
+        // MFMAs stalls more often than six in a row do); s_setprio 1 for waves 4-7 in front of the loop (517 against 507 with the
+        // global form, 493.8 against 494.2 = nothing with the buffer form; with the spread pieces 511 / 501); waves 4-7
+        // meeting the barrier at the head of their tile, i.e. running half a tile behind waves 0-3 (523 / 519 ms).
+        const bool do_stage = pj < nJ && TV != 1 && TV != 4;
         if (do_stage && wq == 0) stage_next();
         __builtin_amdgcn_sched_barrier(0);
         mfma8(a0, b0, 0);
@@ -826,7 +861,9 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, i
 #endif
     // Measured on MI355X (N=512, M=2^20): running K(X*,X) of chunk c+1 beside the variance kernel of chunk c gains
     // nothing - the variance launches slow down by what the overlap hides (0.59 -> 0.70 ms), i.e. fp64 VALU work
-    // and fp64 MFMA work do not co-execute on gfx950.  Kept as an opt-in (GPBO_OVERLAP=1) for other shapes.
+    // and fp64 MFMA work do not co-execute on gfx950.  The same at N = 4096, 2^21 candidates (same box, two runs each):
+    // 507.0 / 507.6 ms per step without, 508.4 / 507.3 ms with; the variance launches 30.67 -> 31.54 ms, which is the
+    // 0.9 ms of the K(X*,X) launch that ran beside them.  Kept as an opt-in (GPBO_OVERLAP=1) for other shapes.
     const int64_t nchunks = (M + chunk - 1) / chunk;
     Helper *hp = (nchunks > 1 && overlap_env) ? helper_for_current_device() : nullptr;
     // Fork: the helper stream builds K(X*,X)+mu of chunk c+1 (fp64 VALU + HBM writes) while the caller's
@@ -908,10 +945,27 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, i
         static const int xg_env = getenv("GPBO_F64_GROUPS") ? atoi(getenv("GPBO_F64_GROUPS")) : 8;
         if (xg_env > 1 && S == 1 && M >= 32768 && Np / BN >= 2 * xg_env && xg_env <= 16 && n_prefix == 0) {
             const int64_t grid1 = (nblk + 7) / 8 * 8 * xg_env;
-            hipLaunchKernelGGL(sigma_acq_kernel<0>, dim3((unsigned)grid1), dim3(NW * 64), 0, st, KsT[b], chunk, U, (int)Np,
-                               mu_part[b], nsl, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,
-                               (double *)nullptr, (double *)nullptr, (double *)nullptr, part_val + nparts,
-                               part_idx + nparts, nan_count, (double *)nullptr, ss_part, xg_env, (int)nblk, 0);
+            // (diagnostics build: the stamps of a stamped variant go to the other chunk buffer, free during the last chunk)
+#define GPBO_SIGMA_XG_LAUNCH(V)                                                                                       \
+    hipLaunchKernelGGL(sigma_acq_kernel<V>, dim3((unsigned)grid1), dim3(NW * 64), 0, st, KsT[b], chunk, U, (int)Np,        \
+                       mu_part[b], nsl, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,                        \
+                       (double *)nullptr, (double *)nullptr, (double *)nullptr, part_val + nparts,                  \
+                       part_idx + nparts, nan_count,                                                                 \
+                       ((V == 6 || V >= 8) && c == nchunks - 1 && nchunks > 1) ? KsT[(c + 1) & 1] : (double *)nullptr, \
+                       ss_part, xg_env, (int)nblk, 0)
+#ifdef GPBO_DIAGNOSTICS
+            if (variant == 1) GPBO_SIGMA_XG_LAUNCH(1);
+            else if (variant == 3) GPBO_SIGMA_XG_LAUNCH(3);
+            else if (variant == 4) GPBO_SIGMA_XG_LAUNCH(4);
+            else if (variant == 6) GPBO_SIGMA_XG_LAUNCH(6);
+            else if (variant == 9) GPBO_SIGMA_XG_LAUNCH(9);
+            else if (variant == 11) GPBO_SIGMA_XG_LAUNCH(11);
+            else if (variant == 12) GPBO_SIGMA_XG_LAUNCH(12);
+            else GPBO_SIGMA_XG_LAUNCH(0);
+#else
+            GPBO_SIGMA_XG_LAUNCH(0);
+#endif
+#undef GPBO_SIGMA_XG_LAUNCH
             hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, xg_env, chunk, mu_part[b],
                                nsl, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,
                                mu_out ? mu_out + s : nullptr, sigma_out ? sigma_out + s : nullptr,

@@ -1,0 +1,155 @@
+"""The fp64 variance kernel (csrc/sigma_acq.hip) bit for bit against recorded results.
+
+Changes to the tile loop of `sigma_acq_kernel` (scheduling of the barrier, the LDS-DMA issue, wave priorities) must leave
+every accumulator's k order, the MFMA k grouping and the reduction tree of |v|^2 as they were: mu, sigma, the acquisition,
+the result record (best value, index, NaN count) and the qEI values are then the SAME BITS.  tests/golden/sigma_bits_*.npz
+were recorded on an MI355X from the library as it was before the first such change (`python tests/test_gpu_sigma_bits.py
+--record`, which computes every case twice and refuses to write a case that is not reproducible), on Sobol problems of
+bayesian_optimisation_amd/synthetic.py:
+
+  n2048   N = 2048, M = 32768, dense LCB and EI: launches of eight column groups per candidate tile + split_finish_kernel
+  n384    N = 384, M = 4096, dense LCB and EI: plain launches (one workgroup per candidate tile, own epilogue)
+  qei     N = 2048, 4,096 candidates, score_qei(dense=True): the GRAM instantiation
+  screens N = 2048, M = 32768: score_bound after factorise(order="fps") (prefix mode, ncb > 0, and the column-split
+          launches S > 1 of the re-scoring) and score_i8c after prepare_i8() (column-split re-scoring): the result record
+          and `last_screen`
+
+Every comparison is np.array_equal / ==: no tolerance."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+GOLDEN = os.path.join(REPO, "tests", "golden")
+
+pytestmark = pytest.mark.gpu
+
+
+def _dense_case(N, M):
+    from bayesian_optimisation_amd import DeviceGP
+    from bayesian_optimisation_amd.synthetic import make_problem
+
+    X, y, Xs, ls = make_problem(N, M, 8)
+    gp = DeviceGP().factorise(X, y, ls)
+    out = {}
+    for name, kw in (("lcb", dict(acquisition="lcb", explore=4.0)), ("ei", dict(acquisition="ei", f_best=float(y.min())))):
+        r = gp.score(Xs, dense=True, **kw)
+        out[f"mu_{name}"] = r.mu.cpu().numpy()
+        out[f"sigma_{name}"] = r.sigma.cpu().numpy()
+        out[f"acq_{name}"] = r.acq.cpu().numpy()
+        out[f"result_{name}"] = np.array([r.best_val, float(r.best_idx), float(r.nan_count)])
+    return out
+
+
+def _split_dense(out):
+    """N = 2048: three files below the repository's size limit for one file (mu and sigma do not depend on the acquisition:
+    stored once, asserted equal for both)."""
+    assert np.array_equal(out["mu_lcb"], out["mu_ei"]) and np.array_equal(out["sigma_lcb"], out["sigma_ei"])
+    return {"mu_sigma": {"mu": out["mu_lcb"], "sigma": out["sigma_lcb"]},
+            "lcb": {"acq": out["acq_lcb"], "result": out["result_lcb"]},
+            "ei": {"acq": out["acq_ei"], "result": out["result_ei"]}}
+
+
+def _case_n2048():
+    parts = _split_dense(_dense_case(2048, 32768))
+    return {f"n2048_{k}": v for k, v in parts.items()}
+
+
+def _case_n384():
+    out = _dense_case(384, 4096)
+    assert np.array_equal(out["mu_lcb"], out["mu_ei"]) and np.array_equal(out["sigma_lcb"], out["sigma_ei"])
+    return {"n384": out}
+
+
+def _case_qei():
+    from bayesian_optimisation_amd import DeviceGP
+    from bayesian_optimisation_amd.synthetic import make_problem
+
+    X, y, Xs, ls = make_problem(2048, 4096, 8)
+    gp = DeviceGP().factorise(X, y, ls)
+    Z = np.random.default_rng(7).standard_normal((64, 8))
+    r = gp.score_qei(Xs, Z, f_best=float(y.min()), dense=True)
+    return {"qei": {"qei": r.acq.cpu().numpy(), "result": np.array([r.best_val, float(r.best_idx), float(r.nan_count)])}}
+
+
+def _case_screens():
+    from bayesian_optimisation_amd import DeviceGP
+    from bayesian_optimisation_amd.synthetic import make_problem
+
+    X, y, Xs, ls = make_problem(2048, 32768, 8)
+    out = {}
+    gp = DeviceGP().factorise(X, y, ls, order="fps")
+    r = gp.score_bound(Xs)
+    out["bound_result"] = np.array([r.best_val, float(r.best_idx), float(r.nan_count)])
+    out["bound_screen"] = np.array(json.dumps(gp.last_screen, sort_keys=True))
+    gp = DeviceGP().factorise(X, y, ls)
+    gp.prepare_i8()
+    r = gp.score_i8c(Xs)
+    out["i8c_result"] = np.array([r.best_val, float(r.best_idx), float(r.nan_count)])
+    out["i8c_screen"] = np.array(json.dumps(gp.last_screen, sort_keys=True))
+    return {"screens": out}
+
+
+CASES = {"n2048": _case_n2048, "n384": _case_n384, "qei": _case_qei, "screens": _case_screens}
+FILES = {"n2048": ("n2048_mu_sigma", "n2048_lcb", "n2048_ei"), "n384": ("n384",), "qei": ("qei",), "screens": ("screens",)}
+
+
+def _same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    if a.dtype.kind in "US":
+        return json.loads(str(a)) == json.loads(str(b))
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+def _load(name):
+    return dict(np.load(os.path.join(GOLDEN, f"sigma_bits_{name}.npz"), allow_pickle=False))
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_variance_kernel_bits_equal_the_recorded_ones(case):
+    got = CASES[case]()
+    assert set(got) == set(FILES[case])
+    for fname, arrays in got.items():
+        want = _load(fname)
+        assert set(arrays) == set(want), fname
+        for key in sorted(want):
+            if not _same(arrays[key], want[key]):
+                a, b = np.asarray(arrays[key]), np.asarray(want[key])
+                detail = (f"{int(np.sum(a != b))} of {a.size} entries differ, max |diff| {np.max(np.abs(a - b)):.3e}"
+                          if a.dtype.kind == "f" and a.shape == b.shape else f"{a} != {b}")
+                pytest.fail(f"sigma_bits_{fname}.npz[{key}]: {detail}")
+
+
+def _record(check_only=False):
+    bad = 0
+    for case in sorted(CASES):
+        first, second = CASES[case](), CASES[case]()
+        for fname in first:
+            ok = all(_same(first[fname][k], second[fname][k]) for k in first[fname])
+            if not ok:
+                print(f"NOT REPRODUCIBLE: {fname}")
+                bad += 1
+                continue
+            path = os.path.join(GOLDEN, f"sigma_bits_{fname}.npz")
+            if check_only:
+                want = _load(fname)
+                same = set(want) == set(first[fname]) and all(_same(first[fname][k], want[k]) for k in want)
+                print(f"{fname}: {'equal' if same else 'DIFFERENT'}")
+                bad += 0 if same else 1
+            else:
+                np.savez_compressed(path, **first[fname])
+                print(f"{fname}: wrote {os.path.getsize(path)} bytes", {k: np.asarray(v).shape for k, v in first[fname].items()})
+    return bad
+
+
+if __name__ == "__main__":
+    # --record [DIR]: write the fixtures (to DIR instead of tests/golden); --check: compare without pytest
+    if len(sys.argv) > 2:
+        GOLDEN = os.path.abspath(sys.argv[2])
+        os.makedirs(GOLDEN, exist_ok=True)
+    sys.exit(1 if _record(check_only=sys.argv[1:2] == ["--check"]) else 0)
