@@ -1040,7 +1040,7 @@ int gpbo_cholinv_run(double *S, int64_t ld, int64_t Np, int32_t *info, const int
 #ifdef GPBO_DIAGNOSTICS
     // GPBO_CI_STAMPS=1 (timing builds only): cycle stamps of workgroup 0 of every PAIR launch, averaged and printed
     static unsigned long long *dstamps = nullptr;
-    const bool want_stamps = getenv("GPBO_CI_STAMPS") && atoi(getenv("GPBO_CI_STAMPS"));
+    const bool want_stamps = env_flag("GPBO_CI_STAMPS");
     if (want_stamps && !dstamps && hipMalloc(&dstamps, 8 * 8 * 1024) != hipSuccess) return GPBO_ERR_LAUNCH;
     int npair = 0;
 #endif
@@ -1048,7 +1048,7 @@ int gpbo_cholinv_run(double *S, int64_t ld, int64_t Np, int32_t *info, const int
     // GPBO_CI_CEILING (timing builds only, WRONG results): what ANY scheduler of these tiles could reach.
     //   1: the critical path alone - the NEAR and PAIR launches without their filler tiles;
     //   2: the work alone - every update tile of the plan in ONE launch, no dependencies, no PAIR workgroups.
-    static const int ceiling = getenv("GPBO_CI_CEILING") ? atoi(getenv("GPBO_CI_CEILING")) : 0;
+    static const int ceiling = env_int("GPBO_CI_CEILING", 0);
     if (ceiling == 2) {
         a.near = CiNear{0, 0, 0, 0, 0, 0, 0, 0};
         a.l = CiLaunch{-1, 0, 0, (int)dp->plan.tiles.size(), 1};
@@ -1173,7 +1173,7 @@ extern "C" int gpbo_cholinv_tiles_f64(double *S, int64_t ld, int64_t Np, int32_t
     a.near = CiNear{0, 0, 0, 0, 0, 0, 0, 0};
 #ifdef GPBO_DIAGNOSTICS
     unsigned long long *dst = nullptr;
-    const bool want_stamps = getenv("GPBO_CI_STAMPS") && atoi(getenv("GPBO_CI_STAMPS")) && pair < 0;
+    const bool want_stamps = env_flag("GPBO_CI_STAMPS") && pair < 0;
     if (want_stamps && hipMalloc(&dst, 8 * 8 * 1024) == hipSuccess) {
         (void)hipMemset(dst, 0, 8 * 8 * 1024);
         a.stamps = dst;

@@ -173,7 +173,7 @@ static int potrf_run(double *Kp, int64_t Np, double *dinv, int32_t *info, bool i
     // Measured on MI355X (GPBO_NO_LOOKAHEAD=1 against 0, whole factorisation): N = 2048: 1.17 -> 1.49 ms, N = 4096:
     // 3.18 -> 3.44 ms (two events and two waits per group cost more than the ~25 us of diagonal block + panel they hide),
     // N = 8192: 12.9 -> 12.3 ms - so it is used from N = 8192 up only.
-    static const bool la_env = !(getenv("GPBO_NO_LOOKAHEAD") && atoi(getenv("GPBO_NO_LOOKAHEAD")));
+    static const bool la_env = !env_flag("GPBO_NO_LOOKAHEAD");
     LookAhead *la = (Np >= 8192 && la_env) ? lookahead_for_current_device() : nullptr;
     bool rest_pending = false;  // a helper-stream update has been issued and not yet waited for
     for (int j0 = 0; j0 < nb; j0 += G) {
@@ -310,7 +310,7 @@ extern "C" int gpbo_factorise_f64(const double *X, const double *y, int64_t N, i
     // Round 3: one sweep of row operations over the stacked matrix S = [K | 0] (cholinv.hip) leaves inv(L) in its right
     // half; U is its transpose.  The two-pass chain of round 2 (blocked Cholesky, then the block-recursive triangular
     // inverse) stays behind GPBO_FACTOR_OLD=1 for A/B runs and behind gpbo_potrf_f64 / gpbo_trtri_f64.
-    static const bool old_chain = getenv("GPBO_FACTOR_OLD") && atoi(getenv("GPBO_FACTOR_OLD"));
+    static const bool old_chain = env_flag("GPBO_FACTOR_OLD");
     // (the fused sweep's plan stops at Np = 32768 - 32-bit tile offsets; beyond, the two-pass chain, which has no such cap)
     if (!old_chain && Np <= GPBO_CHOLINV_MAX_NP) {
         double *S = L;  // [Np x 2 Np]: the same 2 Np^2 doubles
@@ -319,7 +319,7 @@ extern "C" int gpbo_factorise_f64(const double *X, const double *y, int64_t N, i
         // GPBO_CI_OPTS="win,far_k,far_kind,defer+1,group_from+1,small_w": schedule choices of the plan for A/B runs (cholinv_plan.h)
         static int env_opt[7] = {0, 0, 0, 0, 0, 0, 0};
         static const bool have_env_opt = [] {
-            const char *e = getenv("GPBO_CI_OPTS");
+            const char *e = env_str("GPBO_CI_OPTS");
             return e && sscanf(e, "%d,%d,%d,%d,%d,%d", &env_opt[0], &env_opt[1], &env_opt[2], &env_opt[3], &env_opt[5], &env_opt[6]) >= 1;
         }();
         rc = gpbo_cholinv_run(S, 2 * Np, Np, info, have_env_opt ? env_opt : nullptr, gpbo_stream(stream));

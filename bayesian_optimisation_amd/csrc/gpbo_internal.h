@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/gpbo.h"
+#include "host_driver.h"
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -106,17 +107,14 @@ int gpbo_launch_transpose_upper(const double *W, int64_t Np, double *U, hipStrea
 int gpbo_launch_argmax_finish(const double *part_val, const int64_t *part_idx, int64_t nparts,
                               const unsigned long long *nan_count, gpbo_result *result, hipStream_t st);
 int64_t gpbo_posterior_workspace_bytes_split(int64_t Np, int64_t chunk, int64_t M, int split_max);
-int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
-                                 const double *ls_host, const double *U, const double *alpha, double prior_var,
-                                 int32_t acq_kind, double p0, double p1, double diag_add, int64_t idx_offset,
-                                 int64_t chunk, double *mu_out, double *sigma_out, double *acq_out, gpbo_result *result,
-                                 void *work, int64_t work_bytes, gpbo_profile *prof, int split_max, int64_t n_prefix,
-                                 void *stream);
+// the fp64 pass behind every extern "C" scoring entry of sigma_acq.hip (split_max, n_prefix: see its definition); out.var unused
+int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp, const Acquisition &acq, double diag_add,
+                                 int64_t idx_offset, int64_t chunk, const DenseOut &out, gpbo_result *result, void *work,
+                                 int64_t work_bytes, gpbo_profile *prof, int split_max, int64_t n_prefix, void *stream);
 #define GPBO_RESCORE_SPLIT_MAX 64
 int gpbo_gemm_launch_tri(int transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
                          int64_t strideA, const double *B, int64_t ldb, int64_t strideB, double beta, double *C,
                          int64_t ldc, int64_t strideC, int batch, int lower_only, int tri, hipStream_t st);
 int gpbo_launch_split_finish(const double *ss_part, int S, int64_t ldk, const double *mu_part, int nsl, int64_t Mc,
-                             double prior_var, int acq_kind, double p0, double p1, int64_t idx_base, double *mu_out,
-                             double *sigma_out, double *acq_out, double *var_out, double *part_val, int64_t *part_idx,
-                             unsigned long long *nan_count, hipStream_t st);
+                             double prior_var, const Acquisition &acq, int64_t idx_base, const DenseOut &out,
+                             double *part_val, int64_t *part_idx, unsigned long long *nan_count, hipStream_t st);

@@ -56,15 +56,10 @@ extern "C" int gpbo_select_next_host_f64(const double *X, const double *y, int64
                                          int32_t *info) {
     if (!X || !y || !ls || !Xs || !result || !info) return GPBO_ERR_ARG;
     if (N < 1 || M < 1 || d < 1 || d > GPBO_MAX_D_ANY) return GPBO_ERR_ARG;
-    if (acq_kind != GPBO_ACQ_LCB && acq_kind != GPBO_ACQ_EI) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
     if (chunk == 0) chunk = (int64_t)1 << 17;
-    if (chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE || chunk > GPBO_CHUNK_MAX) return GPBO_ERR_ARG;
-    for (int k = 0; k < d; ++k)
-        if (!(ls[k] > 0.0)) return GPBO_ERR_ARG;
-    {  // no more chunk than the candidates need
-        const int64_t need = (M + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
-        if (chunk > need) chunk = need;
-    }
+    if (!chunk_ok(chunk) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    chunk = clamp_chunk(chunk, M);
     const int64_t Np = gpbo_padded_n(N);
     const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
     const int64_t wpost = gpbo_posterior_workspace_bytes(Np, chunk, M);
@@ -136,10 +131,7 @@ extern "C" int gpbo_select_next_host_f64(const double *X, const double *y, int64
             if (!A.d2h(&row, dperm + (*info - 1), sizeof(int64_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
             *info = (int32_t)(row + 1);
         }
-        result->best_val = 0.0;
-        result->best_idx = -1;
-        result->nan_count = 0;
-        result->reserved = 0;
+        *result = {0.0, -1, 0, 0};
         return A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
     }
     const double prior_var = (1.0 + jitter1) + jitter2;  // diagonal of cov_pred as the reference rounds it
@@ -178,13 +170,8 @@ extern "C" int gpbo_select_qei_host_f64(const double *X, const double *y, int64_
     if (!X || !y || !ls || !Xs || !Z || !result || !info) return GPBO_ERR_ARG;
     if (N < 1 || M < 8 || M % 8 || d < 1 || d > GPBO_MAX_D || S < 1) return GPBO_ERR_ARG;
     if (chunk == 0) chunk = (int64_t)1 << 15;
-    if (chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE || chunk > GPBO_CHUNK_MAX) return GPBO_ERR_ARG;
-    for (int k = 0; k < d; ++k)
-        if (!(ls[k] > 0.0)) return GPBO_ERR_ARG;
-    {
-        const int64_t need = (M + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
-        if (chunk > need) chunk = need;
-    }
+    if (!chunk_ok(chunk) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    chunk = clamp_chunk(chunk, M);
     const int64_t Np = gpbo_padded_n(N);
     const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
     const int64_t wq = gpbo_qei_workspace_bytes(Np, chunk, M);
@@ -207,10 +194,7 @@ extern "C" int gpbo_select_qei_host_f64(const double *X, const double *y, int64_
     if (rc != GPBO_OK) return rc;
     if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
     if (*info != 0) {
-        result->best_val = 0.0;
-        result->best_idx = -1;
-        result->nan_count = 0;
-        result->reserved = 0;
+        *result = {0.0, -1, 0, 0};
         return GPBO_OK;
     }
     const double prior_var = (1.0 + jitter1) + jitter2;
@@ -271,9 +255,7 @@ extern "C" int gpbo_nlml_grid_logdet_host_f64(const double *X, const double *y, 
 
 extern "C" int gpbo_nlml_grad_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls,
                                        double jitter, double *out) {
-    if (!X || !y || !ls || !out || N < 1 || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
-    for (int k = 0; k < d; ++k)
-        if (!(ls[k] > 0.0)) return GPBO_ERR_ARG;
+    if (!X || !y || !ls || !out || N < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
     const int64_t Np = gpbo_padded_n(N);
     const int64_t wfact = gpbo_factorise_workspace_bytes(Np), wgrad = gpbo_nlml_grad_workspace_bytes(Np, d);
     if (wgrad < 0) return GPBO_ERR_ARG;

@@ -1,0 +1,133 @@
+// Host-side plumbing shared by the scoring drivers (sigma_acq.hip, posterior_f32.hip, ozaki.hip, rescore.hip, host_api.hip)
+// and the launchers below them: size arithmetic, the argument refusals, environment switches, the profile-slot bookkeeping,
+// the dense outputs of a chunk, the model / acquisition views.  Host only: no device code in this file.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "../../include/gpbo.h"
+
+#pragma GCC visibility push(hidden)   // nothing here is part of the library's interface
+
+// ---- sizes -------------------------------------------------------------------------------------------------------------
+inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+inline int64_t round_up_granule(int64_t M) { return align_up(M, GPBO_CHUNK_GRANULE); }
+// no more chunk than M candidates need
+inline int64_t clamp_chunk(int64_t chunk, int64_t M) {
+    const int64_t need = round_up_granule(M);
+    return chunk > need ? need : chunk;
+}
+
+// ---- refusals (each entry point keeps its own order of checks: GPBO_ERR_ARG before GPBO_ERR_WORKSPACE before any HIP call)
+inline bool chunk_ok(int64_t chunk) {
+    return chunk >= GPBO_CHUNK_GRANULE && chunk % GPBO_CHUNK_GRANULE == 0 && chunk <= GPBO_CHUNK_MAX;
+}
+inline bool acq_kind_ok(int32_t kind) { return kind == GPBO_ACQ_LCB || kind == GPBO_ACQ_EI; }
+inline bool np_ok(int64_t Np) { return Np >= GPBO_NPAD && Np % GPBO_NPAD == 0; }   // a padded size of the fp64 / int8 routes
+inline bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+inline bool length_scales_ok(const double *ls, int d) {
+    for (int k = 0; k < d; ++k)
+        if (!(ls[k] > 0.0)) return false;
+    return true;
+}
+
+// ---- environment switches (include/gpbo.h lists them; a caller that wants one read per process keeps it in a static const)
+inline const char *env_str(const char *name) { return getenv(name); }
+inline int env_int(const char *name, int dflt) {
+    const char *e = env_str(name);
+    return e ? atoi(e) : dflt;
+}
+inline bool env_flag(const char *name) { return env_int(name, 0) != 0; }
+
+// Column groups of the fp64 variance kernel (sigma_acq.hip) for a call of M candidates, 1 = none: a rule of the PROBLEM
+// (N, candidates of the call), never of the chunking, so results stay chunk-size invariant bit for bit.  GPBO_F64_GROUPS=1
+// switches it off (A/B runs).  Both drivers of that kernel ask here.
+inline int f64_column_groups(int64_t M, int64_t Np) {
+    static const int g = env_int("GPBO_F64_GROUPS", 8);
+    return (g > 1 && g <= 16 && M >= 32768 && Np / GPBO_NPAD >= 2 * g) ? g : 1;
+}
+
+// ---- the model and the acquisition, filled once at each extern "C" entry ----------------------------------------------------
+struct GpModel {
+    const double *X;   // [N x d] observations (device)
+    int64_t N, Np;
+    int32_t d;
+    const double *ls_host;
+    const double *U;   // (L^-1)^T in fp64; null on the routes that bring their own copy of it (int8 slices)
+    const double *alpha;
+    double prior_var;
+};
+struct Acquisition {
+    int32_t kind;   // GPBO_ACQ_*
+    double p0, p1;
+};
+
+// ---- dense outputs of a call (each optional); at(s): those of the chunk that starts at candidate s, null stays null ------------
+struct DenseOut {
+    double *mu, *sigma, *acq, *var;
+    static double *shift(double *p, int64_t s) { return p ? p + s : nullptr; }
+    DenseOut at(int64_t s) const { return {shift(mu, s), shift(sigma, s), shift(acq, s), shift(var, s)}; }
+};
+
+// ---- profile slots ---------------------------------------------------------------------------------------------------------
+// One slot of a gpbo_profile per chunk:  [kbegin |] K(X*,X) | begin | variance launch | end [| qEI launch | qend].  The launches
+// of a call form one chain on the stream, so the event in front of the variance launch ends the K(X*,X) interval, and that
+// interval begins at the previous slot's end event (kmode 2: chunks after the first) or at kbegin (kmode 1).  A full or
+// absent profile turns every call into a no-op that succeeds.  Every method returns false when hipEventRecord fails.
+class ProfileRecorder {
+    gpbo_profile *p_;
+    bool prev_recorded_ = false;   // the previous chunk's variance launch has an end event in the slot before
+    bool rec_ = false;             // the slot in hand is recorded (decided at begin())
+    bool open() const { return p_ && p_->count < p_->capacity; }
+    static bool mark(void *ev, hipStream_t st) { return hipEventRecord(reinterpret_cast<hipEvent_t>(ev), st) == hipSuccess; }
+
+public:
+    explicit ProfileRecorder(gpbo_profile *p) : p_(p) {}
+    // in front of the K(X*,X) launch of the next slot.  timed = false: the launch is not on the variance launches' stream
+    // (kmode 0).  may_chain = false: first chunk of a call, or a driver with another launch between `end` and here.
+    bool kstar(hipStream_t st, bool may_chain, bool timed = true) {
+        if (!open()) return true;
+        const int i = p_->count;
+        if (!timed) {
+            p_->kmode[i] = 0;
+            return true;
+        }
+        const bool chained = may_chain && i > 0 && prev_recorded_;
+        p_->kmode[i] = chained ? 2 : 1;
+        return chained || mark(p_->kbegin[i], st);
+    }
+    // in front of the variance launch
+    bool begin(hipStream_t st) {
+        rec_ = open();
+        return !rec_ || mark(p_->begin[p_->count], st);
+    }
+    // behind the variance launch; the slot stays in hand (a qEI launch follows)
+    bool end_open(hipStream_t st) { return !rec_ || mark(p_->end[p_->count], st); }
+    // behind the variance launch: the slot is complete
+    bool end(hipStream_t st, int64_t cands) {
+        if (!end_open(st)) return false;
+        close(cands);
+        return true;
+    }
+    // behind the qEI launch: the slot is complete
+    bool qend(hipStream_t st, int64_t cands) {
+        if (rec_) {
+            if (!mark(p_->qend[p_->count], st)) return false;
+            p_->qmode[p_->count] = 1;
+        }
+        close(cands);
+        return true;
+    }
+
+private:
+    void close(int64_t cands) {
+        if (rec_) {
+            p_->cands[p_->count] = cands;
+            ++p_->count;
+        }
+        prev_recorded_ = rec_;
+    }
+};
+
+#pragma GCC visibility pop

@@ -310,7 +310,7 @@ int gpbo_kstar_mu_anyd(const double *Xs, int64_t Mc, const double *X, int64_t N,
     double *lsd = nullptr;
     int rc = make_ls_anyd(ls_host, d, st, &lsd);
     if (rc != GPBO_OK) return rc;
-    const int64_t used = (Mc + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
+    const int64_t used = round_up_granule(Mc);
     hipLaunchKernelGGL(kstar_mu_anyd_kernel, dim3((unsigned)(used / 256), (unsigned)(Np / KS_SLICE)), dim3(256), 0, st, Xs, Mc, X,
                        (int)N, (int)d, lsd + d, alpha, diag_add, cand_base, KsT, ldk, mu_part);
     const bool ok = hipGetLastError() == hipSuccess;
@@ -422,12 +422,12 @@ int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t 
     LsArgs ls;
     int rc = make_ls(ls_host, d, &ls);
     if (rc != GPBO_OK) return rc;
-    const int64_t used = (Mc + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
+    const int64_t used = round_up_granule(Mc);
     dim3 grid((unsigned)(used / 512), (unsigned)(Np / KS_SLICE));
     // Timing-only variants (1 = no stores, 3 = stores with a trivial body; wrong results) exist only in a diagnostics
     // build (GPBO_DIAG=1 bayesian_optimisation_amd/csrc/build.sh); the shipped library has no switch into them.
 #ifdef GPBO_DIAGNOSTICS
-    static const int variant = getenv("GPBO_KSTAR_VARIANT") ? atoi(getenv("GPBO_KSTAR_VARIANT")) : 0;
+    static const int variant = env_int("GPBO_KSTAR_VARIANT", 0);
 #else
     constexpr int variant = 0;
 #endif
@@ -465,7 +465,7 @@ int gpbo_kstar_mu_mixed(const double *Xs, int64_t Mc, const double *Xsc, int64_t
     LsArgs ls;
     int rc = make_ls(ls_host, d, &ls);
     if (rc != GPBO_OK) return rc;
-    const int64_t used = (Mc + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
+    const int64_t used = round_up_granule(Mc);
     dim3 grid((unsigned)(used / 512), (unsigned)(Np / KS_SLICE));
     const bool nt = (int64_t)sizeof(float) * Np * ldk > ((int64_t)1 << 30);
 #define CALL(DD)                                                                                                     \

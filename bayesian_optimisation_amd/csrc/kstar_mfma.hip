@@ -296,8 +296,6 @@ __global__ __launch_bounds__(256) void kstar_mu_mfma_kernel(const double *__rest
     }
 }
 
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace
 
 // observations per workgroup = per partial of the mean (mu_part has Np / slice rows): the candidate operands of a wave
@@ -346,7 +344,7 @@ int gpbo_kstar_mu_mfma(const double *Xs, int64_t Mc, int64_t N, int64_t Np, int3
     const double *Bp = reinterpret_cast<const double *>(prep_buf);
     const ObsPrep *prep = reinterpret_cast<const ObsPrep *>(reinterpret_cast<const char *>(prep_buf) +
                                                             align_up((int64_t)sizeof(double) * Np * KP_MAX, 256));
-    const int64_t used = (Mc + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
+    const int64_t used = round_up_granule(Mc);
     const int OB = gpbo_kstar_mfma_slice(Np);
     dim3 grid((unsigned)(used / 256), (unsigned)(Np / OB));
 #define GPBO_KM_LAUNCH(Q)                                                                                              \

@@ -842,8 +842,6 @@ __global__ __launch_bounds__(512) void sigma_i8c_kernel(const char *__restrict__
     if (tid < CBM) ss_part[(int64_t)grp * ldk + (int64_t)tile * CBM + tid] = red[tid] + red[CBM + tid];
 }
 
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 struct LayoutI8 {
     int64_t a8_off, mup_off, xsc_off, pval_off, pidx_off, nan_off, ssp_off, total, nparts_cap;
 };
@@ -894,12 +892,12 @@ extern "C" int gpbo_i8_stamps_read(unsigned long long *out4_host, int reset) {
 #endif
 
 extern "C" int64_t gpbo_prepare_i8_bytes(int64_t Np) {
-    if (Np < GPBO_NPAD || Np % GPBO_NPAD || Np > GPBO_I8_MAX_N) return GPBO_ERR_ARG;
+    if (!np_ok(Np) || Np > GPBO_I8_MAX_N) return GPBO_ERR_ARG;
     return align_up(Np * Np * NS, 256) + 2 * align_up((int64_t)sizeof(double) * Np, 256);
 }
 
 extern "C" int gpbo_prepare_i8(const double *U, int64_t Np, void *u8, int64_t u8_bytes, void *stream) {
-    if (!U || !u8 || ((uintptr_t)u8 & 255)) return GPBO_ERR_ARG;
+    if (!U || !u8 || !aligned_to(u8, 256)) return GPBO_ERR_ARG;
     const int64_t need = gpbo_prepare_i8_bytes(Np);
     if (need < 0) return GPBO_ERR_ARG;
     if (u8_bytes < need) return GPBO_ERR_WORKSPACE;
@@ -915,23 +913,23 @@ extern "C" int gpbo_prepare_i8(const double *U, int64_t Np, void *u8, int64_t u8
 }
 
 extern "C" int64_t gpbo_posterior_workspace_bytes_i8(int64_t Np, int64_t chunk, int64_t M) {
-    if (Np < GPBO_NPAD || Np % GPBO_NPAD || Np > GPBO_I8_MAX_N || chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE ||
-        chunk > GPBO_CHUNK_MAX || M < 1)
-        return GPBO_ERR_ARG;
+    if (!np_ok(Np) || Np > GPBO_I8_MAX_N || !chunk_ok(chunk) || M < 1) return GPBO_ERR_ARG;
     return layout_i8(Np, chunk, M).total;
 }
 
 namespace {
-int posterior_i8_impl(bool coarse, const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
-                      const double *ls_host, const void *u8, const double *alpha, double prior_var, int32_t acq_kind,
-                      double p0, double p1, int64_t idx_offset, int64_t chunk, double *mu_out, double *sigma_out,
-                      double *acq_out, double *var_out, gpbo_result *result, void *work, int64_t work_bytes,
-                      gpbo_profile *prof, void *stream) {
+// gp.U is not read: the int8 slices of U and their column scales come in u8 (gpbo_prepare_i8)
+int posterior_i8_impl(bool coarse, const double *Xs, int64_t M, const GpModel &gp, const void *u8, const Acquisition &acq,
+                      int64_t idx_offset, int64_t chunk, const DenseOut &out, gpbo_result *result, void *work,
+                      int64_t work_bytes, gpbo_profile *prof, void *stream) {
+    const double *X = gp.X, *alpha = gp.alpha, *ls_host = gp.ls_host;
+    const int64_t N = gp.N, Np = gp.Np;
+    const int32_t d = gp.d;
     if (!Xs || !X || !u8 || !alpha || !result || !work || !ls_host) return GPBO_ERR_ARG;
     if (M < 1 || N < 1 || Np != gpbo_padded_n(N) || Np > GPBO_I8_MAX_N || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
-    if (chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE || chunk > GPBO_CHUNK_MAX) return GPBO_ERR_ARG;
-    if (acq_kind != GPBO_ACQ_LCB && acq_kind != GPBO_ACQ_EI) return GPBO_ERR_ARG;
-    if (((uintptr_t)work & 255) || ((uintptr_t)u8 & 255)) return GPBO_ERR_ARG;
+    if (!chunk_ok(chunk)) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq.kind)) return GPBO_ERR_ARG;
+    if (!aligned_to(work, 256) || !aligned_to(u8, 256)) return GPBO_ERR_ARG;
     const LayoutI8 L = layout_i8(Np, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     LsArgsI8 ls;
@@ -954,16 +952,10 @@ int posterior_i8_impl(bool coarse, const double *Xs, int64_t M, const double *X,
     if (rc != GPBO_OK) return rc;
     const int64_t RT = chunk / 32;
     int64_t nparts = 0;
-    bool prev_recorded = false;
+    ProfileRecorder slots(prof);
     for (int64_t s = 0; s < M; s += chunk) {
         const int64_t Mc = (M - s < chunk) ? (M - s) : chunk;
-        const bool rec = prof && prof->count < prof->capacity;
-        if (rec) {
-            const bool chained = s > 0 && prof->count > 0 && prev_recorded;
-            prof->kmode[prof->count] = chained ? 2 : 1;
-            if (!chained && hipEventRecord(reinterpret_cast<hipEvent_t>(prof->kbegin[prof->count]), st) != hipSuccess)
-                return GPBO_ERR_LAUNCH;
-        }
+        if (!slots.kstar(st, s > 0)) return GPBO_ERR_LAUNCH;
         // fragments of whole 128-candidate blocks are read by the variance kernel: build them for every block touched
         const int64_t used = (Mc + 255) / 256 * 256;
         dim3 kgrid((unsigned)(used / 256), (unsigned)(Np / KS_SLICE));
@@ -986,49 +978,33 @@ int posterior_i8_impl(bool coarse, const double *Xs, int64_t M, const double *X,
 #undef CALL
 #undef CALL1
         const int64_t nblk = (Mc + BM - 1) / BM;
-        if (rec && hipEventRecord(reinterpret_cast<hipEvent_t>(prof->begin[prof->count]), st) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
+        if (!slots.begin(st)) return GPBO_ERR_LAUNCH;
         const int G = i8_groups(Np);
+        const DenseOut o = out.at(s);
         int64_t nparts_here = nblk;
-        if (coarse) {   // 256-row tiles, partial sums always finished by split_finish_kernel
-            double *ss_part = reinterpret_cast<double *>(w + L.ssp_off);
+        double *ss_part = reinterpret_cast<double *>(w + L.ssp_off);
+        const bool split = coarse || G > 1;   // partial sums to ss_part, the epilogue in split_finish_kernel
+        if (coarse) {   // 256-row tiles
             const int64_t nblk_c = (Mc + CBM - 1) / CBM;
             const int64_t grid = (G > 1) ? (nblk_c + 7) / 8 * 8 * G : nblk_c;
             hipLaunchKernelGGL(sigma_i8c_kernel, dim3((unsigned)grid), dim3(512), 0, st, A8, RT, U8, (int)Np, colscale, chunk, G,
                                (int)nblk_c, ss_part);
             nparts_here = nblk_c;
-            int rc2 = gpbo_launch_split_finish(ss_part, G, chunk, mu_part, (int)(Np / KS_SLICE), Mc, prior_var, acq_kind, p0, p1,
-                                               idx_offset + s, mu_out ? mu_out + s : nullptr, sigma_out ? sigma_out + s : nullptr,
-                                               acq_out ? acq_out + s : nullptr, var_out ? var_out + s : nullptr,
-                                               part_val + nparts, part_idx + nparts, nan_count, st);
-            if (rc2 != GPBO_OK) return rc2;
-        } else if (G > 1) {
-            double *ss_part = reinterpret_cast<double *>(w + L.ssp_off);
-            const int64_t grid = (nblk + 7) / 8 * 8 * G;
-            hipLaunchKernelGGL(sigma_i8_kernel, dim3((unsigned)grid), dim3(512), 0, st, A8, RT, U8, (int)Np, colscale, mu_part,
-                               (int)(Np / KS_SLICE), chunk, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,
-                               (double *)nullptr, (double *)nullptr, (double *)nullptr, (double *)nullptr, part_val + nparts,
-                               part_idx + nparts, nan_count, G, (int)nblk, ss_part);
-            nparts_here = (Mc + 255) / 256;
-            int rc2 = gpbo_launch_split_finish(ss_part, G, chunk, mu_part, (int)(Np / KS_SLICE), Mc, prior_var, acq_kind, p0, p1,
-                                               idx_offset + s, mu_out ? mu_out + s : nullptr, sigma_out ? sigma_out + s : nullptr,
-                                               acq_out ? acq_out + s : nullptr, var_out ? var_out + s : nullptr,
-                                               part_val + nparts, part_idx + nparts, nan_count, st);
-            if (rc2 != GPBO_OK) return rc2;
         } else {
-            hipLaunchKernelGGL(sigma_i8_kernel, dim3((unsigned)nblk), dim3(512), 0, st, A8, RT, U8, (int)Np, colscale, mu_part,
-                               (int)(Np / KS_SLICE), chunk, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,
-                               mu_out ? mu_out + s : nullptr, sigma_out ? sigma_out + s : nullptr,
-                               acq_out ? acq_out + s : nullptr, var_out ? var_out + s : nullptr, part_val + nparts,
-                               part_idx + nparts, nan_count, 1, (int)nblk, (double *)nullptr);
+            const DenseOut ko = split ? DenseOut{} : o;
+            const int64_t grid = split ? (nblk + 7) / 8 * 8 * G : nblk;
+            hipLaunchKernelGGL(sigma_i8_kernel, dim3((unsigned)grid), dim3(512), 0, st, A8, RT, U8, (int)Np, colscale, mu_part,
+                               (int)(Np / KS_SLICE), chunk, Mc, gp.prior_var, (int)acq.kind, acq.p0, acq.p1, idx_offset + s,
+                               ko.mu, ko.sigma, ko.acq, ko.var, part_val + nparts, part_idx + nparts, nan_count, G, (int)nblk,
+                               split ? ss_part : (double *)nullptr);
+            if (split) nparts_here = (Mc + 255) / 256;
         }
-        if (rec) {
-            if (hipEventRecord(reinterpret_cast<hipEvent_t>(prof->end[prof->count]), st) != hipSuccess)
-                return GPBO_ERR_LAUNCH;
-            prof->cands[prof->count] = Mc;
-            ++prof->count;
+        if (split) {
+            int rc2 = gpbo_launch_split_finish(ss_part, G, chunk, mu_part, (int)(Np / KS_SLICE), Mc, gp.prior_var, acq,
+                                               idx_offset + s, o, part_val + nparts, part_idx + nparts, nan_count, st);
+            if (rc2 != GPBO_OK) return rc2;
         }
-        prev_recorded = rec;
+        if (!slots.end(st, Mc)) return GPBO_ERR_LAUNCH;
         GPBO_CHECK_LAUNCH();
         nparts += nparts_here;
     }
@@ -1042,8 +1018,8 @@ extern "C" int gpbo_posterior_acq_i8(const double *Xs, int64_t M, const double *
                                      double *mu_out, double *sigma_out, double *acq_out, double *var_out,
                                      gpbo_result *result, void *work, int64_t work_bytes, gpbo_profile *prof,
                                      void *stream) {
-    return posterior_i8_impl(false, Xs, M, X, N, Np, d, ls_host, u8, alpha, prior_var, acq_kind, p0, p1, idx_offset, chunk,
-                             mu_out, sigma_out, acq_out, var_out, result, work, work_bytes, prof, stream);
+    return posterior_i8_impl(false, Xs, M, {X, N, Np, d, ls_host, nullptr, alpha, prior_var}, u8, {acq_kind, p0, p1},
+                             idx_offset, chunk, {mu_out, sigma_out, acq_out, var_out}, result, work, work_bytes, prof, stream);
 }
 
 extern "C" int gpbo_posterior_acq_i8c(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
@@ -1052,6 +1028,6 @@ extern "C" int gpbo_posterior_acq_i8c(const double *Xs, int64_t M, const double 
                                       double *mu_out, double *sigma_out, double *acq_out, double *var_out,
                                       gpbo_result *result, void *work, int64_t work_bytes, gpbo_profile *prof,
                                       void *stream) {
-    return posterior_i8_impl(true, Xs, M, X, N, Np, d, ls_host, u8, alpha, prior_var, acq_kind, p0, p1, idx_offset, chunk,
-                             mu_out, sigma_out, acq_out, var_out, result, work, work_bytes, prof, stream);
+    return posterior_i8_impl(true, Xs, M, {X, N, Np, d, ls_host, nullptr, alpha, prior_var}, u8, {acq_kind, p0, p1},
+                             idx_offset, chunk, {mu_out, sigma_out, acq_out, var_out}, result, work, work_bytes, prof, stream);
 }

@@ -244,8 +244,6 @@ __global__ __launch_bounds__(512) void sigma_acq_f32_kernel(
     }
 }
 
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 struct Layout32 {
     int64_t kst_off, mup_off, xsc_off, pval_off, pidx_off, nan_off, total, nparts_cap;
 };
@@ -296,8 +294,8 @@ extern "C" int gpbo_posterior_acq_f32(const double *Xs, int64_t M, const double 
     if (!Xs || !X || !U32 || !alpha || !result || !work) return GPBO_ERR_ARG;
     if (M < 1 || N < 1 || Np32 != gpbo_padded_n_f32(N)) return GPBO_ERR_ARG;
     if (chunk < 1024 || chunk % 1024 || chunk > GPBO_CHUNK_MAX) return GPBO_ERR_ARG;
-    if (acq_kind != GPBO_ACQ_LCB && acq_kind != GPBO_ACQ_EI) return GPBO_ERR_ARG;
-    if (((uintptr_t)work & 255) || ((uintptr_t)U32 & 15)) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
+    if (!aligned_to(work, 256) || !aligned_to(U32, 16)) return GPBO_ERR_ARG;
     const Layout32 L = layout32(Np32, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
@@ -312,36 +310,22 @@ extern "C" int gpbo_posterior_acq_f32(const double *Xs, int64_t M, const double 
     int rc = gpbo_scale_points_launch(X, N, Np32, d, ls_host, Xsc, nan_count, stream);
     if (rc != GPBO_OK) return rc;
     int64_t nparts = 0;
-    bool prev_recorded = false;
+    const DenseOut out = {mu_out, sigma_out, acq_out, var_out};
+    ProfileRecorder slots(prof);
     for (int64_t s = 0; s < M; s += chunk) {
         const int64_t Mc = (M - s < chunk) ? (M - s) : chunk;
         // K(X*,X) launches are timed like the fp64 path's: the launches of this call form one chain on the stream
-        const bool krec = prof && prof->count < prof->capacity;
-        if (krec) {
-            const bool chained = s > 0 && prof->count > 0 && prev_recorded;
-            prof->kmode[prof->count] = chained ? 2 : 1;
-            if (!chained && hipEventRecord(reinterpret_cast<hipEvent_t>(prof->kbegin[prof->count]), st) != hipSuccess)
-                return GPBO_ERR_LAUNCH;
-        }
+        if (!slots.kstar(st, s > 0)) return GPBO_ERR_LAUNCH;
         rc = gpbo_kstar_mu_mixed(Xs + s * d, Mc, Xsc, N, Np32, d, ls_host, alpha, diag_add, idx_offset + s, KsT, chunk,
                                  mu_part, stream);
         if (rc != GPBO_OK) return rc;
         const int64_t nblk = (Mc + BM - 1) / BM;
-        const bool rec = krec;
-        if (rec && hipEventRecord(reinterpret_cast<hipEvent_t>(prof->begin[prof->count]), st) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
+        if (!slots.begin(st)) return GPBO_ERR_LAUNCH;
+        const DenseOut o = out.at(s);
         hipLaunchKernelGGL(sigma_acq_f32_kernel, dim3((unsigned)nblk), dim3(512), 0, st, KsT, chunk, U32, (int)Np32, mu_part,
-                           (int)(Np32 / KS_SLICE), Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,
-                           mu_out ? mu_out + s : nullptr, sigma_out ? sigma_out + s : nullptr,
-                           acq_out ? acq_out + s : nullptr, var_out ? var_out + s : nullptr, part_val + nparts,
-                           part_idx + nparts, nan_count);
-        if (rec) {
-            if (hipEventRecord(reinterpret_cast<hipEvent_t>(prof->end[prof->count]), st) != hipSuccess)
-                return GPBO_ERR_LAUNCH;
-            prof->cands[prof->count] = Mc;
-            ++prof->count;
-        }
-        prev_recorded = rec;
+                           (int)(Np32 / KS_SLICE), Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s, o.mu, o.sigma, o.acq,
+                           o.var, part_val + nparts, part_idx + nparts, nan_count);
+        if (!slots.end(st, Mc)) return GPBO_ERR_LAUNCH;
         GPBO_CHECK_LAUNCH();
         nparts += nblk;
     }

@@ -254,8 +254,6 @@ __global__ __launch_bounds__(SB) void rescore_finish_kernel(const double *__rest
     }
 }
 
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 struct RescoreLayout {
     int64_t part_off, L_off, count_off, list_off, rows_off, mu_off, sig_off, acq_off, out_off, post_off, post_bytes, total;
 };
@@ -281,6 +279,50 @@ RescoreLayout rescore_layout(int64_t Np, int64_t cap, int64_t chunk64) {
     return L;
 }
 
+// the pieces of a rescoring workspace
+struct RescoreWork {
+    double *part, *Ldev;
+    unsigned long long *count;
+    RescoreOut *out;
+    int64_t *list;
+    double *rows, *mu64, *sig64, *acq64;
+    void *post;
+    int64_t post_bytes;
+    RescoreWork(void *work, const RescoreLayout &L) {
+        char *w = reinterpret_cast<char *>(work);
+        part = reinterpret_cast<double *>(w + L.part_off);
+        Ldev = reinterpret_cast<double *>(w + L.L_off);
+        count = reinterpret_cast<unsigned long long *>(w + L.count_off);
+        out = reinterpret_cast<RescoreOut *>(w + L.out_off);
+        list = reinterpret_cast<int64_t *>(w + L.list_off);
+        rows = reinterpret_cast<double *>(w + L.rows_off);
+        mu64 = reinterpret_cast<double *>(w + L.mu_off);
+        sig64 = reinterpret_cast<double *>(w + L.sig_off);
+        acq64 = reinterpret_cast<double *>(w + L.acq_off);
+        post = w + L.post_off;
+        post_bytes = L.post_bytes;
+    }
+};
+
+// a few bytes back to the host, and wait for them
+bool read_back(void *dst_host, const void *src, size_t bytes, hipStream_t st) {
+    return hipMemcpyAsync(dst_host, src, bytes, hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess;
+}
+
+// The fp64 kernels on the candidates named by the first K entries of W.list: their rows gathered, no more chunk than they need,
+// the column-split pass.  n_prefix = 0: exact values; > 0: upper bounds from that prefix (gpbo_posterior_prefix_f64).  The
+// dense outputs go where `dense` says; the pass's own arg-max record lands in W.out->res.
+int score_list(const double *Xs, const GpModel &gp, const Acquisition &acq, int64_t chunk64, const RescoreWork &W, int64_t K,
+               int64_t n_prefix, const DenseOut &dense, void *stream) {
+    const int64_t tot = K * gp.d;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((tot + SB - 1) / SB)), dim3(SB), 0, gpbo_stream(stream), Xs,
+                       (int)gp.d, W.list, K, W.rows);
+    GPBO_CHECK_LAUNCH();
+    return gpbo_posterior_acq_f64_split(W.rows, K, gp, acq, 0.0, 0, clamp_chunk(chunk64, K), dense, &W.out->res, W.post,
+                                        W.post_bytes, nullptr, GPBO_RESCORE_SPLIT_MAX, n_prefix, stream);
+}
+
 }  // namespace
 
 extern "C" int64_t gpbo_rescore_workspace_bytes(int64_t Np, int64_t cap, int64_t chunk64) {
@@ -297,22 +339,14 @@ extern "C" int gpbo_rescore_f64(const double *Xs, int64_t M, const double *mu, c
     if (!Xs || !mu || !var32 || !X || !U || !alpha || !result || !stats_host || !work) return GPBO_ERR_ARG;
     if (M < 1 || N < 1 || Np != gpbo_padded_n(N) || d < 1 || d > GPBO_MAX_D || cap < 1 || !(tau0 > 0.0) || sample_stride < 1)
         return GPBO_ERR_ARG;
-    if (acq_kind != GPBO_ACQ_LCB && acq_kind != GPBO_ACQ_EI) return GPBO_ERR_ARG;
-    if (gpbo_posterior_workspace_bytes(Np, chunk64, cap) < 0 || ((uintptr_t)work & 255)) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
+    if (gpbo_posterior_workspace_bytes(Np, chunk64, cap) < 0 || !aligned_to(work, 256)) return GPBO_ERR_ARG;
     const RescoreLayout L = rescore_layout(Np, cap, chunk64);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    double *part = reinterpret_cast<double *>(w + L.part_off);
-    double *Ldev = reinterpret_cast<double *>(w + L.L_off);
-    unsigned long long *count = reinterpret_cast<unsigned long long *>(w + L.count_off);
-    RescoreOut *out = reinterpret_cast<RescoreOut *>(w + L.out_off);
-    int64_t *list = reinterpret_cast<int64_t *>(w + L.list_off);
-    double *rows = reinterpret_cast<double *>(w + L.rows_off);
-    double *mu64 = reinterpret_cast<double *>(w + L.mu_off);
-    double *sig64 = reinterpret_cast<double *>(w + L.sig_off);
-    double *acq64 = reinterpret_cast<double *>(w + L.acq_off);
-    void *post = w + L.post_off;
+    const GpModel gp = {X, N, Np, d, ls_host, U, alpha, prior_var};
+    const Acquisition acq = {acq_kind, p0, p1};
+    const RescoreWork W(work, L);
 
     int64_t nblk = (M + SB - 1) / SB;
     if (nblk > SCREEN_BLOCKS) nblk = SCREEN_BLOCKS;
@@ -322,43 +356,30 @@ extern "C" int gpbo_rescore_f64(const double *Xs, int64_t M, const double *mu, c
         stt.rounds = round + 1;
         stt.tau = tau;
         hipLaunchKernelGGL(screen_lo_kernel, dim3((unsigned)nblk), dim3(SB), 0, st, mu, var32, M, tau, (int)acq_kind, p0, p1,
-                           part);
-        hipLaunchKernelGGL(screen_max_kernel, dim3(1), dim3(SB), 0, st, part, (int)nblk, Ldev, count);
+                           W.part);
+        hipLaunchKernelGGL(screen_max_kernel, dim3(1), dim3(SB), 0, st, W.part, (int)nblk, W.Ldev, W.count);
         hipLaunchKernelGGL(screen_select_kernel, dim3((unsigned)nblk), dim3(SB), 0, st, mu, var32, M, tau, (int)acq_kind, p0,
-                           p1, Ldev, sample_stride, list, cap, count);
+                           p1, W.Ldev, sample_stride, W.list, cap, W.count);
         GPBO_CHECK_LAUNCH();
         unsigned long long K = 0;
-        if (hipMemcpyAsync(&K, count, sizeof(K), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
+        if (!read_back(&K, W.count, sizeof(K), st)) return GPBO_ERR_LAUNCH;
         stt.survivors = (int64_t)K;
         if ((int64_t)K > cap) {  // too many candidates could still be the maximum: the plain fp64 pass decides
             stt.fallback = 1;
             *stats_host = stt;
             return GPBO_OK;
         }
-        const int64_t tot = (int64_t)K * d;
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((tot + SB - 1) / SB)), dim3(SB), 0, st, Xs, (int)d, list,
-                           (int64_t)K, rows);
-        GPBO_CHECK_LAUNCH();
-        int64_t chunk = chunk64;
-        const int64_t kpad = ((int64_t)K + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
-        if (chunk > kpad) chunk = kpad;
-        int rc = gpbo_posterior_acq_f64_split(rows, (int64_t)K, X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1,
-                                              0.0, 0, chunk, mu64, sig64, acq64, &out->res, post, L.post_bytes, nullptr,
-                                              GPBO_RESCORE_SPLIT_MAX, 0, stream);
+        int rc = score_list(Xs, gp, acq, chunk64, W, (int64_t)K, 0, {W.mu64, W.sig64, W.acq64, nullptr}, stream);
         if (rc != GPBO_OK) return rc;
-        hipLaunchKernelGGL(rescore_finish_kernel, dim3(1), dim3(SB), 0, st, acq64, sig64, list, (int64_t)K, var32, idx_offset,
-                           out);
+        hipLaunchKernelGGL(rescore_finish_kernel, dim3(1), dim3(SB), 0, st, W.acq64, W.sig64, W.list, (int64_t)K, var32, idx_offset,
+                           W.out);
         GPBO_CHECK_LAUNCH();
         RescoreOut h;
-        if (hipMemcpyAsync(&h, out, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
+        if (!read_back(&h, W.out, sizeof(h), st)) return GPBO_ERR_LAUNCH;
         stt.rescored += (int64_t)K;
         stt.err_max = h.err_max;
         if (4.0 * h.err_max <= tau) {  // the screen's assumption held with a factor 4 to spare on this call's sample
-            if (hipMemcpyAsync(result, &out->res, sizeof(gpbo_result), hipMemcpyDeviceToDevice, st) != hipSuccess)
+            if (hipMemcpyAsync(result, &W.out->res, sizeof(gpbo_result), hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return GPBO_ERR_LAUNCH;
             *stats_host = stt;
             return GPBO_OK;
@@ -379,30 +400,28 @@ extern "C" int gpbo_rescore_f64(const double *Xs, int64_t M, const double *mu, c
 //             first `refine` survivors are re-scored to raise the threshold and the selection is repeated (at most 3 times).
 // When the survivors still do not fit (a flat mean, thousands of ties, an exploration weight that dwarfs the mean) the caller
 // is told to run the plain pass (stats->fallback).  stats: tau = the last threshold, err_max unused.
-static int bound_select_impl(const double *Xs, int64_t M, const double *ub, const double *X, int64_t N, int64_t Np,
-                             int32_t d, const double *ls_host, const double *U, const double *alpha,
-                             double prior_var, int32_t acq_kind, double p0, double p1, int64_t idx_offset,
-                             int64_t sample_stride, int64_t cap, int64_t chunk64, int64_t n_prefix2,
-                             gpbo_result *result, gpbo_screen_stats *stats_host, void *work, int64_t work_bytes,
-                             void *stream) {
+extern "C" int gpbo_bound_select_f64(const double *Xs, int64_t M, const double *ub, const double *X, int64_t N, int64_t Np,
+                                     int32_t d, const double *ls_host, const double *U, const double *alpha,
+                                     double prior_var, int32_t acq_kind, double p0, double p1, int64_t idx_offset,
+                                     int64_t sample_stride, int64_t cap, int64_t chunk64, int64_t n_prefix2,
+                                     gpbo_result *result, gpbo_screen_stats *stats_host, void *work, int64_t work_bytes,
+                                     void *stream) {
     if (!Xs || !ub || !X || !U || !alpha || !result || !stats_host || !work) return GPBO_ERR_ARG;
     if (n_prefix2 < 0 || n_prefix2 > Np || n_prefix2 % 128) return GPBO_ERR_ARG;
     if (M < 1 || N < 1 || Np != gpbo_padded_n(N) || d < 1 || d > GPBO_MAX_D || cap < 1 || sample_stride < 1) return GPBO_ERR_ARG;
-    if (acq_kind != GPBO_ACQ_LCB && acq_kind != GPBO_ACQ_EI) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
     if (acq_kind == GPBO_ACQ_LCB && !(p0 >= 0.0)) return GPBO_ERR_ARG;   // the bound needs an acquisition that increases with sigma
-    if (gpbo_posterior_workspace_bytes(Np, chunk64, cap) < 0 || ((uintptr_t)work & 255)) return GPBO_ERR_ARG;
+    if (gpbo_posterior_workspace_bytes(Np, chunk64, cap) < 0 || !aligned_to(work, 256)) return GPBO_ERR_ARG;
     const RescoreLayout L = rescore_layout(Np, cap, chunk64);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    unsigned long long *count = reinterpret_cast<unsigned long long *>(w + L.count_off);
-    RescoreOut *out = reinterpret_cast<RescoreOut *>(w + L.out_off);
-    int64_t *list = reinterpret_cast<int64_t *>(w + L.list_off);
-    double *rows = reinterpret_cast<double *>(w + L.rows_off);
-    double *mu64 = reinterpret_cast<double *>(w + L.mu_off);
-    double *sig64 = reinterpret_cast<double *>(w + L.sig_off);
-    double *acq64 = reinterpret_cast<double *>(w + L.acq_off);
-    void *post = w + L.post_off;
+    const GpModel gp = {X, N, Np, d, ls_host, U, alpha, prior_var};
+    const Acquisition acq = {acq_kind, p0, p1};
+    const RescoreWork W(work, L);
+    double *const part = W.part, *const Ldev = W.Ldev, *const mu64 = W.mu64, *const sig64 = W.sig64, *const acq64 = W.acq64;
+    unsigned long long *const count = W.count;
+    RescoreOut *const out = W.out;
+    int64_t *const list = W.list;
     int64_t nblk = (M + SB - 1) / SB;
     if (nblk > SCREEN_BLOCKS) nblk = SCREEN_BLOCKS;
     const double inf = std::numeric_limits<double>::infinity();
@@ -410,21 +429,12 @@ static int bound_select_impl(const double *Xs, int64_t M, const double *ub, cons
 
     // exact fp64 values of the first K entries of `list`; their arg-max (lowest original index) lands in *out
     auto exact = [&](int64_t K, RescoreOut *h) -> int {
-        const int64_t tot = K * d;
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((tot + SB - 1) / SB)), dim3(SB), 0, st, Xs, (int)d, list, K, rows);
-        GPBO_CHECK_LAUNCH();
-        int64_t chunk = chunk64;
-        const int64_t kpad = (K + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
-        if (chunk > kpad) chunk = kpad;
-        int rc = gpbo_posterior_acq_f64_split(rows, K, X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, 0.0, 0,
-                                              chunk, mu64, sig64, acq64, &out->res, post, L.post_bytes, nullptr,
-                                              GPBO_RESCORE_SPLIT_MAX, 0, stream);
+        int rc = score_list(Xs, gp, acq, chunk64, W, K, 0, {mu64, sig64, acq64, nullptr}, stream);
         if (rc != GPBO_OK) return rc;
         hipLaunchKernelGGL(rescore_finish_kernel, dim3(1), dim3(SB), 0, st, acq64, sig64, list, K, (const double *)nullptr,
                            idx_offset, out);
         GPBO_CHECK_LAUNCH();
-        if (hipMemcpyAsync(h, out, sizeof(*h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
+        if (!read_back(h, out, sizeof(*h), st)) return GPBO_ERR_LAUNCH;
         stt.rescored += K;
         ++stt.rounds;   // = launches of the fp64 kernels on gathered rows
         return GPBO_OK;
@@ -436,17 +446,13 @@ static int bound_select_impl(const double *Xs, int64_t M, const double *ub, cons
         hipLaunchKernelGGL(bound_select_kernel, dim3((unsigned)nblk), dim3(SB), 0, st, ub, M, thr, slack, stride,
                            count_only ? (int64_t *)nullptr : list, cap, count);
         GPBO_CHECK_LAUNCH();
-        if (hipMemcpyAsync(K, count, sizeof(*K), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
-        return GPBO_OK;
+        return read_back(K, count, sizeof(*K), st) ? GPBO_OK : GPBO_ERR_LAUNCH;
     };
 
     RescoreOut h;
     unsigned long long K = 0;
     int rc;
     double thr = -inf;
-    double *part = reinterpret_cast<double *>(w + L.part_off);
-    double *Ldev = reinterpret_cast<double *>(w + L.L_off);
     // smallest and largest value of n bounds (NaNs skipped)
     auto minmax = [&](const double *v, int64_t n, double *mm) -> int {
         int64_t blk = (n + SB - 1) / SB;
@@ -454,10 +460,7 @@ static int bound_select_impl(const double *Xs, int64_t M, const double *ub, cons
         hipLaunchKernelGGL(bound_minmax_kernel, dim3((unsigned)blk), dim3(SB), 0, st, v, n, part);
         hipLaunchKernelGGL(bound_minmax_finish_kernel, dim3(1), dim3(SB), 0, st, part, (int)blk, Ldev);
         GPBO_CHECK_LAUNCH();
-        if (hipMemcpyAsync(mm, Ldev, 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
-        return GPBO_OK;
+        return read_back(mm, Ldev, 2 * sizeof(double), st) ? GPBO_OK : GPBO_ERR_LAUNCH;
     };
     // a level between mm[1] and mm[0] that `counter(level)` candidates reach, want_lo <= count <= want_hi
     auto bisect = [&](const double *mm, int64_t want_lo, int64_t want_hi, auto &&counter, double *level) -> int {
@@ -499,17 +502,8 @@ static int bound_select_impl(const double *Xs, int64_t M, const double *ub, cons
             if (rc != GPBO_OK) return rc;
             const int64_t K1 = (int64_t)K;
             if (K1 >= 1 && K1 <= cap) {
-                const int64_t tot = K1 * d;
-                hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((tot + SB - 1) / SB)), dim3(SB), 0, st, Xs, (int)d, list, K1,
-                                   rows);
-                GPBO_CHECK_LAUNCH();
-                int64_t chunk = chunk64;
-                const int64_t kpad = (K1 + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
-                if (chunk > kpad) chunk = kpad;
                 double *ub2 = sig64;   // (acq64 / mu64 are overwritten by the fp64 launch below; sig64 is too, AFTER ub2's last use)
-                rc = gpbo_posterior_acq_f64_split(rows, K1, X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, 0.0, 0,
-                                                  chunk, nullptr, nullptr, ub2, &out->res, post, L.post_bytes, nullptr,
-                                                  GPBO_RESCORE_SPLIT_MAX, n_prefix2, stream);
+                rc = score_list(Xs, gp, acq, chunk64, W, K1, n_prefix2, {nullptr, nullptr, ub2, nullptr}, stream);
                 if (rc != GPBO_OK) return rc;
                 int64_t *list2 = reinterpret_cast<int64_t *>(mu64);
                 int64_t rblk = (K1 + SB - 1) / SB;
@@ -519,10 +513,7 @@ static int bound_select_impl(const double *Xs, int64_t M, const double *ub, cons
                     hipLaunchKernelGGL(bound_refine_kernel, dim3((unsigned)rblk), dim3(SB), 0, st, ub2, list, K1, level,
                                        1e-10 * fmax(1.0, fabs(level)), list2, count);
                     GPBO_CHECK_LAUNCH();
-                    if (hipMemcpyAsync(c, count, sizeof(*c), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        hipStreamSynchronize(st) != hipSuccess)
-                        return GPBO_ERR_LAUNCH;
-                    return GPBO_OK;
+                    return read_back(c, count, sizeof(*c), st) ? GPBO_OK : GPBO_ERR_LAUNCH;
                 };
                 double mm2[2], level2 = inf;
                 rc = minmax(ub2, K1, mm2);
@@ -593,16 +584,7 @@ static int bound_select_impl(const double *Xs, int64_t M, const double *ub, cons
             if (n_prefix2 > 0 && (int64_t)K > 4 * refine) {
                 // second level: a longer prefix for the survivors only (tighter bounds at (n_prefix2 / Np)^2 of the
                 // exact cost); what still reaches the threshold goes to the fp64 kernels
-                const int64_t tot = (int64_t)K * d;
-                hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((tot + SB - 1) / SB)), dim3(SB), 0, st, Xs, (int)d, list,
-                                   (int64_t)K, rows);
-                GPBO_CHECK_LAUNCH();
-                int64_t chunk = chunk64;
-                const int64_t kpad = ((int64_t)K + GPBO_CHUNK_GRANULE - 1) / GPBO_CHUNK_GRANULE * GPBO_CHUNK_GRANULE;
-                if (chunk > kpad) chunk = kpad;
-                rc = gpbo_posterior_acq_f64_split(rows, (int64_t)K, X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1,
-                                                  0.0, 0, chunk, nullptr, nullptr, acq64, &out->res, post, L.post_bytes, nullptr,
-                                                  GPBO_RESCORE_SPLIT_MAX, n_prefix2, stream);
+                rc = score_list(Xs, gp, acq, chunk64, W, (int64_t)K, n_prefix2, {nullptr, nullptr, acq64, nullptr}, stream);
                 if (rc != GPBO_OK) return rc;
                 int64_t *list2 = reinterpret_cast<int64_t *>(mu64);   // (cap x 8 bytes, not used by the call above)
                 if (hipMemsetAsync(count, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
@@ -612,9 +594,7 @@ static int bound_select_impl(const double *Xs, int64_t M, const double *ub, cons
                                    1e-10 * fmax(1.0, fabs(thr)), list2, count);
                 GPBO_CHECK_LAUNCH();
                 unsigned long long K2 = 0;
-                if (hipMemcpyAsync(&K2, count, sizeof(K2), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess)
-                    return GPBO_ERR_LAUNCH;
+                if (!read_back(&K2, count, sizeof(K2), st)) return GPBO_ERR_LAUNCH;
                 if (K2 > K) return GPBO_ERR_LAUNCH;
                 if (hipMemcpyAsync(list, list2, sizeof(int64_t) * K2, hipMemcpyDeviceToDevice, st) != hipSuccess)
                     return GPBO_ERR_LAUNCH;
@@ -639,14 +619,4 @@ static int bound_select_impl(const double *Xs, int64_t M, const double *ub, cons
     stt.fallback = 1;
     *stats_host = stt;
     return GPBO_OK;
-}
-
-extern "C" int gpbo_bound_select_f64(const double *Xs, int64_t M, const double *ub, const double *X, int64_t N, int64_t Np,
-                                     int32_t d, const double *ls_host, const double *U, const double *alpha,
-                                     double prior_var, int32_t acq_kind, double p0, double p1, int64_t idx_offset,
-                                     int64_t sample_stride, int64_t cap, int64_t chunk64, int64_t n_prefix2,
-                                     gpbo_result *result, gpbo_screen_stats *stats_host, void *work, int64_t work_bytes,
-                                     void *stream) {
-    return bound_select_impl(Xs, M, ub, X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, idx_offset, sample_stride,
-                             cap, chunk64, n_prefix2, result, stats_host, work, work_bytes, stream);
 }

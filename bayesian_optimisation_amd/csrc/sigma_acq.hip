@@ -555,7 +555,7 @@ Helper *helper_for_current_device() {
     return tab[dev];
 }
 
-inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+static_assert(BN == GPBO_NPAD, "f64_column_groups (host_driver.h) counts column blocks of GPBO_NPAD");
 
 struct PosteriorLayout {
     int64_t kst_off[2], mup_off[2], xsc_off, prep_off, pval_off, pidx_off, nan_off, ssp_off, total, nparts_cap;
@@ -744,15 +744,69 @@ QeiLayout qei_layout(int64_t Np, int64_t chunk, int64_t M) {
     return L;
 }
 
+// One variance launch of the acquisition driver: the kernel's arguments once, whichever variant is launched.
+struct SigmaLaunch {
+    dim3 grid;
+    const double *KsT;
+    int64_t ldk;
+    const double *U;
+    int Np;
+    const double *mu_part;
+    int nsl;
+    int64_t Mc;
+    double prior_var;
+    Acquisition acq;
+    int64_t idx_base;
+    DenseOut out;       // all null where split_finish_kernel writes the dense outputs
+    double *part_val;
+    int64_t *part_idx;
+    unsigned long long *nan_count;
+    double *stamps;     // diagnostics build: where a stamped variant may leave its stamps, or null
+    double *ss_part;
+    int xg, ntile, ncb;
+};
+
+template <int V>
+void launch_sigma(const SigmaLaunch &a, hipStream_t st) {
+    // (stamped variants: 6 everywhere, 8 and above in the grouped launch only)
+    double *stamps = (V == 6 || (a.xg > 1 && V >= 8)) ? a.stamps : nullptr;
+    hipLaunchKernelGGL(sigma_acq_kernel<V>, a.grid, dim3(NW * 64), 0, st, a.KsT, a.ldk, a.U, a.Np, a.mu_part, a.nsl, a.Mc,
+                       a.prior_var, (int)a.acq.kind, a.acq.p0, a.acq.p1, a.idx_base, a.out.mu, a.out.sigma, a.out.acq,
+                       a.part_val, a.part_idx, a.nan_count, stamps, a.ss_part, a.xg, a.ntile, a.ncb);
+}
+
+// Timing-only variants of the variance kernel (wrong results; tools/tile_stamps.py uses 6) exist only in a
+// diagnostics build (GPBO_DIAG=1 build.sh): the shipped library has no switch into them.
+void launch_sigma_variant(const SigmaLaunch &a, hipStream_t st) {
+#ifdef GPBO_DIAGNOSTICS
+    static const int variant = env_int("GPBO_SIGMA_VARIANT", 0);
+    // the grouped launch has variants 1 3 4 6 9 11 12, the plain one 1 2 3 4 6; anything else is the product kernel
+    const bool have = (a.xg > 1) ? variant != 2 : variant < 9;
+    switch (have ? variant : 0) {
+        case 1: return launch_sigma<1>(a, st);
+        case 3: return launch_sigma<3>(a, st);
+        case 4: return launch_sigma<4>(a, st);
+        case 6: return launch_sigma<6>(a, st);
+        case 9: return launch_sigma<9>(a, st);
+        case 11: return launch_sigma<11>(a, st);
+        case 12: return launch_sigma<12>(a, st);
+        default: return launch_sigma<0>(a, st);
+        case 2: return launch_sigma<2>(a, st);
+    }
+#else
+    launch_sigma<0>(a, st);
+#endif
+}
+
 }  // namespace
 
 int gpbo_launch_split_finish(const double *ss_part, int S, int64_t ldk, const double *mu_part, int nsl, int64_t Mc,
-                             double prior_var, int acq_kind, double p0, double p1, int64_t idx_base, double *mu_out,
-                             double *sigma_out, double *acq_out, double *var_out, double *part_val, int64_t *part_idx,
-                             unsigned long long *nan_count, hipStream_t st) {
+                             double prior_var, const Acquisition &acq, int64_t idx_base, const DenseOut &out,
+                             double *part_val, int64_t *part_idx, unsigned long long *nan_count, hipStream_t st) {
     const int64_t nb = (Mc + 255) / 256;
     hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nb), dim3(256), 0, st, ss_part, S, ldk, mu_part, nsl, Mc, prior_var,
-                       acq_kind, p0, p1, idx_base, mu_out, sigma_out, acq_out, var_out, part_val, part_idx, nan_count, 0.0);
+                       (int)acq.kind, acq.p0, acq.p1, idx_base, out.mu, out.sigma, out.acq, out.var, part_val, part_idx,
+                       nan_count, 0.0);
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
 }
@@ -765,9 +819,7 @@ int gpbo_launch_argmax_finish(const double *part_val, const int64_t *part_idx, i
 }
 
 extern "C" int64_t gpbo_posterior_workspace_bytes(int64_t Np, int64_t chunk, int64_t M) {
-    if (Np < GPBO_NPAD || Np % GPBO_NPAD || chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE || chunk > GPBO_CHUNK_MAX || M < 1)
-        return GPBO_ERR_ARG;
-    return posterior_layout(Np, chunk, M).total;
+    return gpbo_posterior_workspace_bytes_split(Np, chunk, M, 1);
 }
 
 extern "C" int gpbo_posterior_acq_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
@@ -776,9 +828,9 @@ extern "C" int gpbo_posterior_acq_f64(const double *Xs, int64_t M, const double 
                                       int64_t chunk, double *mu_out, double *sigma_out, double *acq_out,
                                       gpbo_result *result, void *work, int64_t work_bytes, gpbo_profile *prof,
                                       void *stream) {
-    return gpbo_posterior_acq_f64_split(Xs, M, X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, diag_add,
-                                        idx_offset, chunk, mu_out, sigma_out, acq_out, result, work, work_bytes, prof, 1,
-                                        0, stream);
+    return gpbo_posterior_acq_f64_split(Xs, M, {X, N, Np, d, ls_host, U, alpha, prior_var}, {acq_kind, p0, p1}, diag_add,
+                                        idx_offset, chunk, {mu_out, sigma_out, acq_out, nullptr}, result, work, work_bytes,
+                                        prof, 1, 0, stream);
 }
 
 // The prefix-bound screen's first pass (rescore.hip, gpbo_bound_select_f64): the mean over all N observations, the
@@ -793,14 +845,13 @@ extern "C" int gpbo_posterior_prefix_f64(const double *Xs, int64_t M, const doub
                                          void *stream) {
     if (n_prefix < BN || n_prefix % BN || n_prefix > Np) return GPBO_ERR_ARG;
     if (acq_kind == GPBO_ACQ_LCB && !(p0 >= 0.0)) return GPBO_ERR_ARG;
-    return gpbo_posterior_acq_f64_split(Xs, M, X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, 0.0,
-                                        idx_offset, chunk, mu_out, sigma_ub_out, acq_ub_out, result, work, work_bytes,
-                                        prof, 1, n_prefix, stream);
+    return gpbo_posterior_acq_f64_split(Xs, M, {X, N, Np, d, ls_host, U, alpha, prior_var}, {acq_kind, p0, p1}, 0.0,
+                                        idx_offset, chunk, {mu_out, sigma_ub_out, acq_ub_out, nullptr}, result, work,
+                                        work_bytes, prof, 1, n_prefix, stream);
 }
 
 int64_t gpbo_posterior_workspace_bytes_split(int64_t Np, int64_t chunk, int64_t M, int split_max) {
-    if (Np < GPBO_NPAD || Np % GPBO_NPAD || chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE || chunk > GPBO_CHUNK_MAX || M < 1)
-        return GPBO_ERR_ARG;
+    if (!np_ok(Np) || !chunk_ok(chunk) || M < 1) return GPBO_ERR_ARG;
     return posterior_layout(Np, chunk, M, split_max).total;
 }
 
@@ -808,18 +859,19 @@ int64_t gpbo_posterior_workspace_bytes_split(int64_t Np, int64_t chunk, int64_t 
 // of a few survivors: one workgroup per 256 candidates would take N^2/2 MFMA-bound k tiles on ONE compute unit).
 // The partial sums are combined in a fixed order, so results are deterministic; they differ from the unsplit
 // kernel's by the rounding of a different summation order (~1e-16 relative).
-int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
-                                 const double *ls_host, const double *U, const double *alpha, double prior_var,
-                                 int32_t acq_kind, double p0, double p1, double diag_add, int64_t idx_offset,
-                                 int64_t chunk, double *mu_out, double *sigma_out, double *acq_out, gpbo_result *result,
-                                 void *work, int64_t work_bytes, gpbo_profile *prof, int split_max,
+int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp, const Acquisition &acq, double diag_add,
+                                 int64_t idx_offset, int64_t chunk, const DenseOut &out, gpbo_result *result, void *work,
+                                 int64_t work_bytes, gpbo_profile *prof, int split_max,
                                  int64_t n_prefix /* 0: everything; else see gpbo_posterior_prefix_f64 */, void *stream) {
+    const double *X = gp.X, *U = gp.U, *alpha = gp.alpha, *ls_host = gp.ls_host;
+    const int64_t N = gp.N, Np = gp.Np;
+    const int32_t d = gp.d;
     if (!Xs || !X || !U || !alpha || !result || !work) return GPBO_ERR_ARG;
     if (n_prefix < 0 || n_prefix > Np || n_prefix % BN || (n_prefix && diag_add != 0.0)) return GPBO_ERR_ARG;
     if (M < 1 || N < 1 || Np != gpbo_padded_n(N) || Np > (1 << 20)) return GPBO_ERR_ARG;
-    if (chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE || chunk > GPBO_CHUNK_MAX) return GPBO_ERR_ARG;
-    if (acq_kind != GPBO_ACQ_LCB && acq_kind != GPBO_ACQ_EI) return GPBO_ERR_ARG;
-    if (((uintptr_t)work & 255) || ((uintptr_t)U & 15)) return GPBO_ERR_ARG;
+    if (!chunk_ok(chunk)) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq.kind)) return GPBO_ERR_ARG;
+    if (!aligned_to(work, 256) || !aligned_to(U, 16)) return GPBO_ERR_ARG;
     const PosteriorLayout L = posterior_layout(Np, chunk, M, split_max);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
@@ -833,8 +885,8 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, i
     unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
     // prefix-bound route: K(X*,X) with the pair distances on the matrix cores and the mean reported from below by its error
     // bound (kstar_mfma.hip; GPBO_PREFIX_VALU=1: the difference-form kernel instead, for A/B runs)
-    static const bool prefix_valu = getenv("GPBO_PREFIX_VALU") && atoi(getenv("GPBO_PREFIX_VALU"));
-    static const bool overlap_env = getenv("GPBO_OVERLAP") && atoi(getenv("GPBO_OVERLAP"));
+    static const bool prefix_valu = env_flag("GPBO_PREFIX_VALU");
+    static const bool overlap_env = env_flag("GPBO_OVERLAP");
     // (and only while the unused rows of the K*^T slab can take that launch's mean partials)
     const bool kstar_mfma = n_prefix > 0 && !prefix_valu && !overlap_env && n_prefix + n_prefix / GPBO_KS_SLICE <= Np;
     const bool anyd = d > GPBO_MAX_D;   // slow path of the fp64 route: no unrolled registers, no pre-scaled copy
@@ -852,13 +904,6 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, i
         if (rc0 != GPBO_OK) return rc0;
     }
 
-    // Timing-only variants of the variance kernel (wrong results; tools/tile_stamps.py uses 6) exist only in a
-    // diagnostics build (GPBO_DIAG=1 build.sh): the shipped library has no switch into them.
-#ifdef GPBO_DIAGNOSTICS
-    static const int variant = getenv("GPBO_SIGMA_VARIANT") ? atoi(getenv("GPBO_SIGMA_VARIANT")) : 0;
-#else
-    constexpr int variant = 0;
-#endif
     // Measured on MI355X (N=512, M=2^20): running K(X*,X) of chunk c+1 beside the variance kernel of chunk c gains
     // nothing - the variance launches slow down by what the overlap hides (0.59 -> 0.70 ms), i.e. fp64 VALU work
     // and fp64 MFMA work do not co-execute on gfx950.  The same at N = 4096, 2^21 candidates (same box, two runs each):
@@ -875,24 +920,14 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, i
     }
     // partials of the mean per candidate: 64-observation slices, coarser ones from the matrix-core K(X*,X) kernel
     const int nsl = kstar_mfma ? (int)(Np / gpbo_kstar_mfma_slice(Np)) : (int)(Np / GPBO_KS_SLICE);
-    bool prev_recorded = false;  // the previous chunk's variance launch has an end event in the slot before
+    ProfileRecorder slots(prof);
     auto launch_kstar = [&](int64_t c) -> int {
         const int64_t s = c * chunk;
         const int64_t Mc = (M - s < chunk) ? (M - s) : chunk;
         const int b = (int)(c & 1);
         // K(X*,X) launches are timed only in the plain in-order mode, where the launches of this call form one chain
-        // on the caller's stream: the event in front of the variance launch of the slot ends the K(X*,X) interval, and
-        // the interval begins at the previous variance launch's end event (chunks after the first) or at kbegin.
-        const bool krec = prof && !hp && prof->count < prof->capacity;
-        if (krec) {
-            const bool chained = c > 0 && prof->count > 0 && prev_recorded;
-            prof->kmode[prof->count] = chained ? 2 : 1;
-            if (!chained &&
-                hipEventRecord(reinterpret_cast<hipEvent_t>(prof->kbegin[prof->count]), ks) != hipSuccess)
-                return GPBO_ERR_LAUNCH;
-        } else if (prof && prof->count < prof->capacity) {
-            prof->kmode[prof->count] = 0;
-        }
+        // on the caller's stream
+        if (!slots.kstar(ks, c > 0, !hp)) return GPBO_ERR_LAUNCH;
         int rc;
         if (kstar_mfma) {
             // The MEAN of all N observations from the matrix-core kernel (expanded distances; reported from below by its
@@ -934,81 +969,32 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, i
         }
         if (hp && hipStreamWaitEvent(st, hp->kdone[b], 0) != hipSuccess) return GPBO_ERR_LAUNCH;
         const int64_t nblk = (Mc + BM - 1) / BM;
-        const bool rec = prof && prof->count < prof->capacity;
-        if (rec && hipEventRecord(reinterpret_cast<hipEvent_t>(prof->begin[prof->count]), st) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
+        if (!slots.begin(st)) return GPBO_ERR_LAUNCH;
         const int S = split_factor(nblk, (n_prefix ? n_prefix : Np) / BN, split_max);
         // Column groups on one XCD for large calls (see the kernel): measured on MI355X at N = 4096, 2^21 candidates,
-        // same box: 543 -> 509 ms per step with 8 groups (16: 512), the variance launches 32.9 -> 30.7 ms.  The rule depends
-        // on the problem (N, candidates of the CALL), never on the chunking, so results stay chunk-size invariant bit for
-        // bit.  GPBO_F64_GROUPS=1 switches it off (A/B runs).
-        static const int xg_env = getenv("GPBO_F64_GROUPS") ? atoi(getenv("GPBO_F64_GROUPS")) : 8;
-        if (xg_env > 1 && S == 1 && M >= 32768 && Np / BN >= 2 * xg_env && xg_env <= 16 && n_prefix == 0) {
-            const int64_t grid1 = (nblk + 7) / 8 * 8 * xg_env;
-            // (diagnostics build: the stamps of a stamped variant go to the other chunk buffer, free during the last chunk)
-#define GPBO_SIGMA_XG_LAUNCH(V)                                                                                       \
-    hipLaunchKernelGGL(sigma_acq_kernel<V>, dim3((unsigned)grid1), dim3(NW * 64), 0, st, KsT[b], chunk, U, (int)Np,        \
-                       mu_part[b], nsl, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,                        \
-                       (double *)nullptr, (double *)nullptr, (double *)nullptr, part_val + nparts,                  \
-                       part_idx + nparts, nan_count,                                                                 \
-                       ((V == 6 || V >= 8) && c == nchunks - 1 && nchunks > 1) ? KsT[(c + 1) & 1] : (double *)nullptr, \
-                       ss_part, xg_env, (int)nblk, 0)
-#ifdef GPBO_DIAGNOSTICS
-            if (variant == 1) GPBO_SIGMA_XG_LAUNCH(1);
-            else if (variant == 3) GPBO_SIGMA_XG_LAUNCH(3);
-            else if (variant == 4) GPBO_SIGMA_XG_LAUNCH(4);
-            else if (variant == 6) GPBO_SIGMA_XG_LAUNCH(6);
-            else if (variant == 9) GPBO_SIGMA_XG_LAUNCH(9);
-            else if (variant == 11) GPBO_SIGMA_XG_LAUNCH(11);
-            else if (variant == 12) GPBO_SIGMA_XG_LAUNCH(12);
-            else GPBO_SIGMA_XG_LAUNCH(0);
-#else
-            GPBO_SIGMA_XG_LAUNCH(0);
-#endif
-#undef GPBO_SIGMA_XG_LAUNCH
-            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, xg_env, chunk, mu_part[b],
-                               nsl, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,
-                               mu_out ? mu_out + s : nullptr, sigma_out ? sigma_out + s : nullptr,
-                               acq_out ? acq_out + s : nullptr, (double *)nullptr, part_val + nparts, part_idx + nparts,
-                               nan_count, n_prefix ? GPBO_BOUND_VAR_PAD : 0.0);
-        } else if (S > 1) {
-            hipLaunchKernelGGL(sigma_acq_kernel<0>, dim3((unsigned)nblk, (unsigned)S), dim3(NW * 64), 0, st, KsT[b], chunk, U,
-                               (int)Np, mu_part[b], nsl, Mc, prior_var, (int)acq_kind, p0, p1,
-                               idx_offset + s, (double *)nullptr, (double *)nullptr, (double *)nullptr, part_val + nparts,
-                               part_idx + nparts, nan_count, (double *)nullptr, ss_part, 1, (int)nblk, (int)(n_prefix / BN));
-            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, S, chunk, mu_part[b],
-                               nsl, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,
-                               mu_out ? mu_out + s : nullptr, sigma_out ? sigma_out + s : nullptr,
-                               acq_out ? acq_out + s : nullptr, (double *)nullptr, part_val + nparts, part_idx + nparts,
-                               nan_count, n_prefix ? GPBO_BOUND_VAR_PAD : 0.0);
+        // same box: 543 -> 509 ms per step with 8 groups (16: 512), the variance launches 32.9 -> 30.7 ms.
+        const int xg = (S == 1 && n_prefix == 0) ? f64_column_groups(M, Np) : 1;
+        const DenseOut o = out.at(s);
+        SigmaLaunch a = {dim3((unsigned)nblk), KsT[b], chunk, U, (int)Np, mu_part[b], nsl, Mc, gp.prior_var, acq,
+                         idx_offset + s, o, part_val + nparts, part_idx + nparts, nan_count,
+                         // (the stamps of a stamped variant go to the other chunk buffer, free during the last chunk)
+                         (c == nchunks - 1 && nchunks > 1) ? KsT[(c + 1) & 1] : nullptr, nullptr, 1, (int)nblk,
+                         (int)(n_prefix / BN)};
+        if (xg > 1 || S > 1) {   // partial sums to ss_part, the epilogue in split_finish_kernel
+            a.grid = (xg > 1) ? dim3((unsigned)((nblk + 7) / 8 * 8 * xg)) : dim3((unsigned)nblk, (unsigned)S);
+            a.out = {nullptr, nullptr, nullptr, nullptr};
+            a.ss_part = ss_part;
+            a.xg = xg;
+            if (xg > 1) launch_sigma_variant(a, st);
+            else launch_sigma<0>(a, st);
+            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, xg > 1 ? xg : S, chunk,
+                               mu_part[b], nsl, Mc, gp.prior_var, (int)acq.kind, acq.p0, acq.p1, idx_offset + s, o.mu, o.sigma,
+                               o.acq, (double *)nullptr, part_val + nparts, part_idx + nparts, nan_count,
+                               n_prefix ? GPBO_BOUND_VAR_PAD : 0.0);
         } else {
-#define GPBO_SIGMA_LAUNCH(V)                                                                                        \
-    hipLaunchKernelGGL(sigma_acq_kernel<V>, dim3((unsigned)nblk), dim3(NW * 64), 0, st, KsT[b], chunk, U, (int)Np,          \
-                       mu_part[b], nsl, Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s,               \
-                       mu_out ? mu_out + s : nullptr, sigma_out ? sigma_out + s : nullptr,                              \
-                       acq_out ? acq_out + s : nullptr, part_val + nparts, part_idx + nparts, nan_count,                     \
-                       (V == 6 && c == nchunks - 1 && nchunks > 1) ? KsT[(c + 1) & 1] : (double *)nullptr, (double *)nullptr, 1, \
-                       (int)nblk, (int)(n_prefix / BN))
-#ifdef GPBO_DIAGNOSTICS
-        if (variant == 1) GPBO_SIGMA_LAUNCH(1);
-        else if (variant == 2) GPBO_SIGMA_LAUNCH(2);
-        else if (variant == 3) GPBO_SIGMA_LAUNCH(3);
-        else if (variant == 4) GPBO_SIGMA_LAUNCH(4);
-        else if (variant == 6) GPBO_SIGMA_LAUNCH(6);
-        else GPBO_SIGMA_LAUNCH(0);
-#else
-        (void)variant;
-        GPBO_SIGMA_LAUNCH(0);
-#endif
-#undef GPBO_SIGMA_LAUNCH
+            launch_sigma_variant(a, st);
         }
-        if (rec) {
-            if (hipEventRecord(reinterpret_cast<hipEvent_t>(prof->end[prof->count]), st) != hipSuccess)
-                return GPBO_ERR_LAUNCH;
-            prof->cands[prof->count] = Mc;
-            ++prof->count;
-        }
-        prev_recorded = rec;
+        if (!slots.end(st, Mc)) return GPBO_ERR_LAUNCH;
         GPBO_CHECK_LAUNCH();
         if (hp && hipEventRecord(hp->sdone[b], st) != hipSuccess) return GPBO_ERR_LAUNCH;
         if (!hp && c + 1 < nchunks) {
@@ -1017,9 +1003,7 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const double *X, i
         }
         nparts += nblk;
     }
-    hipLaunchKernelGGL(argmax_finish_kernel, dim3(1), dim3(256), 0, st, part_val, part_idx, nparts, nan_count, result);
-    GPBO_CHECK_LAUNCH();
-    return GPBO_OK;
+    return gpbo_launch_argmax_finish(part_val, part_idx, nparts, nan_count, result, st);
 }
 
 extern "C" int64_t gpbo_acq_workspace_bytes(void) { return 1024 * 16 + 256; }
@@ -1028,7 +1012,7 @@ extern "C" int gpbo_acq_argmax_f64(const double *mu, const double *sigma, int64_
                                    double p1, int64_t idx_offset, double *acq_out, gpbo_result *result, void *work,
                                    int64_t work_bytes, void *stream) {
     if (!mu || !sigma || !result || !work || M < 1) return GPBO_ERR_ARG;
-    if (acq_kind != GPBO_ACQ_LCB && acq_kind != GPBO_ACQ_EI) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
     if (work_bytes < gpbo_acq_workspace_bytes()) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
     char *w = reinterpret_cast<char *>(work);
@@ -1046,8 +1030,7 @@ extern "C" int gpbo_acq_argmax_f64(const double *mu, const double *sigma, int64_
 }
 
 extern "C" int64_t gpbo_qei_workspace_bytes(int64_t Np, int64_t chunk, int64_t M) {
-    if (Np < GPBO_NPAD || Np % GPBO_NPAD || chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE || chunk > GPBO_CHUNK_MAX || M < 1)
-        return GPBO_ERR_ARG;
+    if (!np_ok(Np) || !chunk_ok(chunk) || M < 1) return GPBO_ERR_ARG;
     return qei_layout(Np, chunk, M).total;
 }
 
@@ -1058,8 +1041,8 @@ extern "C" int gpbo_posterior_qei_f64(const double *Xs, int64_t M, const double 
                                       int64_t work_bytes, gpbo_profile *prof, void *stream) {
     if (!Xs || !X || !U || !alpha || !Z || !result || !work) return GPBO_ERR_ARG;
     if (M < QQ || M % QQ || N < 1 || Np != gpbo_padded_n(N) || S < 1 || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
-    if (chunk < GPBO_CHUNK_GRANULE || chunk % GPBO_CHUNK_GRANULE || chunk > GPBO_CHUNK_MAX) return GPBO_ERR_ARG;
-    if (((uintptr_t)work & 255) || ((uintptr_t)U & 15)) return GPBO_ERR_ARG;
+    if (!chunk_ok(chunk)) return GPBO_ERR_ARG;
+    if (!aligned_to(work, 256) || !aligned_to(U, 16)) return GPBO_ERR_ARG;
     const QeiLayout L = qei_layout(Np, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     QeiLs ls;
@@ -1085,53 +1068,40 @@ extern "C" int gpbo_posterior_qei_f64(const double *Xs, int64_t M, const double 
     int rc = gpbo_scale_points_f64(X, N, Np, d, ls_host, Xsc, stream);
     if (rc != GPBO_OK) return rc;
     int64_t nparts = 0;
+    ProfileRecorder slots(prof);
     for (int64_t s = 0; s < M; s += chunk) {
         const int64_t Mc = (M - s < chunk) ? (M - s) : chunk;
         // one profile slot per chunk: kbegin | K(X*,X) | begin | variance launch (+ its finish) | end | qEI launch | qend
-        const bool rec = prof && prof->count < prof->capacity;
-        auto mark = [&](void *ev) { return hipEventRecord(reinterpret_cast<hipEvent_t>(ev), st) == hipSuccess; };
-        if (rec && !mark(prof->kbegin[prof->count])) return GPBO_ERR_LAUNCH;
+        // (the qEI launch lies between a slot's end and the next K(X*,X) launch: no chaining)
+        if (!slots.kstar(st, false)) return GPBO_ERR_LAUNCH;
         rc = gpbo_kstar_mu_f64(Xs + s * d, Mc, Xsc, N, Np, d, ls_host, alpha, 0.0, 0, KsT, chunk, mu_part, stream);
         if (rc != GPBO_OK) return rc;
-        if (rec && !mark(prof->begin[prof->count])) return GPBO_ERR_LAUNCH;
+        if (!slots.begin(st)) return GPBO_ERR_LAUNCH;
         const int64_t nblk = (Mc + BM - 1) / BM;
         // the variance kernel in its GRAM form leaves the batches' partial V V^T blocks (vbuf) and mu; its own single-point
         // acquisition result is ignored.  Large calls: column groups on one XCD as in gpbo_posterior_acq_f64 (each group
         // leaves the Gram partials of its column blocks; the mean then comes from split_finish_kernel).
-        static const int xg_env = getenv("GPBO_F64_GROUPS") ? atoi(getenv("GPBO_F64_GROUPS")) : 8;
-        int gram_parts = WQ;   // partial Gram blocks per batch: one per column group of waves and of workgroups
-        if (xg_env > 1 && xg_env <= 16 && M >= 32768 && Np / BN >= 2 * xg_env) {
-            gram_parts = xg_env * WQ;
-            double *ss_part = reinterpret_cast<double *>(w + L.ssp_off);
-            const int64_t grid1 = (nblk + 7) / 8 * 8 * xg_env;
-            hipLaunchKernelGGL((sigma_acq_kernel<0, true>), dim3((unsigned)grid1), dim3(NW * 64), 0, st, KsT, chunk, U, (int)Np, mu_part,
-                               (int)(Np / GPBO_KS_SLICE), Mc, prior_var, (int)GPBO_ACQ_LCB, 0.0, 0.0, (int64_t)0,
-                               (double *)nullptr, (double *)nullptr, (double *)nullptr, spv, spi, nan_scratch, Vb, ss_part,
-                               xg_env, (int)nblk, 0);
-            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, xg_env, chunk, mu_part,
+        const int xg = f64_column_groups(M, Np);
+        const int gram_parts = xg * WQ;   // partial Gram blocks per batch: one per column group of waves and of workgroups
+        double *ss_part = xg > 1 ? reinterpret_cast<double *>(w + L.ssp_off) : nullptr;
+        const int64_t grid = xg > 1 ? (nblk + 7) / 8 * 8 * xg : nblk;
+        hipLaunchKernelGGL((sigma_acq_kernel<0, true>), dim3((unsigned)grid), dim3(NW * 64), 0, st, KsT, chunk, U, (int)Np, mu_part,
+                           (int)(Np / GPBO_KS_SLICE), Mc, prior_var, (int)GPBO_ACQ_LCB, 0.0, 0.0, (int64_t)0,
+                           xg > 1 ? (double *)nullptr : mu, (double *)nullptr, (double *)nullptr, spv, spi, nan_scratch, Vb,
+                           ss_part, xg, (int)nblk, 0);
+        if (xg > 1)
+            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, xg, chunk, mu_part,
                                (int)(Np / GPBO_KS_SLICE), Mc, prior_var, (int)GPBO_ACQ_LCB, 0.0, 0.0, (int64_t)0, mu,
                                (double *)nullptr, (double *)nullptr, (double *)nullptr, spv, spi, nan_scratch, 0.0);
-        } else {
-            hipLaunchKernelGGL((sigma_acq_kernel<0, true>), dim3((unsigned)nblk), dim3(NW * 64), 0, st, KsT, chunk, U, (int)Np, mu_part,
-                               (int)(Np / GPBO_KS_SLICE), Mc, prior_var, (int)GPBO_ACQ_LCB, 0.0, 0.0, (int64_t)0, mu,
-                               (double *)nullptr, (double *)nullptr, spv, spi, nan_scratch, Vb, (double *)nullptr, 1,
-                               (int)nblk, 0);
-        }
         GPBO_CHECK_LAUNCH();
-        if (rec && !mark(prof->end[prof->count])) return GPBO_ERR_LAUNCH;
+        if (!slots.end_open(st)) return GPBO_ERR_LAUNCH;
         const int64_t nbatch = Mc / QQ;
         const int64_t qblk = (nbatch + 3) / 4;
         hipLaunchKernelGGL(qei_kernel, dim3((unsigned)qblk), dim3(256), 0, st, Vb, gram_parts, chunk / 8, mu, Xs + s * d, (int)d, ls, nbatch,
                            prior_var, f_best, xi, Z, (int)S, batch_offset + s / QQ, qei_out ? qei_out + s / QQ : nullptr,
                            part_val + nparts, part_idx + nparts, nan_count);
         GPBO_CHECK_LAUNCH();
-        if (rec) {
-            if (!mark(prof->qend[prof->count])) return GPBO_ERR_LAUNCH;
-            prof->kmode[prof->count] = 1;
-            prof->qmode[prof->count] = 1;
-            prof->cands[prof->count] = Mc;
-            ++prof->count;
-        }
+        if (!slots.qend(st, Mc)) return GPBO_ERR_LAUNCH;
         nparts += qblk;
     }
     return gpbo_launch_argmax_finish(part_val, part_idx, nparts, nan_count, result, st);

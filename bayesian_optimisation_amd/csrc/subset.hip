@@ -539,8 +539,8 @@ extern "C" int gpbo_fps_order_f64(const double *X, const double *y, int64_t N, i
     // bounded waits run out (~1 s), every workgroup leaves, fps_check_kernel installs the identity order (the arrival order:
     // an exact route, it only prunes less) and gpbo_fps_order_status reports the fall-back.
     // GPBO_FPS_SHAPE="threads,points" overrides the shape (A/B runs; ignored when the points do not fit).
-    static const int mute_env = getenv("GPBO_FPS_MUTE") ? atoi(getenv("GPBO_FPS_MUTE")) : -1;
-    static const char *shape_env = getenv("GPBO_FPS_SHAPE");
+    static const int mute_env = env_int("GPBO_FPS_MUTE", -1);
+    static const char *shape_env = env_str("GPBO_FPS_SHAPE");
     mute_wg = mute_env;
     if (shape_env) {
         int eth = 0, epts = 0;

@@ -39,6 +39,21 @@ def _torch():
     return torch
 
 
+def acq_params(acquisition: str, explore: float = 4.0, f_best: Optional[float] = None, xi: float = 0.0) -> tuple:
+    """(kind, p0, p1) of the C ABI for an acquisition by name (include/gpbo.h: GPBO_ACQ_*)."""
+    if acquisition == "lcb":
+        return _lib.ACQ_LCB, float(explore), 0.0
+    if acquisition == "ei":
+        if f_best is None:
+            raise ValueError("EI needs f_best (the incumbent minimum)")
+        return _lib.ACQ_EI, float(f_best), float(xi)
+    raise ValueError(f"unknown acquisition {acquisition!r}")
+
+
+def _round_up(n: int, granule: int = _lib.CHUNK_GRANULE) -> int:
+    return (n + granule - 1) // granule * granule
+
+
 @dataclass
 class ScoreResult:
     best_val: float
@@ -61,9 +76,21 @@ class DeviceGP:
             raise ValueError(f"chunk must be a multiple of {_lib.CHUNK_GRANULE}")
         self.chunk = int(chunk)
         self.N = self.Np = self.d = 0
-        self._work_post = None
-        self._work_fact = None
+        self.X = self.y = self.ls_h = None   # the observations and length scales of the last factorise() / load_state_dict()
+        self.jitter1 = self.jitter2 = 0.0
+        self.n_appended = 0
+        self._owns_xy = False
         self.K = self.U = self.alpha = None
+        # workspaces, kept from call to call and only ever grown (_workspace)
+        self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
+        self._work_qei = self._work_ard = None
+        self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
+        self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
+        self.U8, self._u8_valid = None, False                   # prepare_i8()
+        self._screen_mu = self._screen_var = self._bound_ub = None
+        self._fit_bufs = None
+        self._keep = self._keep_ard = None   # inputs of the last enqueued call, alive until the stream has consumed them
+        self.last_screen = None      # statistics of the last screened call (dict)
         self.perm = None             # factorise(order="fps"): device int64 [N], row of the factorisation -> the caller's row
         # the 32-byte result record and the factorisation's info word share one small buffer, so that a step can read
         # both back with a single device-to-host copy (each copy is a host synchronisation)
@@ -83,24 +110,22 @@ class DeviceGP:
     def reset_profile(self):
         self.lib.gpbo_profile_reset(self._profile)
 
+    def _read_profile(self, name):
+        ms, n, c = C.c_double(0), C.c_int64(0), C.c_int64(0)
+        _lib.check(getattr(self.lib, name)(self._profile, C.byref(ms), C.byref(n), C.byref(c)), name)
+        return ms.value, n.value, c.value
+
     def read_profile(self):
         """(total ms, launches, candidates) summed over the recorded sigma/acquisition launches."""
-        ms, n, c = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        _lib.check(self.lib.gpbo_profile_read(self._profile, C.byref(ms), C.byref(n), C.byref(c)), "gpbo_profile_read")
-        return ms.value, n.value, c.value
+        return self._read_profile("gpbo_profile_read")
 
     def read_profile_kstar(self):
         """(total ms, launches, candidates) of the K(X*,X) launches recorded beside the variance launches."""
-        ms, n, c = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        _lib.check(self.lib.gpbo_profile_read_kstar(self._profile, C.byref(ms), C.byref(n), C.byref(c)),
-                   "gpbo_profile_read_kstar")
-        return ms.value, n.value, c.value
+        return self._read_profile("gpbo_profile_read_kstar")
 
     def read_profile_qei(self):
         """(total ms, launches, candidates) of the qEI launches recorded by score_qei()."""
-        ms, n, c = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        _lib.check(self.lib.gpbo_profile_read_qei(self._profile, C.byref(ms), C.byref(n), C.byref(c)), "gpbo_profile_read_qei")
-        return ms.value, n.value, c.value
+        return self._read_profile("gpbo_profile_read_qei")
 
     # -- helpers -------------------------------------------------------------------------------
     def _stream(self):
@@ -116,6 +141,38 @@ class DeviceGP:
     @staticmethod
     def _ptr(t):
         return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+    def _candidates(self, Xs):
+        """(Xs as a contiguous fp64 device tensor, its row count); refuses anything but (M, d)."""
+        Xsd = self._dev(Xs)
+        if Xsd.dim() != 2 or int(Xsd.shape[1]) != self.d:
+            raise ValueError("Xs must be (M, d) with the same d as X")
+        return Xsd, int(Xsd.shape[0])
+
+    def _chunk_for(self, M: int, granule: int = _lib.CHUNK_GRANULE) -> int:
+        """self.chunk, but no more than M candidates need, in whole granules."""
+        return _round_up(min(self.chunk, _round_up(M, granule)), granule)
+
+    def _workspace(self, slot_name: str, nbytes: int, free_first: bool = False):
+        """The workspace tensor kept in attribute `slot_name`, grown to hold nbytes (the answer of a size query; negative:
+        the library refused the sizes).  free_first: the old buffer goes before the new one comes - for the slots that
+        reach GiBs, where the two must not coexist."""
+        if nbytes < 0:
+            raise _lib.GpboError(f"{slot_name}: the workspace size query refused the sizes")
+        w = getattr(self, slot_name)
+        if w is None or w.numel() * 8 < nbytes:
+            if free_first:
+                w = None
+                setattr(self, slot_name, None)
+            w = self.torch.empty((nbytes + 7) // 8, dtype=self.torch.float64, device=self.device)
+            setattr(self, slot_name, w)
+        return w
+
+    def _read(self, res_tuple) -> ScoreResult:
+        """The synchronous form of what a score_async* call returned (reads the result record: synchronises)."""
+        res, mu, sigma, acq = res_tuple
+        v, i, n = self.read_result(res)
+        return ScoreResult(v, i, n, mu, sigma, acq)
 
     # -- factorisation (once per BO step) ---------------------------------------------------------
     def factorise(self, X, y, ls, jitter1: float = JITTER_KERNEL, jitter2: float = JITTER_ASSEMBLY,
@@ -150,8 +207,7 @@ class DeviceGP:
             if order == "fps" and d <= _lib.MAX_D and J < N:
                 # (fewer observations than one prefix, or the slow any-d kernels: the bound route is not taken anyway)
                 wob = int(self.lib.gpbo_fps_order_workspace_bytes(N))
-                if getattr(self, "_work_order", None) is None or self._work_order.numel() * 8 < wob:
-                    self._work_order = torch.empty((wob + 7) // 8, dtype=torch.float64, device=self.device)
+                self._workspace("_work_order", wob)
                 perm = torch.empty(N, dtype=torch.int64, device=self.device)
                 Xp, yp = torch.empty_like(Xd), torch.empty_like(yd)
                 st = self.lib.gpbo_fps_order_f64(self._ptr(Xd), self._ptr(yd), N, d, ls_h.ctypes.data_as(C.c_void_p), J,
@@ -160,7 +216,7 @@ class DeviceGP:
                 _lib.check(st, "gpbo_fps_order_f64")
                 # did the co-operative selection give up (a workgroup never scheduled) and install the arrival order?  The
                 # flag stays on the device until somebody asks (order_fell_back(), last_screen): no synchronisation here
-                if getattr(self, "_order_flag", None) is None:
+                if self._order_flag is None:
                     self._order_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
                 _lib.check(self.lib.gpbo_fps_order_status(self._ptr(self._work_order), N, self._ptr(self._order_flag),
                                                           self._stream()), "gpbo_fps_order_status")
@@ -170,7 +226,7 @@ class DeviceGP:
             self.jitter1, self.jitter2 = float(jitter1), float(jitter2)
             self._owns_xy = False
             self.n_appended = 0  # columns of U built by append() since the last full factorisation
-            if getattr(self, "K", None) is None or self.K.shape[0] != Np or self.U.shape[0] != Np:
+            if self.K is None or self.K.shape[0] != Np or self.U.shape[0] != Np:
                 # the factor buffers (and the workspace) are kept from step to step: a BO loop refactorises
                 # at the same padded size many times, and fresh 100-MB allocations cost more than the kernels
                 self.K = torch.empty((Np, Np), dtype=torch.float64, device=self.device)
@@ -180,9 +236,7 @@ class DeviceGP:
             self._u32_valid = False
             self._u8_valid = False
             wbytes = int(self.lib.gpbo_factorise_workspace_bytes(Np))
-            if self._work_fact is None or self._work_fact.numel() * 8 < wbytes:
-                self._work_fact = torch.empty(wbytes // 8, dtype=torch.float64, device=self.device)
-            work = self._work_fact
+            work = self._workspace("_work_fact", wbytes)
             st = self.lib.gpbo_factorise_f64(self._ptr(Xd), self._ptr(yd), N, d, ls_h.ctypes.data_as(C.c_void_p),
                                              jitter1, jitter2, Np, self._ptr(self.K), self._ptr(self.U),
                                              self._ptr(self.alpha), self._ptr(self.info), self._ptr(work), wbytes,
@@ -216,7 +270,7 @@ class DeviceGP:
         """True when factorise(order="fps") came back with the ARRIVAL order because the co-operative selection gave up (one of
         its workgroups was never scheduled: bounded waits, csrc/subset.hip).  Exact either way - but candidate shards of one
         step must hold the same factorisation, so PointSelector votes on this flag.  Reads one device word (synchronises)."""
-        if self.perm is None or getattr(self, "_order_flag", None) is None:
+        if self.perm is None or self._order_flag is None:
             return False
         return bool(int(self._order_flag.item()))
 
@@ -385,13 +439,9 @@ class DeviceGP:
 
     # -- scoring ------------------------------------------------------------------------------------
     def _ensure_post_workspace(self, M):
-        torch = self.torch
-        chunk = min(self.chunk, (M + _lib.CHUNK_GRANULE - 1) // _lib.CHUNK_GRANULE * _lib.CHUNK_GRANULE)
+        chunk = self._chunk_for(M)
         need = int(self.lib.gpbo_posterior_workspace_bytes(self.Np, chunk, M))
-        if need < 0:
-            raise _lib.GpboError("gpbo_posterior_workspace_bytes: invalid sizes")
-        if self._work_post is None or self._work_post.numel() * 8 < need:
-            self._work_post = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+        self._workspace("_work_post", need)
         return chunk, need
 
     def score_async(self, Xs, acquisition: str = "lcb", explore: float = 4.0, f_best: Optional[float] = None,
@@ -400,18 +450,8 @@ class DeviceGP:
         """Enqueue K(X*,X) + mu + sigma + acquisition + arg-max for all rows of Xs; no host sync.
         Returns (result_tensor[int64 x4 on device], mu, sigma, acq)."""
         torch = self.torch
-        Xsd = self._dev(Xs)
-        if Xsd.dim() != 2 or int(Xsd.shape[1]) != self.d:
-            raise ValueError("Xs must be (M, d) with the same d as X")
-        M = int(Xsd.shape[0])
-        if acquisition == "lcb":
-            kind, p0, p1 = _lib.ACQ_LCB, float(explore), 0.0
-        elif acquisition == "ei":
-            if f_best is None:
-                raise ValueError("EI needs f_best (the incumbent minimum)")
-            kind, p0, p1 = _lib.ACQ_EI, float(f_best), float(xi)
-        else:
-            raise ValueError(f"unknown acquisition {acquisition!r}")
+        Xsd, M = self._candidates(Xs)
+        kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
         if diag_add != 0.0 and self.perm is not None:
             # the N == M quirk (point_selector.py:173) adds to entry (i, i) of k(X, X*): candidate i against the caller's
             # observation i, which is not row i of a permuted factorisation
@@ -444,13 +484,11 @@ class DeviceGP:
         torch = self.torch
         Np32 = int(self.lib.gpbo_padded_n_f32(self.N))
         with torch.cuda.device(self.device):
-            if getattr(self, "U32", None) is None or self.U32.shape[0] != Np32:
+            if self.U32 is None or self.U32.shape[0] != Np32:
                 self.U32 = torch.empty((Np32, Np32), dtype=torch.float32, device=self.device)
             st = self.lib.gpbo_prepare_f32(self._ptr(self.U), None, self.Np, self._ptr(self.U32), None, Np32,
                                            self._stream())
             _lib.check(st, "gpbo_prepare_f32")
-        if getattr(self, "Np32", 0) != Np32:
-            self._work_post32 = None
         self.Np32 = Np32
         self._u32_valid = True
         return self
@@ -464,7 +502,7 @@ class DeviceGP:
             need = int(self.lib.gpbo_prepare_i8_bytes(self.Np))
             if need < 0:
                 raise _lib.GpboError("gpbo_prepare_i8_bytes: invalid size")
-            if getattr(self, "U8", None) is None or self.U8.numel() < need:
+            if self.U8 is None or self.U8.numel() < need:
                 self.U8 = torch.empty(need, dtype=torch.uint8, device=self.device)
             st = self.lib.gpbo_prepare_i8(self._ptr(self.U), self.Np, self._ptr(self.U8), need, self._stream())
             _lib.check(st, "gpbo_prepare_i8")
@@ -475,35 +513,25 @@ class DeviceGP:
     SCREEN_TAU0_I8C = 1e-3      # coarse int8 screen (three digits per operand): |var64 - var| ~ 2e-4 at N = 4096
 
     def _score_screened(self, mode, Xs, acquisition, explore, f_best, xi, dense, idx_offset, diag_add, prior_var):
-        self._need_unrolled_d(f"the {mode} screen")
         """A reduced-cost pass over all rows of Xs (mode "f32": fp32 matrix cores; "i8": int8 slices on the integer
         matrix cores), then the fp64 decision (gpbo_rescore_f64): the result record holds the fp64 kernels' maximum and
         its lowest index.  Dense outputs (mu exactly the fp64 path's; sigma / acq with the screen's variance) are
         float64 tensors.  Unlike score_async this call synchronises (the survivor count is read back).
         `last_screen` keeps the statistics of the call."""
+        self._need_unrolled_d(f"the {mode} screen")
         torch = self.torch
-        Xsd = self._dev(Xs)
-        if Xsd.dim() != 2 or int(Xsd.shape[1]) != self.d:
-            raise ValueError("Xs must be (M, d) with the same d as X")
-        M = int(Xsd.shape[0])
-        if acquisition == "lcb":
-            kind, p0, p1 = _lib.ACQ_LCB, float(explore), 0.0
-        elif acquisition == "ei":
-            if f_best is None:
-                raise ValueError("EI needs f_best (the incumbent minimum)")
-            kind, p0, p1 = _lib.ACQ_EI, float(f_best), float(xi)
-        else:
-            raise ValueError(f"unknown acquisition {acquisition!r}")
+        Xsd, M = self._candidates(Xs)
+        kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
         if diag_add != 0.0:
             # N == M shape quirk (point_selector.py:173): gathered rows lose the index the quirk is keyed on
             self.last_screen = dict(fallback=True, reason="diag_add")
             return self.score_async(Xsd, acquisition, explore, f_best, xi, dense, idx_offset, diag_add, prior_var)
-        if mode == "f32" and (not getattr(self, "_u32_valid", False) or getattr(self, "U32", None) is None):
+        if mode == "f32" and (not self._u32_valid or self.U32 is None):
             self.prepare_f32()
-        if mode in ("i8", "i8c") and (not getattr(self, "_u8_valid", False) or getattr(self, "U8", None) is None):
+        if mode in ("i8", "i8c") and (not self._u8_valid or self.U8 is None):
             self.prepare_i8()
         with torch.cuda.device(self.device):
-            if getattr(self, "_screen_mu", None) is None or self._screen_mu.numel() < M:
+            if self._screen_mu is None or self._screen_mu.numel() < M:
                 self._screen_mu = torch.empty(M, dtype=torch.float64, device=self.device)
                 self._screen_var = torch.empty(M, dtype=torch.float64, device=self.device)
             mu = sigma = acq = None
@@ -513,17 +541,12 @@ class DeviceGP:
             prof = self._profile if self.profile_active else None
             lsp = self.ls_h.ctypes.data_as(C.c_void_p)
             if mode == "f32":
-                chunk = min(self.chunk, (M + 1023) // 1024 * 1024)
-                chunk = (chunk + 1023) // 1024 * 1024
+                chunk = self._chunk_for(M, 1024)
                 need = int(self.lib.gpbo_posterior_workspace_bytes_f32(self.Np32, chunk, M))
             else:
-                chunk = min(self.chunk, (M + _lib.CHUNK_GRANULE - 1) // _lib.CHUNK_GRANULE * _lib.CHUNK_GRANULE)
+                chunk = self._chunk_for(M)
                 need = int(self.lib.gpbo_posterior_workspace_bytes_i8(self.Np, chunk, M))
-            if need < 0:
-                raise _lib.GpboError("screen workspace: invalid sizes")
-            if getattr(self, "_work_screen", None) is None or self._work_screen.numel() * 8 < need:
-                self._work_screen = None
-                self._work_screen = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+            self._workspace("_work_screen", need, free_first=True)
             if mode == "f32":
                 st = self.lib.gpbo_posterior_acq_f32(
                     self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np32, self.d, lsp, self._ptr(self.U32),
@@ -544,10 +567,7 @@ class DeviceGP:
             cap = self.screen_cap if self.screen_cap else max(4096, min(M, max(M // 16, 1 << 16)))
             chunk64 = self.SCREEN_CHUNK64
             rbytes = int(self.lib.gpbo_rescore_workspace_bytes(self.Np, cap, chunk64))
-            if rbytes < 0:
-                raise _lib.GpboError("gpbo_rescore_workspace_bytes: invalid sizes")
-            if getattr(self, "_work_rescore", None) is None or self._work_rescore.numel() * 8 < rbytes:
-                self._work_rescore = torch.empty((rbytes + 7) // 8, dtype=torch.float64, device=self.device)
+            self._workspace("_work_rescore", rbytes)
             stats = _lib.ScreenStats()
             stride = max(1, M // self.SCREEN_SAMPLE)
             st = self.lib.gpbo_rescore_f64(
@@ -578,9 +598,7 @@ class DeviceGP:
         return self._score_screened("i8", Xs, acquisition, explore, f_best, xi, dense, idx_offset, diag_add, prior_var)
 
     def score_i8(self, Xs, **kw) -> ScoreResult:
-        res, mu, sigma, acq = self.score_async_i8(Xs, **kw)
-        v, i, n = self.read_result(res)
-        return ScoreResult(v, i, n, mu, sigma, acq)
+        return self._read(self.score_async_i8(Xs, **kw))
 
     def score_async_i8c(self, Xs, acquisition: str = "lcb", explore: float = 4.0, f_best: Optional[float] = None,
                         xi: float = 0.0, dense: bool = False, idx_offset: int = 0, diag_add: float = 0.0,
@@ -590,14 +608,10 @@ class DeviceGP:
         return self._score_screened("i8c", Xs, acquisition, explore, f_best, xi, dense, idx_offset, diag_add, prior_var)
 
     def score_i8c(self, Xs, **kw) -> ScoreResult:
-        res, mu, sigma, acq = self.score_async_i8c(Xs, **kw)
-        v, i, n = self.read_result(res)
-        return ScoreResult(v, i, n, mu, sigma, acq)
+        return self._read(self.score_async_i8c(Xs, **kw))
 
     def score_f32(self, Xs, **kw) -> ScoreResult:
-        res, mu, sigma, acq = self.score_async_f32(Xs, **kw)
-        v, i, n = self.read_result(res)
-        return ScoreResult(v, i, n, mu, sigma, acq)
+        return self._read(self.score_async_f32(Xs, **kw))
 
     # -- prefix-bound screen: exact branch and bound, all fp64 ---------------------------------------------------
     ARD_KEEP_WORKSPACE_BYTES = 1 << 28   # the batched ARD workspace is dropped after a call when larger than this
@@ -622,18 +636,8 @@ class DeviceGP:
         if self.d > _lib.MAX_D:   # the slow any-d kernels serve the plain pass only
             self.last_screen = dict(mode="bound", fallback=True, reason="d > 16")
             return self.score_async(Xs, acquisition, explore, f_best, xi, dense, idx_offset, diag_add, prior_var)
-        Xsd = self._dev(Xs)
-        if Xsd.dim() != 2 or int(Xsd.shape[1]) != self.d:
-            raise ValueError("Xs must be (M, d) with the same d as X")
-        M = int(Xsd.shape[0])
-        if acquisition == "lcb":
-            kind, p0, p1 = _lib.ACQ_LCB, float(explore), 0.0
-        elif acquisition == "ei":
-            if f_best is None:
-                raise ValueError("EI needs f_best (the incumbent minimum)")
-            kind, p0, p1 = _lib.ACQ_EI, float(f_best), float(xi)
-        else:
-            raise ValueError(f"unknown acquisition {acquisition!r}")
+        Xsd, M = self._candidates(Xs)
+        kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
         J = int(prefix) if prefix else self.bound_prefix()
         J2 = int(prefix2) if prefix2 is not None else (4 * J if 8 * J <= self.Np else 0)   # second level: survivors only
         reason = None
@@ -657,7 +661,7 @@ class DeviceGP:
             return self.score_async(Xsd, acquisition, explore, f_best, xi, dense, idx_offset, diag_add, prior_var)
         with torch.cuda.device(self.device):
             chunk, wbytes = self._ensure_post_workspace(M)
-            if getattr(self, "_bound_ub", None) is None or self._bound_ub.numel() < M:
+            if self._bound_ub is None or self._bound_ub.numel() < M:
                 self._bound_ub = torch.empty(M, dtype=torch.float64, device=self.device)
             lsp = self.ls_h.ctypes.data_as(C.c_void_p)
             st = self.lib.gpbo_posterior_prefix_f64(
@@ -672,10 +676,7 @@ class DeviceGP:
             cap = self.screen_cap if self.screen_cap else max(4096, M)
             chunk64 = self.SCREEN_CHUNK64
             rbytes = int(self.lib.gpbo_rescore_workspace_bytes(self.Np, cap, chunk64))
-            if rbytes < 0:
-                raise _lib.GpboError("gpbo_rescore_workspace_bytes: invalid sizes")
-            if getattr(self, "_work_rescore", None) is None or self._work_rescore.numel() * 8 < rbytes:
-                self._work_rescore = torch.empty((rbytes + 7) // 8, dtype=torch.float64, device=self.device)
+            self._workspace("_work_rescore", rbytes)
             stats = _lib.ScreenStats()
             stride = max(1, M // self.SCREEN_SAMPLE)
             st = self.lib.gpbo_bound_select_f64(
@@ -693,9 +694,7 @@ class DeviceGP:
         return self._result, None, None, None
 
     def score_bound(self, Xs, **kw) -> ScoreResult:
-        res, mu, sigma, acq = self.score_async_bound(Xs, **kw)
-        v, i, n = self.read_result(res)
-        return ScoreResult(v, i, n, mu, sigma, acq)
+        return self._read(self.score_async_bound(Xs, **kw))
 
     # -- q = 8 Monte-Carlo Expected Improvement (BASELINE config 5) ---------------------------------------
     def score_qei_async(self, Xs, Z, f_best: float, xi: float = 0.0, dense: bool = False, batch_offset: int = 0,
@@ -709,12 +708,9 @@ class DeviceGP:
         if M % 8 or int(Zd.shape[1]) != 8:
             raise ValueError("qEI needs M % 8 == 0 and base samples of shape (S, 8)")
         with torch.cuda.device(self.device):
-            chunk = min(self.chunk, (M + _lib.CHUNK_GRANULE - 1) // _lib.CHUNK_GRANULE * _lib.CHUNK_GRANULE)
+            chunk = self._chunk_for(M)
             need = int(self.lib.gpbo_qei_workspace_bytes(self.Np, chunk, M))
-            if need < 0:
-                raise _lib.GpboError("gpbo_qei_workspace_bytes: invalid sizes")
-            if getattr(self, "_work_qei", None) is None or self._work_qei.numel() * 8 < need:
-                self._work_qei = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+            self._workspace("_work_qei", need)
             qei = torch.empty(M // 8, dtype=torch.float64, device=self.device) if dense else None
             st = self.lib.gpbo_posterior_qei_f64(
                 self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
@@ -750,16 +746,14 @@ class DeviceGP:
         return best_val, int(r[1]), int(r[2])
 
     def score(self, Xs, **kw) -> ScoreResult:
-        res, mu, sigma, acq = self.score_async(Xs, **kw)
-        v, i, n = self.read_result(res)
-        return ScoreResult(v, i, n, mu, sigma, acq)
+        return self._read(self.score_async(Xs, **kw))
 
     def acquisition_on_posterior(self, mu, sigma, acquisition: str = "lcb", explore: float = 4.0,
                                  f_best: Optional[float] = None, xi: float = 0.0, idx_offset: int = 0) -> ScoreResult:
         """Second acquisition on dense device mu/sigma (lower_confidence_bound(explore) after the fact)."""
         torch = self.torch
         M = int(mu.numel())
-        kind, p0, p1 = (_lib.ACQ_LCB, float(explore), 0.0) if acquisition == "lcb" else (_lib.ACQ_EI, float(f_best), float(xi))
+        kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
         with torch.cuda.device(self.device):
             acq = torch.empty(M, dtype=torch.float64, device=self.device)
             wbytes = int(self.lib.gpbo_acq_workspace_bytes())
@@ -788,7 +782,7 @@ class DeviceGP:
         res = self.nlml_grid_device(X, y, ls_cells, jitter, likelihood).cpu().numpy()   # synchronises: the workspace is idle
         # the scratch slots can be GiBs (512 x (N + 16) x N x 8 bytes): kept between the calls of one search (a
         # coordinate-wise ARD search calls this once per axis and sweep) only while they are small
-        if getattr(self, "_work_ard", None) is not None and self._work_ard.numel() * 8 > self.ARD_KEEP_WORKSPACE_BYTES:
+        if self._work_ard is not None and self._work_ard.numel() * 8 > self.ARD_KEEP_WORKSPACE_BYTES:
             self._work_ard = None
         return res
 
@@ -816,11 +810,7 @@ class DeviceGP:
                 # one persistent workgroup per cell, the whole factorisation in one launch (csrc/ard.hip, round 5)
                 out = torch.empty(G, dtype=torch.float64 if logdet else torch.float32, device=self.device)
                 need = int(self.lib.gpbo_nlml_grid_batched_workspace_bytes(N, G))
-                if need < 0:
-                    raise _lib.GpboError("gpbo_nlml_grid_batched_workspace_bytes: invalid sizes")
-                if getattr(self, "_work_ard", None) is None or self._work_ard.numel() * 8 < need:
-                    self._work_ard = None
-                    self._work_ard = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+                self._workspace("_work_ard", need, free_first=True)
                 fn = self.lib.gpbo_nlml_grid_batched_logdet_f64 if logdet else self.lib.gpbo_nlml_grid_batched_f64
                 st = fn(self._ptr(Xd), self._ptr(yd), N, d, self._ptr(cells), G, float(jitter), self._ptr(out),
                         self._ptr(self._work_ard), need, self._stream())
@@ -837,7 +827,7 @@ class DeviceGP:
     def _fit_buffers(self, Np: int, d: int):
         """The fit's own factor buffers (K, U, alpha, info, workspaces): the surrogate's K / U / alpha stay untouched."""
         torch = self.torch
-        fb = getattr(self, "_fit_bufs", None)
+        fb = self._fit_bufs
         if fb is None or fb["Np"] != Np or fb["d"] < d:
             self._fit_bufs = None
             wf = int(self.lib.gpbo_factorise_workspace_bytes(Np))
@@ -853,9 +843,7 @@ class DeviceGP:
         return fb
 
     def _fit_bytes(self) -> int:
-        fb = getattr(self, "_fit_bufs", None)
-        if fb is None:
-            return 0
+        fb = self._fit_bufs or {}
         return sum(t.numel() * t.element_size() for t in fb.values() if isinstance(t, self.torch.Tensor))
 
     def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL):
@@ -934,7 +922,7 @@ class DeviceGP:
         torch = self.torch
         Xsd = self._dev(Xs)
         M = int(Xsd.shape[0])
-        ldk = (M + _lib.CHUNK_GRANULE - 1) // _lib.CHUNK_GRANULE * _lib.CHUNK_GRANULE
+        ldk = _round_up(M)
         with torch.cuda.device(self.device):
             kst = torch.empty((self.Np, ldk), dtype=torch.float64, device=self.device)
             mup = torch.empty((self.Np // 64, ldk), dtype=torch.float64, device=self.device)

@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL
+from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, acq_params
 from .point_selector import PointSelector
 
 
@@ -74,14 +74,7 @@ def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_
     M = Xs.shape[0]
     if Xs.shape[1] != d or ls.size != d or y.size != N:
         raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
-    if acquisition == "lcb":
-        kind, p0, p1 = _lib.ACQ_LCB, float(explore), 0.0
-    elif acquisition == "ei":
-        if f_best is None:
-            raise ValueError("EI needs f_best (the incumbent minimum)")
-        kind, p0, p1 = _lib.ACQ_EI, float(f_best), float(xi)
-    else:
-        raise ValueError(f"unknown acquisition {acquisition!r}")
+    kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
     mu = np.empty(M) if dense else None
     sigma = np.empty(M) if dense else None
     acq = np.empty(M) if dense else None
