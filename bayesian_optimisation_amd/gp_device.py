@@ -700,9 +700,13 @@ class DeviceGP:
     def score_qei_async(self, Xs, Z, f_best: float, xi: float = 0.0, dense: bool = False, batch_offset: int = 0,
                         prior_var: float = PRIOR_VAR):
         """Enqueue qEI over consecutive batches of 8 rows of Xs; Z = [S x 8] base samples; no host sync.
-        Returns (result_tensor, qei or None); the result's best_idx is a BATCH index."""
+        Returns (result_tensor, qei or None); the result's best_idx is a BATCH index.
+        Z must be finite: a host array is checked here, a device tensor is the caller's (the kernel skips the improvements
+        a NaN sample makes NaN instead of reporting them: DESIGN.md 1, "qEI and NaN")."""
         self._need_unrolled_d("qEI")
         torch = self.torch
+        if isinstance(Z, np.ndarray) and not np.isfinite(Z).all():
+            raise ValueError("qEI needs finite base samples Z")
         Xsd, Zd = self._dev(Xs), self._dev(Z)
         M, S = int(Xsd.shape[0]), int(Zd.shape[0])
         if M % 8 or int(Zd.shape[1]) != 8:

@@ -15,6 +15,7 @@ from bayesian_optimisation_amd import DeviceGP  # noqa: E402
 from bayesian_optimisation_amd import distributed as D  # noqa: E402
 from bayesian_optimisation_amd.synthetic import make_problem  # noqa: E402
 from oracle import gp_oracle as O  # noqa: E402
+import qei_ref  # noqa: E402  (tests/)
 
 
 def _first_argmax(a):
@@ -139,6 +140,14 @@ def test_config5_full_size_qei_n2048_m2e20():
     top2 = np.sort(ref)[-2:]
     if top2[1] - top2[0] > 1e-7:
         assert batches[_first_argmax(ref)] == r.best_idx
+    # the same rows with an incumbent that leaves none of them at 0 == 0 (tests/qei_ref.py): the oracle's median mean there
+    f_mid = qei_ref.incumbent(X, y, Xs[rows], ls, 0.5)
+    r = gp.score_qei(Xsd, Z, f_mid, dense=True)
+    got = r.acq.cpu().numpy()
+    ref = O.qei_mc(X, y, Xs[rows], ls, Z, f_mid)
+    qei_ref.assert_informative(ref)
+    assert r.nan_count == 0 and r.best_idx == _first_argmax(got) and r.best_val == got.max()
+    assert np.max(np.abs(got[batches] - ref)) <= 1e-9 * max(1.0, np.abs(y).max())
 
 
 @pytest.mark.parametrize("N,M,d", [(4096, 1 << 21, 8), (8192, 1 << 19, 16)])

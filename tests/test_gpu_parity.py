@@ -11,6 +11,7 @@ from bayesian_optimisation_amd import DeviceGP, PointSelector  # noqa: E402
 from bayesian_optimisation_amd import distributed as D  # noqa: E402
 from bayesian_optimisation_amd.synthetic import make_problem  # noqa: E402
 from oracle import gp_oracle as O  # noqa: E402
+import qei_ref  # noqa: E402  (tests/)
 
 # fp64 tolerances: vs the reference |dmu| <= 1e-9 max(1,|y|inf), |dsigma| <= 1e-8,
 # |dacq| <= 1e-8 max(1,|y|inf); vs the Cholesky-route oracle an order tighter.
@@ -436,6 +437,14 @@ def test_config5_shape_qei_n2048_subsampled():
     top2 = np.sort(ref)[-2:]
     if top2[1] - top2[0] > 1e-7:
         assert batches[_first_argmax(ref)] == r.best_idx
+    # the same rows with an incumbent that leaves none of them at 0 == 0 (tests/qei_ref.py): the oracle's median mean there
+    f_mid = qei_ref.incumbent(X, y, Xs[rows], ls, 0.5)
+    r = gp.score_qei(Xs, Z, f_mid, dense=True)
+    got = r.acq.cpu().numpy()
+    ref = O.qei_mc(X, y, Xs[rows], ls, Z, f_mid)
+    qei_ref.assert_informative(ref)
+    assert r.nan_count == 0 and r.best_idx == _first_argmax(got) and r.best_val == got.max()
+    assert np.max(np.abs(got[batches] - ref)) <= 1e-9 * max(1.0, np.abs(y).max())
 
 
 # ----------------------------------------------------------------------------------------------

@@ -10,6 +10,8 @@ bayesian_optimisation_amd/synthetic.py:
   n2048   N = 2048, M = 32768, dense LCB and EI: launches of eight column groups per candidate tile + split_finish_kernel
   n384    N = 384, M = 4096, dense LCB and EI: plain launches (one workgroup per candidate tile, own epilogue)
   qei     N = 2048, 4,096 candidates, score_qei(dense=True): the GRAM instantiation
+  qei_mid the same problem with f_best = median(y) (recorded later, from the library whose `qei` bits are the recorded ones):
+          with f_best = min(y) most of the 512 values of `qei` are exactly 0, whatever the Gram blocks were; here none is
   screens N = 2048, M = 32768: score_bound after factorise(order="fps") (prefix mode, ncb > 0, and the column-split
           launches S > 1 of the re-scoring) and score_i8c after prepare_i8() (column-split re-scoring): the result record
           and `last_screen`
@@ -77,6 +79,17 @@ def _case_qei():
     return {"qei": {"qei": r.acq.cpu().numpy(), "result": np.array([r.best_val, float(r.best_idx), float(r.nan_count)])}}
 
 
+def _case_qei_mid():
+    from bayesian_optimisation_amd import DeviceGP
+    from bayesian_optimisation_amd.synthetic import make_problem
+
+    X, y, Xs, ls = make_problem(2048, 4096, 8)
+    gp = DeviceGP().factorise(X, y, ls)
+    Z = np.random.default_rng(7).standard_normal((64, 8))
+    r = gp.score_qei(Xs, Z, f_best=float(np.median(y)), dense=True)
+    return {"qei_mid": {"qei": r.acq.cpu().numpy(), "result": np.array([r.best_val, float(r.best_idx), float(r.nan_count)])}}
+
+
 def _case_screens():
     from bayesian_optimisation_amd import DeviceGP
     from bayesian_optimisation_amd.synthetic import make_problem
@@ -95,8 +108,9 @@ def _case_screens():
     return {"screens": out}
 
 
-CASES = {"n2048": _case_n2048, "n384": _case_n384, "qei": _case_qei, "screens": _case_screens}
-FILES = {"n2048": ("n2048_mu_sigma", "n2048_lcb", "n2048_ei"), "n384": ("n384",), "qei": ("qei",), "screens": ("screens",)}
+CASES = {"n2048": _case_n2048, "n384": _case_n384, "qei": _case_qei, "qei_mid": _case_qei_mid, "screens": _case_screens}
+FILES = {"n2048": ("n2048_mu_sigma", "n2048_lcb", "n2048_ei"), "n384": ("n384",), "qei": ("qei",), "qei_mid": ("qei_mid",),
+         "screens": ("screens",)}
 
 
 def _same(a, b):
