@@ -21,6 +21,9 @@ CHUNK_GRANULE = 512
 MAX_D = 16          # every route
 MAX_D_ANY = 1024    # fp64 route (factorise, score): any d up to this, slow path beyond MAX_D
 I8_MAX_N = 16384
+BATCH_MAX_Q = 64
+FANTASY_BELIEVER = 0
+FANTASY_LIE = 1
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -85,6 +88,11 @@ SIGNATURES = {
     "gpbo_rescore_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "gpbo_rescore_f64": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _f64, _i32, _f64, _f64, _i64,
                                    _f64, _i64, _i64, _i64, _p, _p, _p, _i64, _p]),
+    "gpbo_batch_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "gpbo_select_batch_f64": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _f64, _f64, _f64, _i32, _f64, _f64, _i32,
+                                        _i32, _f64, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
+    "gpbo_select_batch_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _f64, _p, _i64, _i32, _f64, _f64, _i64, _i32, _i32,
+                                             _f64, _p, _p, _p, _p, _p, _p]),
     "gpbo_acq_workspace_bytes": (_i64, []),
     "gpbo_acq_argmax_f64": (C.c_int, [_p, _p, _i64, _i32, _f64, _f64, _i64, _p, _p, _p, _i64, _p]),
     "gpbo_nlml_grid_max_n": (C.c_int, []),

@@ -6,6 +6,7 @@
 // with ctypes + NumPy alone (no PyTorch, no device-memory handling on the caller's side): device buffers are
 // allocated, filled, used and released inside the call, on the library's own stream.
 //   gpbo_select_next_host_f64  = update_surrogate() after the length scales are chosen + the acquisition arg-max
+//   gpbo_select_batch_host_f64 = the same step, then q points for parallel evaluation (not in the reference; batch.hip)
 //   gpbo_nlml_grid_host_f64    = tune_kernel()'s likelihood grid
 //   gpbo_nlml_grad_host_f64    = the likelihood and its gradient in the log length scales (ard="gradient")
 #include "gpbo_internal.h"
@@ -203,6 +204,64 @@ extern "C" int gpbo_select_qei_host_f64(const double *X, const double *y, int64_
     if (rc != GPBO_OK) return rc;
     bool okc = A.d2h(result, dres, sizeof(gpbo_result));
     if (qei_out) okc = okc && A.d2h(qei_out, dq, sizeof(double) * (M / 8));
+    if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
+    return GPBO_OK;
+}
+
+// Greedy q-point batch on host arrays: factorisation + the dense plain pass + gpbo_select_batch_f64 (csrc/batch.hip).
+extern "C" int gpbo_select_batch_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls,
+                                          double jitter1, double jitter2, const double *Xs, int64_t M, int32_t acq_kind,
+                                          double p0, double p1, int64_t chunk, int32_t q, int32_t fantasy, double lie,
+                                          int64_t *idx_out, double *val_out, double *mu_out, double *sigma_out,
+                                          gpbo_result *result, int32_t *info) {
+    if (!X || !y || !ls || !Xs || !idx_out || !val_out || !result || !info) return GPBO_ERR_ARG;
+    if (N < 1 || M < 1 || d < 1 || d > GPBO_MAX_D || q < 1 || q > GPBO_BATCH_MAX_Q || q > M) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
+    if (fantasy != GPBO_FANTASY_BELIEVER && fantasy != GPBO_FANTASY_LIE) return GPBO_ERR_ARG;
+    if (fantasy == GPBO_FANTASY_LIE && !(lie - lie == 0.0)) return GPBO_ERR_ARG;   // not finite
+    if (chunk == 0) chunk = (int64_t)1 << 17;
+    if (!chunk_ok(chunk) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    chunk = clamp_chunk(chunk, M);
+    const int64_t Np = gpbo_padded_n(N);
+    const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
+    const int64_t wpost = gpbo_posterior_workspace_bytes(Np, chunk, M);
+    const int64_t wbatch = gpbo_batch_workspace_bytes(Np, M, q);
+    if (wpost < 0 || wbatch < 0) return GPBO_ERR_ARG;
+
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N), *dXs = A.alloc<double>(M * d);
+    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
+    int32_t *dinfo = A.alloc<int32_t>(1);
+    gpbo_result *dres = A.alloc<gpbo_result>(1);
+    char *dwork = A.alloc<char>((wfact > wpost ? wfact : wpost) + 256);   // the factorisation's workspace is dead by the pass
+    char *dbatch = A.alloc<char>(wbatch);                                  // (hipMalloc: 256-byte aligned)
+    double *dmu = A.alloc<double>(M), *dsig = A.alloc<double>(M), *dval = A.alloc<double>(q);
+    int64_t *didx = A.alloc<int64_t>(q);
+    if (!A.ok) return GPBO_ERR_WORKSPACE;
+    void *st = reinterpret_cast<void *>(A.stream);
+    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N) ||
+        !A.h2d(dXs, Xs, sizeof(double) * M * d))
+        return GPBO_ERR_LAUNCH;
+    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter1, jitter2, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    if (rc != GPBO_OK) return rc;
+    if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
+    if (*info != 0) {  // not positive definite: nothing to select from
+        *result = {0.0, -1, 0, 0};
+        for (int32_t j = 0; j < q; ++j) idx_out[j] = -1;
+        return GPBO_OK;
+    }
+    const double prior_var = (1.0 + jitter1) + jitter2;
+    rc = gpbo_posterior_acq_f64(dXs, M, dX, N, Np, d, ls, dU, dalpha, prior_var, acq_kind, p0, p1, 0.0, 0, chunk, dmu, dsig,
+                                nullptr, dres, dwork, wpost, nullptr, st);
+    if (rc != GPBO_OK) return rc;
+    rc = gpbo_select_batch_f64(dXs, M, dX, N, Np, d, ls, dU, dalpha, jitter1, jitter2, prior_var, acq_kind, p0, p1, q, fantasy,
+                               lie, dmu, dsig, 0, didx, dval, dres, dinfo, dbatch, wbatch, st);
+    if (rc != GPBO_OK) return rc;
+    bool okc = A.d2h(result, dres, sizeof(gpbo_result)) && A.d2h(info, dinfo, sizeof(int32_t)) &&
+               A.d2h(idx_out, didx, sizeof(int64_t) * q) && A.d2h(val_out, dval, sizeof(double) * q);
+    if (mu_out) okc = okc && A.d2h(mu_out, dmu, sizeof(double) * M);
+    if (sigma_out) okc = okc && A.d2h(sigma_out, dsig, sizeof(double) * M);
     if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
     return GPBO_OK;
 }

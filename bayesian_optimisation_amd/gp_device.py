@@ -64,6 +64,28 @@ class ScoreResult:
     acq: Optional[object] = None
 
 
+@dataclass
+class BatchResult:
+    """What DeviceGP.select_batch returns: the q members in selection order."""
+    indices: np.ndarray              # int64 [q], idx_offset + row of Xs; -1 from the first member that could not be chosen
+    values: np.ndarray               # float64 [q], the acquisition of each member when it was chosen
+    nan_count: int                   # > 0: the acquisition contains NaN (the reference raises IndexError)
+    info: int                        # 0, or the 1-based member whose fantasy pivot s_j was not positive / not finite
+    mu: Optional[object] = None      # torch fp64 device tensors [M]: the posterior the q-th member was chosen from
+    sigma: Optional[object] = None
+
+
+def fantasy_params(fantasy: str, lie: Optional[float]) -> tuple:
+    """(kind, lie) of the C ABI for a fantasy rule by name (include/gpbo.h: GPBO_FANTASY_*)."""
+    if fantasy == "believer":
+        return _lib.FANTASY_BELIEVER, 0.0
+    if fantasy == "liar":
+        if lie is None or not np.isfinite(float(lie)):
+            raise ValueError("fantasy='liar' needs a finite lie (the constant every fantasy observation takes)")
+        return _lib.FANTASY_LIE, float(lie)
+    raise ValueError(f"fantasy must be 'believer' or 'liar', got {fantasy!r}")
+
+
 class DeviceGP:
     """One BO step's surrogate on one GPU: factorise once, then score any number of candidates."""
 
@@ -83,7 +105,7 @@ class DeviceGP:
         self.K = self.U = self.alpha = None
         # workspaces, kept from call to call and only ever grown (_workspace)
         self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
-        self._work_qei = self._work_ard = None
+        self._work_qei = self._work_ard = self._work_batch = None
         self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
         self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
         self.U8, self._u8_valid = None, False                   # prepare_i8()
@@ -731,6 +753,66 @@ class DeviceGP:
         res, qei = self.score_qei_async(Xs, Z, f_best, xi, dense, batch_offset, prior_var)
         v, i, n = self.read_result(res)
         return ScoreResult(v, i, n, None, None, qei)
+
+    # -- greedy q-point batch by rank-one posterior updates (csrc/batch.hip) -------------------------
+    def select_batch_on_posterior(self, Xs, mu, sigma, q: int, acquisition: str = "lcb", explore: float = 4.0,
+                                  f_best: Optional[float] = None, xi: float = 0.0, fantasy: str = "believer",
+                                  lie: Optional[float] = None, idx_offset: int = 0,
+                                  prior_var: float = PRIOR_VAR) -> BatchResult:
+        """The batch from dense device mu / sigma [M] of THIS surrogate at the rows of Xs (score(dense=True) without
+        diag_add).  mu / sigma are updated in place: they leave as the posterior the q-th member was chosen from.
+        One read-back (synchronises).  This is the call for a posterior the caller already holds on the device
+        (PointSelector after update_surrogate()); select_batch() runs the plain pass first and then this.
+        prior_var must be the one mu / sigma were scored with.
+        EI keeps the f_best it is given for the whole batch: with fantasy="liar" and lie < f_best the later members are still
+        scored against f_best, not against the lie (the NumPy reference of the tests, tests/batch_ref.py, does the same).
+        A caller who wants the lie to count as the incumbent passes f_best = min(f_best, lie)."""
+        self._need_unrolled_d("select_batch()")
+        torch = self.torch
+        Xsd, M = self._candidates(Xs)
+        q = int(q)
+        if not 1 <= q <= min(_lib.BATCH_MAX_Q, M):
+            raise ValueError(f"q must be in [1, min({_lib.BATCH_MAX_Q}, M = {M})], got {q}")
+        kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
+        fkind, fl = fantasy_params(fantasy, lie)
+        for name, t in (("mu", mu), ("sigma", sigma)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.is_contiguous() and t.numel() == M
+                    and t.device == self.device):
+                raise ValueError(f"{name} must be a contiguous fp64 tensor of {M} values on {self.device}")
+        with torch.cuda.device(self.device):
+            need = int(self.lib.gpbo_batch_workspace_bytes(self.Np, M, q))
+            work = self._workspace("_work_batch", need)
+            # members, values, the result record and the info word in one buffer: one device-to-host copy
+            out = torch.zeros(2 * q + 5, dtype=torch.int64, device=self.device)
+            idx, val, res, info = out[:q], out[q: 2 * q], out[2 * q: 2 * q + 4], out[2 * q + 4:]
+            st = self.lib.gpbo_select_batch_f64(
+                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
+                self._ptr(self.U), self._ptr(self.alpha), self.jitter1, self.jitter2, float(prior_var), kind, p0, p1, q,
+                fkind, fl, self._ptr(mu), self._ptr(sigma), int(idx_offset), self._ptr(idx), self._ptr(val),
+                self._ptr(res), self._ptr(info), self._ptr(work), need, self._stream())
+            _lib.check(st, "gpbo_select_batch_f64")
+            h = out.cpu()   # synchronises: Xsd has been consumed
+        return BatchResult(indices=h[:q].numpy().copy(), values=h[q: 2 * q].view(torch.float64).numpy().copy(),
+                           nan_count=int(h[2 * q + 2]), info=int(h[2 * q + 4:].view(torch.int32)[0]), mu=mu, sigma=sigma)
+
+    def select_batch(self, Xs, q: int, acquisition: str = "lcb", explore: float = 4.0, f_best: Optional[float] = None,
+                     xi: float = 0.0, fantasy: str = "believer", lie: Optional[float] = None, idx_offset: int = 0,
+                     diag_add: float = 0.0) -> BatchResult:
+        """q candidates to evaluate in parallel, chosen greedily: the first is score()'s, each further one the arg-max
+        after conditioning the surrogate on a fantasy observation at the one before it - its current mean
+        (fantasy="believer": Kriging believer, GP-BUCB under LCB) or the constant `lie` (fantasy="liar") - with the members
+        chosen so far excluded.  Runs the dense plain pass, then gpbo_select_batch_f64: per member N kernel entries per
+        candidate instead of the N^2 of a pass after append().  The factorisation (U, alpha, N) is not touched.
+        d <= 16; not with the N == M shape quirk (diag_add)."""
+        if diag_add != 0.0:
+            raise ValueError("select_batch() does not support diag_add (the N == M shape quirk)")
+        self._need_unrolled_d("select_batch()")
+        Xsd, M = self._candidates(Xs)
+        fantasy_params(fantasy, lie)   # (refused before the N^2 pass is spent)
+        if not 1 <= int(q) <= min(_lib.BATCH_MAX_Q, M):
+            raise ValueError(f"q must be in [1, min({_lib.BATCH_MAX_Q}, M = {M})], got {q}")
+        _, mu, sigma, _ = self.score_async(Xsd, acquisition, explore, f_best, xi, dense=True, idx_offset=idx_offset)
+        return self.select_batch_on_posterior(Xsd, mu, sigma, q, acquisition, explore, f_best, xi, fantasy, lie, idx_offset)
 
     @property
     def status(self):

@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, acq_params
+from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, acq_params, fantasy_params
 from .point_selector import PointSelector
 
 
@@ -90,6 +90,35 @@ def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_
     best_val = float(np.frombuffer(res, dtype=np.float64, count=1)[0])
     return dict(best_val=best_val, best_idx=int(res[1]), nan_count=int(res[2]), info=int(info.value), mu=mu, sigma=sigma,
                 acq=acq, cov_meas=cov)
+
+
+def select_batch(X, y, ls, Xs, q: int, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
+                 fantasy: str = "believer", lie=None, dense: bool = False, chunk: int = 0, lib=None) -> dict:
+    """Greedy q-point batch on host arrays (gpbo_select_batch_host_f64).  Returns dict(indices, values, nan_count, info,
+    mu, sigma); mu / sigma (dense=True) are the posterior the q-th member was chosen from."""
+    lib = lib or _lib.load()
+    X, y, Xs = _f64(X), _f64(y).reshape(-1), _f64(Xs)
+    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
+    N, d = X.shape
+    M = Xs.shape[0]
+    if Xs.shape[1] != d or ls.size != d or y.size != N:
+        raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
+    q = int(q)
+    if d > _lib.MAX_D or not 1 <= q <= min(_lib.BATCH_MAX_Q, M):
+        raise ValueError(f"select_batch needs d <= {_lib.MAX_D} and q in [1, min({_lib.BATCH_MAX_Q}, M = {M})]")
+    kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
+    fkind, fl = fantasy_params(fantasy, lie)
+    idx, val = np.full(q, -1, dtype=np.int64), np.full(q, np.nan)
+    mu = np.empty(M) if dense else None
+    sigma = np.empty(M) if dense else None
+    res = (C.c_int64 * 4)()
+    info = C.c_int32(0)
+    _lib.note_hip_use()
+    st = lib.gpbo_select_batch_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M, kind,
+                                        p0, p1, int(chunk), q, fkind, fl, _ptr(idx), _ptr(val), _ptr(mu), _ptr(sigma),
+                                        C.cast(res, C.c_void_p), C.cast(C.pointer(info), C.c_void_p))
+    _lib.check(st, "gpbo_select_batch_host_f64")
+    return dict(indices=idx, values=val, nan_count=int(res[2]), info=int(info.value), mu=mu, sigma=sigma)
 
 
 class _GridOnly:
@@ -191,3 +220,17 @@ class PointSelectorHost(PointSelector):
             raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
         flat = int(res[1]) * 8 + np.arange(8)
         return np.stack(np.unravel_index(flat, fd), axis=1).astype(np.int64)
+
+    def select_batch(self, q, acquisition="lcb", explore=4, xi=0.0, fantasy="believer", lie=None):
+        """PointSelector.select_batch on the host-pointer route (gpbo_select_batch_host_f64: factorisation, plain pass and
+        selection in one call): the same (q, ndim) multi-indices, the same errors."""
+        if self._inputs is None:
+            raise RuntimeError("call update_surrogate() first")
+        X, y, ls, Xs = self._inputs
+        if Xs.shape == X.shape:
+            raise ValueError("select_batch() does not support candidates of the observations' shape (the N == M quirk)")
+        r = select_batch(X, y, ls, Xs, q, fantasy=fantasy, lie=lie, chunk=self._chunk, lib=self.lib,
+                         **self._batch_acq(acquisition, explore, xi))
+        if r["info"] != 0 and np.all(r["indices"] < 0):
+            raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)})")
+        return self._batch_indices(r["indices"], r["nan_count"])

@@ -24,7 +24,8 @@ Differences from the reference, all deliberate:
     The screens' tolerance is verified per call on every re-scored candidate and a strided sample, not proven for each
     candidate: the route that is exact by construction is `dense_outputs=False` (the prefix bound).
     Also extra: `expected_improvement(xi)`,
-    `q_expected_improvement()`, `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
+    `q_expected_improvement()`, `select_batch(q)` (q points for parallel evaluation: greedy Kriging believer / GP-BUCB /
+    constant liar), `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
     calls go through the exact prefix bound), `kernel_params` may be preset (then no
     ARD search runs), optional multi-GPU candidate sharding when torch.distributed is initialised,
     `incremental=True` / `state_path=...` (append new observations to the previous factorisation in O(N^2)
@@ -108,6 +109,7 @@ class PointSelector:
         self._dense = bool(dense_outputs)
         self._gp = None
         self._mu_dev = self._sigma_dev = None
+        self._xs_dev = None            # fp64 dense route: this rank's candidates on the device (select_batch reuses them)
         self._cached = None  # (kind, p0, p1) -> (acq ndarray, flat index)
         self._preset_kernel_params = False
         self._ls_cells = None          # explicit [G x d] cell list for d > 2 (set_length_scale_cells)
@@ -190,7 +192,7 @@ class PointSelector:
         lo, hi = D.shard_bounds(M, world, rank)
         if not self._dense:
             self.mean_func = self.cov_func = self.acq_func_eval = None
-            self._mu_dev = self._sigma_dev = None
+            self._mu_dev = self._sigma_dev = self._xs_dev = None
             self._cached = {}
             self._lo_hi = (lo, hi)
             self._select_only = (gp._dev(Xs[lo:hi]), diag_add)
@@ -201,12 +203,14 @@ class PointSelector:
             return
         if self._precision in ("fp32", "i8", "i8c"):   # screened variance product (fp32: BASELINE config 4's mode), fp64 decision
             score = {"fp32": gp.score_f32, "i8": gp.score_i8, "i8c": gp.score_i8c}[self._precision]
+            self._xs_dev = None
             self._screen_ctx = (gp._dev(Xs[lo:hi]), diag_add)
             res = score(self._screen_ctx[0], acquisition="lcb", explore=4.0, dense=True, idx_offset=lo, diag_add=diag_add)
             self.last_screen = dict(gp.last_screen, sigma_abs_tol=SCREEN_SIGMA_TOL[self._precision])
         else:
             self._screen_ctx = None
-            res = gp.score(Xs[lo:hi], acquisition="lcb", explore=4.0, dense=True, idx_offset=lo, diag_add=diag_add)
+            self._xs_dev = gp._dev(Xs[lo:hi])
+            res = gp.score(self._xs_dev, acquisition="lcb", explore=4.0, dense=True, idx_offset=lo, diag_add=diag_add)
         self._mu_dev, self._sigma_dev = res.mu, res.sigma
         best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
         # sharded: the three dense arrays are gathered on the device (one collective), then copied to the host once
@@ -475,6 +479,47 @@ class PointSelector:
         res.best_idx = best_idx
         flat = res.best_idx * 8 + np.arange(8)
         return np.stack(np.unravel_index(flat, fd), axis=1).astype(np.int64)
+
+    def _batch_acq(self, acquisition, explore, xi):
+        """Keyword arguments of the acquisition for a select_batch call (EI: f_best = min(measured_vals))."""
+        if acquisition == "lcb":
+            return dict(acquisition="lcb", explore=float(explore))
+        if acquisition == "ei":
+            return dict(acquisition="ei", f_best=float(np.min(np.asarray(self.measured_vals, dtype=np.float64))), xi=float(xi))
+        raise ValueError(f"unknown acquisition {acquisition!r}")
+
+    def _batch_indices(self, indices, nan_count):
+        fd = [int(v) for v in self.feature_domain]
+        if nan_count > 0 or np.any(indices < 0) or np.any(indices >= int(np.prod(fd))):
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+        return np.stack(np.unravel_index(indices, fd), axis=1).astype(np.int64)
+
+    def select_batch(self, q, acquisition="lcb", explore=4, xi=0.0, fantasy="believer", lie=None):
+        """Not in the reference (one point per iteration): q points to evaluate in parallel, chosen greedily on the surrogate
+        of the last update_surrogate().  The first is the acquisition's own arg-max; each further one is the arg-max after
+        conditioning on a fantasy observation at the one before it - the current mean there (fantasy="believer": Kriging
+        believer; under LCB this is GP-BUCB, only the variance shrinks) or the constant `lie` (fantasy="liar") - with the
+        members chosen so far excluded (DeviceGP.select_batch).  acquisition: "lcb" (explore) or "ei"
+        (f_best = min(measured_vals), xi).  Returns the (q, ndim) int64 multi-indices in selection order, the form
+        q_expected_improvement() returns; IndexError when the acquisition contains NaN.  mean_func / cov_func /
+        acq_func_eval stay as update_surrogate() set them (the selection works on copies of the device posterior).
+        Needs precision="fp64", dense_outputs=True and candidates of another shape than the observations (the N == M
+        quirk); candidates sharded over more than one rank are OUT OF SCOPE: NotImplementedError."""
+        if self._cached is None:
+            raise RuntimeError("call update_surrogate() first")
+        if self._precision != "fp64":
+            raise ValueError("select_batch() needs precision='fp64' (a screened sigma cannot seed the updates)")
+        if not self._dense:
+            raise ValueError("select_batch() needs dense_outputs=True (it starts from the dense posterior)")
+        if np.shape(self.predicted_pts) == np.shape(self.measured_pts):
+            raise ValueError("select_batch() does not support candidates of the observations' shape (the N == M quirk)")
+        if self._world()[0] > 1:
+            raise NotImplementedError("select_batch() with candidates sharded over several ranks is not implemented")
+        kw = self._batch_acq(acquisition, explore, xi)
+        # the candidates update_surrogate() left on the device: no second upload of M x d values
+        r = self._gp.select_batch_on_posterior(self._xs_dev, self._mu_dev.clone(), self._sigma_dev.clone(), int(q),
+                                               fantasy=fantasy, lie=lie, **kw)
+        return self._batch_indices(r.indices, r.nan_count)
 
     def expected_improvement(self, xi=0.0):
         """Not in the reference (docs/README.md:363-365 'future work'): EI for minimisation,

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -150,7 +150,9 @@ int gpbo_factorise_f64(const double *X, const double *y, int64_t N, int32_t d, c
  *   alpha [Np]: recomputed as U'(U'^T y');   Kp [Np x Np] or NULL: row and column N of K.
  * Needs N + 1 <= Np (Np a multiple of 64; the caller re-pads into larger buffers when the padding is used up:
  * identity on the new diagonal).  info (device int32): 0, or N+1 when the new pivot is not positive - U and alpha are
- * then unchanged (the surrogate of the N old observations stays valid) and the caller refactorises.  work: gpbo_append_workspace_bytes(Np). */
+ * then unchanged (the surrogate of the N old observations stays valid) and the caller refactorises.  work: gpbo_append_workspace_bytes(Np).
+ * (To FANTASISE observations - a batch of q points chosen one after the other - gpbo_select_batch_f64 below is the cheaper
+ * way: it updates a dense posterior in O(N) per candidate and member and leaves the factorisation alone.) */
 int64_t gpbo_append_workspace_bytes(int64_t Np);
 int gpbo_append_f64(double *X, double *y, int64_t N, int32_t d, const double *ls_host, double jitter1,
                     double jitter2, int64_t Np, const double *x_new, const double *y_new, double *Kp, double *U,
@@ -317,6 +319,44 @@ int64_t gpbo_acq_workspace_bytes(void);
 int gpbo_acq_argmax_f64(const double *mu, const double *sigma, int64_t M, int32_t acq_kind, double p0, double p1,
                         int64_t idx_offset, double *acq_out, gpbo_result *result, void *work, int64_t work_bytes,
                         void *stream);
+
+/* Greedy q-point batch selection by rank-one posterior updates (csrc/batch.hip; not in the reference, which
+ * selects one point per iteration).  Member 0 is the arg-max of the posterior as given; every further member is the arg-max
+ * after conditioning the GP on a FANTASY observation y_j at the member before it, members chosen so far excluded:
+ *   t_j(c) = k(c, x_j) - k_c . beta_j - sum_{i<j} t_i(c) t_i(x_j) / s_i,   beta_j = U (U^T k(X, x_j))
+ *   s_j = var_j(x_j) - prior_var + ((1 + jitter1) + jitter2);  var'(c) = var(c) - t_j(c)^2 / s_j;  mu'(c) = mu(c) + t_j(c) (y_j - mu(x_j)) / s_j
+ * N kernel entries per candidate and member instead of the N^2 of a variance pass; the factorisation (U, alpha, X) is only
+ * read.  GPBO_FANTASY_BELIEVER: y_j = the current mean at x_j (Kriging believer; GP-BUCB under LCB: only the variance
+ * shrinks); GPBO_FANTASY_LIE: y_j = lie (constant liar).
+ *   mu / sigma [M]: IN the dense outputs of gpbo_posterior_acq_f64 for the same Xs (diag_add = 0; the variance state is
+ *     sigma^2), OUT the posterior the q-th member was chosen from;
+ *   idx_out [q]: the members in selection order as idx_offset + row of Xs (the first equals the plain pass's arg-max);
+ *     val_out [q]: their acquisition values at selection time;
+ *   result: the record of the last member, nan_count = the largest NaN count of any step.  nan_count > 0 (the caller raises):
+ *     every LATER member is -1 (value NaN);  info (device int32): 0, or the 1-based member whose s_j was not positive or not
+ *     finite - that member's successors are -1 as well, mu / sigma stay as they were before the failed step;
+ *   alpha: the factorisation's (not read today: the mean arrives in mu; kept with the model's other arguments);
+ *   1 <= q <= GPBO_BATCH_MAX_Q, q <= M, d <= GPBO_MAX_D, Np = gpbo_padded_n(N); work: gpbo_batch_workspace_bytes(Np, M, q)
+ *   bytes (negative: invalid sizes), 256-byte aligned.  Enqueues only, never synchronises; no atomics in the sums: two
+ *   calls give the same bits.
+ * gpbo_select_batch_host_f64: factorisation + plain pass + selection on host arrays (conventions of
+ *   gpbo_select_next_host_f64; idx_out_host / val_out_host [q], mu_out_host / sigma_out_host optional [M]; info_host: the
+ *   failing pivot of the factorisation - then every member is -1 - or the failing member as above). */
+#define GPBO_BATCH_MAX_Q 64
+#define GPBO_FANTASY_BELIEVER 0 /* y_j = the current mean at x_j */
+#define GPBO_FANTASY_LIE 1      /* y_j = lie */
+int64_t gpbo_batch_workspace_bytes(int64_t Np, int64_t M, int32_t q);
+int gpbo_select_batch_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
+                          const double *ls_host, const double *U, const double *alpha, double jitter1, double jitter2,
+                          double prior_var, int32_t acq_kind, double p0, double p1, int32_t q, int32_t fantasy, double lie,
+                          double *mu /* in/out [M] */, double *sigma /* in/out [M] */, int64_t idx_offset,
+                          int64_t *idx_out /* [q] */, double *val_out /* [q] */, gpbo_result *result, int32_t *info,
+                          void *work, int64_t work_bytes, void *stream);
+int gpbo_select_batch_host_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
+                               double jitter1, double jitter2, const double *Xs_host, int64_t M, int32_t acq_kind,
+                               double p0, double p1, int64_t chunk, int32_t q, int32_t fantasy, double lie,
+                               int64_t *idx_out_host, double *val_out_host, double *mu_out_host, double *sigma_out_host,
+                               gpbo_result *result_host, int32_t *info_host);
 
 /* ---- Host-pointer entry points: the reference's call sequence on NumPy-style arrays, no device handling by the
  * caller (device buffers and a private stream live inside the call).  What a ctypes stub in the reference binds.

@@ -131,6 +131,17 @@ int main() {
     EXPECT(post(128, 512, 7, (int64_t)1 << 40) == GPBO_ERR_ARG);
     EXPECT(post(128, (int64_t)1 << 25, 0, (int64_t)1 << 40) == GPBO_ERR_ARG);
     EXPECT(post(128, 512, 0, 8) == GPBO_ERR_WORKSPACE);
+    // batch selection (tests/test_batch_abi_cpu.py): q range, q > M, d, fantasy rule, a NaN lie, the workspace one byte short
+    auto batch = [&](int64_t M, int32_t d, int32_t q, int32_t fantasy, double lie, int64_t wbytes) {
+        return gpbo_select_batch_f64(pd, M, pd, 100, 128, d, ls, pd, pd, 1e-4, 1e-6, 1.000101, 0, 4.0, 0.0, q, fantasy, lie, pd, pd,
+                                     0, reinterpret_cast<int64_t *>(p), pd, reinterpret_cast<gpbo_result *>(p), pi, p, wbytes, nullptr);
+    };
+    const int64_t wb = gpbo_batch_workspace_bytes(128, 1000, 8);
+    EXPECT(wb > 0 && gpbo_batch_workspace_bytes(128, 1000, 65) == -1 && gpbo_batch_workspace_bytes(100, 1000, 8) == -1);
+    EXPECT(batch(1000, 2, 0, 0, 0.0, wb) == GPBO_ERR_ARG && batch(1000, 2, 65, 0, 0.0, wb) == GPBO_ERR_ARG);
+    EXPECT(batch(7, 2, 8, 0, 0.0, (int64_t)1 << 40) == GPBO_ERR_ARG && batch(1000, 17, 8, 0, 0.0, wb) == GPBO_ERR_ARG);
+    EXPECT(batch(1000, 2, 8, 2, 0.0, wb) == GPBO_ERR_ARG && batch(1000, 2, 8, 1, __builtin_nan(""), wb) == GPBO_ERR_ARG);
+    EXPECT(batch(1000, 2, 8, 0, 0.0, wb - 1) == GPBO_ERR_WORKSPACE);
     EXPECT(gpbo_potrf_f64(pd, 100, pd, pi, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_trtri_f64(pd, pd, 100, pd, pd, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_nlml_grid_f64(pd, pd, 177, 2, pd, 4, 1e-4, reinterpret_cast<float *>(p), nullptr) == GPBO_ERR_ARG);
