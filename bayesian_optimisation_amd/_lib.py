@@ -24,6 +24,7 @@ I8_MAX_N = 16384
 BATCH_MAX_Q = 64
 FANTASY_BELIEVER = 0
 FANTASY_LIE = 1
+REFINE_MAX_P = 4096
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -93,6 +94,14 @@ SIGNATURES = {
                                         _i32, _f64, _p, _p, _i64, _p, _p, _p, _p, _p, _i64, _p]),
     "gpbo_select_batch_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _f64, _p, _i64, _i32, _f64, _f64, _i64, _i32, _i32,
                                              _f64, _p, _p, _p, _p, _p, _p]),
+    "gpbo_posterior_grad_workspace_bytes": (_i64, [_i64, _i64]),
+    "gpbo_posterior_grad_f64": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _f64, _i32, _f64, _f64, _p, _p, _p, _p, _p,
+                                          _p, _p, _i64, _p]),
+    "gpbo_refine_workspace_bytes": (_i64, [_i64, _i64]),
+    "gpbo_refine_f64": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _f64, _i32, _f64, _f64, _i32, _f64, _p, _p,
+                                  _p, _p, _p, _p, _i64, _p]),
+    "gpbo_refine_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _f64, _p, _i64, _p, _p, _i32, _f64, _f64, _i32, _f64, _p, _p,
+                                       _p, _p, _p, _p]),
     "gpbo_acq_workspace_bytes": (_i64, []),
     "gpbo_acq_argmax_f64": (C.c_int, [_p, _p, _i64, _i32, _f64, _f64, _i64, _p, _p, _p, _i64, _p]),
     "gpbo_nlml_grid_max_n": (C.c_int, []),

@@ -7,6 +7,7 @@
 // allocated, filled, used and released inside the call, on the library's own stream.
 //   gpbo_select_next_host_f64  = update_surrogate() after the length scales are chosen + the acquisition arg-max
 //   gpbo_select_batch_host_f64 = the same step, then q points for parallel evaluation (not in the reference; batch.hip)
+//   gpbo_refine_host_f64       = the factorisation, then gradient refinement of given starts off the grid (refine.hip)
 //   gpbo_nlml_grid_host_f64    = tune_kernel()'s likelihood grid
 //   gpbo_nlml_grad_host_f64    = the likelihood and its gradient in the log length scales (ard="gradient")
 #include "gpbo_internal.h"
@@ -262,6 +263,56 @@ extern "C" int gpbo_select_batch_host_f64(const double *X, const double *y, int6
                A.d2h(idx_out, didx, sizeof(int64_t) * q) && A.d2h(val_out, dval, sizeof(double) * q);
     if (mu_out) okc = okc && A.d2h(mu_out, dmu, sizeof(double) * M);
     if (sigma_out) okc = okc && A.d2h(sigma_out, dsig, sizeof(double) * M);
+    if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
+    return GPBO_OK;
+}
+
+// Off-grid refinement on host arrays: factorisation + gpbo_refine_f64 (csrc/refine.hip).
+extern "C" int gpbo_refine_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls, double jitter1,
+                                    double jitter2, double *Xq, int64_t P, const double *lower, const double *upper,
+                                    int32_t acq_kind, double p0, double p1, int32_t iters, double step0, double *acq_out,
+                                    double *acq0_out, int32_t *accepted_out, double *pg_out, gpbo_result *result,
+                                    int32_t *info) {
+    if (!X || !y || !ls || !Xq || !lower || !upper || !result || !info) return GPBO_ERR_ARG;
+    if (N < 1 || d < 1 || d > GPBO_MAX_D || P < 1 || P > GPBO_REFINE_MAX_P) return GPBO_ERR_ARG;
+    if (!acq_kind_ok(acq_kind) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    if (iters < 0 || iters > 1000 || !(step0 > 0.0) || !(step0 - step0 == 0.0)) return GPBO_ERR_ARG;
+    for (int k = 0; k < d; ++k)
+        if (!(lower[k] - lower[k] == 0.0) || !(upper[k] - upper[k] == 0.0) || lower[k] > upper[k]) return GPBO_ERR_ARG;
+    const int64_t Np = gpbo_padded_n(N);
+    const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
+    const int64_t wref = gpbo_refine_workspace_bytes(Np, P);
+    if (wref < 0) return GPBO_ERR_ARG;
+
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N), *dXq = A.alloc<double>(P * d);
+    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
+    int32_t *dinfo = A.alloc<int32_t>(1);
+    gpbo_result *dres = A.alloc<gpbo_result>(1);
+    char *dwork = A.alloc<char>(wfact > wref ? wfact : wref);   // the factorisation's workspace is dead by the refinement
+    double *dacq = A.alloc<double>(P), *dacq0 = A.alloc<double>(P), *dpg = A.alloc<double>(P);
+    int32_t *dacc = A.alloc<int32_t>(P);
+    if (!A.ok) return GPBO_ERR_WORKSPACE;
+    void *st = reinterpret_cast<void *>(A.stream);
+    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N) || !A.h2d(dXq, Xq, sizeof(double) * P * d))
+        return GPBO_ERR_LAUNCH;
+    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter1, jitter2, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    if (rc != GPBO_OK) return rc;
+    if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
+    if (*info != 0) {  // not positive definite: nothing to refine on
+        *result = {0.0, -1, 0, 0};
+        return GPBO_OK;
+    }
+    const double prior_var = (1.0 + jitter1) + jitter2;
+    rc = gpbo_refine_f64(dXq, P, lower, upper, dX, N, Np, d, ls, dU, dalpha, prior_var, acq_kind, p0, p1, iters, step0, dacq,
+                         dacq0, dacc, dpg, dres, dwork, wref, st);
+    if (rc != GPBO_OK) return rc;
+    bool okc = A.d2h(result, dres, sizeof(gpbo_result)) && A.d2h(Xq, dXq, sizeof(double) * P * d);
+    if (acq_out) okc = okc && A.d2h(acq_out, dacq, sizeof(double) * P);
+    if (acq0_out) okc = okc && A.d2h(acq0_out, dacq0, sizeof(double) * P);
+    if (accepted_out) okc = okc && A.d2h(accepted_out, dacc, sizeof(int32_t) * P);
+    if (pg_out) okc = okc && A.d2h(pg_out, dpg, sizeof(double) * P);
     if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
     return GPBO_OK;
 }

@@ -75,6 +75,55 @@ class BatchResult:
     sigma: Optional[object] = None
 
 
+@dataclass
+class GradResult:
+    """What DeviceGP.posterior_grad returns: torch fp64 device tensors, values [P] and gradients in x [P x d]."""
+    mu: object
+    sigma: object
+    acq: object
+    dmu: object
+    dsigma: object
+    dacq: object
+
+
+@dataclass
+class RefineResult:
+    """What DeviceGP.refine returns.  x / acq / acq0 / accepted / pg are device tensors, one row per start."""
+    x: object                        # fp64 [P x d]: the refined points (inside the box)
+    acq: object                      # fp64 [P]: the acquisition there
+    acq0: object                     # fp64 [P]: the acquisition at the clipped start
+    accepted: object                 # int32 [P]: accepted steps
+    pg: object                       # fp64 [P]: projected-gradient norm max_k |x_k - clip(x_k + g_k ls_k^2)| / ls_k
+    best: int                        # the LOWEST start with the largest final acquisition (-1: none)
+    best_val: float
+    nan_count: int                   # starts whose acq0 is NaN (they never move; the classes raise IndexError)
+    grid_idx: Optional[int] = None   # select_refined(): score()'s arg-max over the candidates and its value
+    grid_val: Optional[float] = None
+
+
+def refine_params(P: int, d: int, iters: int, step0: float) -> tuple:
+    """(iters, step0) as the C ABI takes them; refuses what gpbo_refine_f64 refuses (include/gpbo.h)."""
+    if not 1 <= int(P) <= _lib.REFINE_MAX_P:
+        raise ValueError(f"the number of points must be in [1, {_lib.REFINE_MAX_P}], got {P}")
+    if not 1 <= int(d) <= _lib.MAX_D:
+        raise ValueError(f"refinement needs 1 <= d <= {_lib.MAX_D}, got d = {d}")
+    if int(iters) != iters or not 0 <= int(iters) <= 1000:
+        raise ValueError(f"iters must be an integer in [0, 1000], got {iters!r}")
+    step0 = float(step0)
+    if not (np.isfinite(step0) and step0 > 0.0):
+        raise ValueError(f"step0 must be positive and finite, got {step0!r}")
+    return int(iters), step0
+
+
+def refine_box(lower, upper, d: int) -> tuple:
+    """(lower, upper) as contiguous fp64 host arrays of d finite values with lower <= upper (scalars are broadcast)."""
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64).reshape(-1), (d,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64).reshape(-1), (d,)))
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo <= hi)):
+        raise ValueError("the box needs finite bounds with lower <= upper in every coordinate")
+    return lo, hi
+
+
 def fantasy_params(fantasy: str, lie: Optional[float]) -> tuple:
     """(kind, lie) of the C ABI for a fantasy rule by name (include/gpbo.h: GPBO_FANTASY_*)."""
     if fantasy == "believer":
@@ -105,7 +154,7 @@ class DeviceGP:
         self.K = self.U = self.alpha = None
         # workspaces, kept from call to call and only ever grown (_workspace)
         self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
-        self._work_qei = self._work_ard = self._work_batch = None
+        self._work_qei = self._work_ard = self._work_batch = self._work_refine = None
         self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
         self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
         self.U8, self._u8_valid = None, False                   # prepare_i8()
@@ -813,6 +862,94 @@ class DeviceGP:
             raise ValueError(f"q must be in [1, min({_lib.BATCH_MAX_Q}, M = {M})], got {q}")
         _, mu, sigma, _ = self.score_async(Xsd, acquisition, explore, f_best, xi, dense=True, idx_offset=idx_offset)
         return self.select_batch_on_posterior(Xsd, mu, sigma, q, acquisition, explore, f_best, xi, fantasy, lie, idx_offset)
+
+    # -- acquisition gradients and off-grid refinement (csrc/refine.hip) -------------------------------
+    def _points(self, Xq, what: str):
+        """(Xq as a contiguous fp64 device tensor [P x d], P) for the query-point calls."""
+        Xd = self._dev(Xq)
+        if Xd.dim() == 1:
+            Xd = Xd.reshape(1, -1)
+        if Xd.dim() != 2 or int(Xd.shape[1]) != self.d:
+            raise ValueError(f"{what} must be (P, d) with the same d as X")
+        return Xd, int(Xd.shape[0])
+
+    def posterior_grad(self, Xq, acquisition: str = "lcb", explore: float = 4.0, f_best: Optional[float] = None,
+                       xi: float = 0.0, prior_var: float = PRIOR_VAR) -> GradResult:
+        """Posterior mean, standard deviation and acquisition at the rows of Xq [P x d] (P <= 4096) with their gradients in
+        x (gpbo_posterior_grad_f64).  Query points, not candidates: the N == M quirk (diag_add) does not apply.  Works on
+        the factorisation as it is (any order=, appended rows included).  Enqueues only; device tensors come back."""
+        self._need_unrolled_d("posterior_grad()")
+        torch = self.torch
+        Xd, P = self._points(Xq, "Xq")
+        refine_params(P, self.d, 0, 1.0)
+        kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
+        with torch.cuda.device(self.device):
+            need = int(self.lib.gpbo_posterior_grad_workspace_bytes(self.Np, P))
+            work = self._workspace("_work_refine", need)
+            vals = torch.empty((3, P), dtype=torch.float64, device=self.device)
+            grads = torch.empty((3, P, self.d), dtype=torch.float64, device=self.device)
+            st = self.lib.gpbo_posterior_grad_f64(
+                self._ptr(Xd), P, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
+                self._ptr(self.U), self._ptr(self.alpha), float(prior_var), kind, p0, p1, self._ptr(vals[0]),
+                self._ptr(vals[1]), self._ptr(vals[2]), self._ptr(grads[0]), self._ptr(grads[1]), self._ptr(grads[2]),
+                self._ptr(work), need, self._stream())
+            _lib.check(st, "gpbo_posterior_grad_f64")
+        self._keep = Xd
+        return GradResult(vals[0], vals[1], vals[2], grads[0], grads[1], grads[2])
+
+    def refine(self, starts, lower, upper, acquisition: str = "lcb", explore: float = 4.0, f_best: Optional[float] = None,
+               xi: float = 0.0, iters: int = 30, step0: float = 0.1, prior_var: float = PRIOR_VAR) -> RefineResult:
+        """Projected gradient ascent of the acquisition from every row of starts [P x d] (P <= 4096) inside the box
+        [lower, upper] (gpbo_refine_f64; the rule is stated in include/gpbo.h): each start on its own, step doubled after an
+        accepted trial and halved after a rejected one, iters trials.  All iters + 1 evaluations are enqueued at once;
+        one read-back of the result record (synchronises).  Two calls give the same bits."""
+        self._need_unrolled_d("refine()")
+        torch = self.torch
+        Xd, P = self._points(starts, "starts")
+        iters, step0 = refine_params(P, self.d, iters, step0)
+        lo, hi = refine_box(lower, upper, self.d)
+        kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
+        with torch.cuda.device(self.device):
+            x = Xd.clone()   # in: the starts, out: the refined points; the caller's tensor is never written to
+            need = int(self.lib.gpbo_refine_workspace_bytes(self.Np, P))
+            work = self._workspace("_work_refine", need)
+            vals = torch.empty((3, P), dtype=torch.float64, device=self.device)
+            accepted = torch.empty(P, dtype=torch.int32, device=self.device)
+            res = torch.zeros(4, dtype=torch.int64, device=self.device)
+            st = self.lib.gpbo_refine_f64(
+                self._ptr(x), P, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), self._ptr(self.X), self.N,
+                self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p), self._ptr(self.U), self._ptr(self.alpha),
+                float(prior_var), kind, p0, p1, iters, step0, self._ptr(vals[0]), self._ptr(vals[1]), self._ptr(accepted),
+                self._ptr(vals[2]), self._ptr(res), self._ptr(work), need, self._stream())
+            _lib.check(st, "gpbo_refine_f64")
+            v, i, n = self.read_result(res)   # synchronises
+        return RefineResult(x=x, acq=vals[0], acq0=vals[1], accepted=accepted, pg=vals[2], best=i, best_val=v, nan_count=n)
+
+    def select_refined(self, Xs, n_starts: int = 64, lower=None, upper=None, acquisition: str = "lcb", explore: float = 4.0,
+                       f_best: Optional[float] = None, xi: float = 0.0, iters: int = 30, step0: float = 0.1) -> RefineResult:
+        """The dense score() of the candidates Xs, then refine() from the n_starts candidates with the largest acquisition
+        (stable descending sort: ties keep the lower index first).  lower / upper omitted: the per-feature minimum / maximum
+        of Xs.  Returns refine()'s result with grid_idx / grid_val = score()'s arg-max and its value."""
+        self._need_unrolled_d("select_refined()")
+        torch = self.torch
+        Xsd, M = self._candidates(Xs)
+        n_starts = int(n_starts)
+        if not 1 <= n_starts <= min(_lib.REFINE_MAX_P, M):
+            raise ValueError(f"n_starts must be in [1, min({_lib.REFINE_MAX_P}, M = {M})], got {n_starts}")
+        refine_params(n_starts, self.d, iters, step0)
+        if (lower is None) != (upper is None):
+            raise ValueError("give both lower and upper, or neither")
+        s = self.score(Xsd, acquisition=acquisition, explore=explore, f_best=f_best, xi=xi, dense=True)
+        if s.nan_count > 0:
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+        with torch.cuda.device(self.device):
+            order = torch.sort(s.acq, descending=True, stable=True).indices[:n_starts]   # plumbing
+            starts = Xsd[order].contiguous()
+            if lower is None:
+                lower, upper = Xsd.min(dim=0).values.cpu().numpy(), Xsd.max(dim=0).values.cpu().numpy()
+        r = self.refine(starts, lower, upper, acquisition, explore, f_best, xi, iters, step0)
+        r.grid_idx, r.grid_val = s.best_idx, s.best_val
+        return r
 
     @property
     def status(self):

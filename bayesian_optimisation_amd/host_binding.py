@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, acq_params, fantasy_params
+from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, acq_params, fantasy_params, refine_box, refine_params
 from .point_selector import PointSelector
 
 
@@ -119,6 +119,34 @@ def select_batch(X, y, ls, Xs, q: int, acquisition: str = "lcb", explore: float 
                                         C.cast(res, C.c_void_p), C.cast(C.pointer(info), C.c_void_p))
     _lib.check(st, "gpbo_select_batch_host_f64")
     return dict(indices=idx, values=val, nan_count=int(res[2]), info=int(info.value), mu=mu, sigma=sigma)
+
+
+def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
+           iters: int = 30, step0: float = 0.1, lib=None) -> dict:
+    """Off-grid refinement on host arrays (gpbo_refine_host_f64: factorisation and refinement in one call).  Returns
+    dict(x [P x d], acq, acq0, accepted, pg, best, best_val, nan_count, info)."""
+    lib = lib or _lib.load()
+    X, y = _f64(X), _f64(y).reshape(-1)
+    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
+    N, d = X.shape
+    x = np.array(np.asarray(starts, dtype=np.float64).reshape(-1, d), dtype=np.float64, order="C")   # a copy: in / out
+    P = x.shape[0]
+    if ls.size != d or y.size != N:
+        raise ValueError("shapes: X (N, d), y (N,), ls (d,), starts (P, d)")
+    iters, step0 = refine_params(P, d, iters, step0)
+    lo, hi = refine_box(lower, upper, d)
+    kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
+    acq, acq0, pg, accepted = np.empty(P), np.empty(P), np.empty(P), np.empty(P, dtype=np.int32)
+    res = (C.c_int64 * 4)()
+    info = C.c_int32(0)
+    _lib.note_hip_use()
+    st = lib.gpbo_refine_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(x), P, _ptr(lo), _ptr(hi),
+                                  kind, p0, p1, iters, step0, _ptr(acq), _ptr(acq0), _ptr(accepted), _ptr(pg),
+                                  C.cast(res, C.c_void_p), C.cast(C.pointer(info), C.c_void_p))
+    _lib.check(st, "gpbo_refine_host_f64")
+    best_val = float(np.frombuffer(res, dtype=np.float64, count=1)[0])
+    return dict(x=x, acq=acq, acq0=acq0, accepted=accepted, pg=pg, best=int(res[1]), best_val=best_val, nan_count=int(res[2]),
+                info=int(info.value))
 
 
 class _GridOnly:
@@ -234,3 +262,17 @@ class PointSelectorHost(PointSelector):
         if r["info"] != 0 and np.all(r["indices"] < 0):
             raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)})")
         return self._batch_indices(r["indices"], r["nan_count"])
+
+    def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
+        """PointSelector.refine_next on the host-pointer route (gpbo_refine_host_f64): the same d coordinates, the same
+        errors."""
+        if self._inputs is None:
+            raise RuntimeError("call update_surrogate() first")
+        kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
+        X, y, ls, _ = self._inputs
+        r = refine(X, y, ls, starts, lo, hi, iters=int(iters), lib=self.lib, **kw)
+        if r["info"] != 0:
+            raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)})")
+        if r["nan_count"] > 0 or r["best"] < 0:
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+        return r["x"][r["best"]].copy()

@@ -25,7 +25,7 @@ Differences from the reference, all deliberate:
     candidate: the route that is exact by construction is `dense_outputs=False` (the prefix bound).
     Also extra: `expected_improvement(xi)`,
     `q_expected_improvement()`, `select_batch(q)` (q points for parallel evaluation: greedy Kriging believer / GP-BUCB /
-    constant liar), `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
+    constant liar), `refine_next()` (the next point off the grid: the best candidates polished by acquisition gradients), `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
     calls go through the exact prefix bound), `kernel_params` may be preset (then no
     ARD search runs), optional multi-GPU candidate sharding when torch.distributed is initialised,
     `incremental=True` / `state_path=...` (append new observations to the previous factorisation in O(N^2)
@@ -520,6 +520,49 @@ class PointSelector:
         r = self._gp.select_batch_on_posterior(self._xs_dev, self._mu_dev.clone(), self._sigma_dev.clone(), int(q),
                                                fantasy=fantasy, lie=lie, **kw)
         return self._batch_indices(r.indices, r.nan_count)
+
+    def _refine_inputs(self, n_starts, iters, acquisition, explore, xi):
+        """(acquisition keywords, starts [n x d], lower, upper) of a refine_next call: the n_starts candidates with the
+        largest value of the class's own dense acquisition (stable order: ties keep the lower flat index first) and the
+        bounding box of predicted_pts.  acq_func_eval and last_screen are left as they were.  Under a screened precision
+        the ranking is the one the class's own acquisition methods use there: fp64 values on the screen's survivors (the
+        top of the order), the screen's values below them; the refinement itself is always fp64."""
+        from .gp_device import refine_params
+
+        if self._cached is None:
+            raise RuntimeError("call update_surrogate() first")
+        if not self._dense:
+            raise ValueError("refine_next() needs dense_outputs=True (its starts come from the dense acquisition)")
+        kw = self._batch_acq(acquisition, explore, xi)
+        Xs = np.asarray(self.predicted_pts, dtype=np.float64)
+        Xs = Xs.reshape(len(Xs), -1)
+        n_starts = int(n_starts)
+        if not 1 <= n_starts <= len(Xs):
+            raise ValueError(f"n_starts must be in [1, M = {len(Xs)}], got {n_starts}")
+        refine_params(n_starts, Xs.shape[1], iters, 0.1)
+        key = ("lcb", kw["explore"], 0.0) if acquisition == "lcb" else ("ei", kw["f_best"], kw["xi"])
+        keep = self.acq_func_eval, self.last_screen   # what _finish sets (last_screen: an uncached key under a screen)
+        try:
+            self._finish(key, acquisition, **{k: v for k, v in kw.items() if k != "acquisition"})   # IndexError on NaN
+        finally:
+            self.acq_func_eval, self.last_screen = keep
+        acq = np.asarray(self._cached[key][0], dtype=np.float64).reshape(-1)
+        order = np.argsort(-acq, kind="stable")[:n_starts]
+        return kw, np.ascontiguousarray(Xs[order]), Xs.min(axis=0), Xs.max(axis=0)
+
+    def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
+        """Not in the reference (whose lower_confidence_bound() answers with a grid index): the next point OFF the grid, as
+        a float64 array of d coordinates.  The n_starts best candidates of the dense acquisition are refined by projected
+        gradient ascent inside the bounding box of predicted_pts (DeviceGP.refine) and the best refined point
+        is returned; call after update_surrogate().  acquisition: "lcb" (explore) or "ei" (f_best = min(measured_vals),
+        xi).  mean_func / cov_func / acq_func_eval and every other attribute stay as they are; IndexError when the
+        acquisition contains NaN.  With sharded candidates every rank refines the same global starts on the replicated
+        factorisation (same bits on every rank, no collective)."""
+        kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
+        r = self._gp.refine(starts, lo, hi, iters=int(iters), **kw)
+        if r.nan_count > 0 or r.best < 0:
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+        return r.x[r.best].cpu().numpy().astype(np.float64)
 
     def expected_improvement(self, xi=0.0):
         """Not in the reference (docs/README.md:363-365 'future work'): EI for minimisation,

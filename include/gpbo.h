@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -357,6 +357,49 @@ int gpbo_select_batch_host_f64(const double *X_host, const double *y_host, int64
                                double p0, double p1, int64_t chunk, int32_t q, int32_t fantasy, double lie,
                                int64_t *idx_out_host, double *val_out_host, double *mu_out_host, double *sigma_out_host,
                                gpbo_result *result_host, int32_t *info_host);
+
+/* Acquisition gradients and off-grid refinement of selected points (csrc/refine.hip; not in the reference, which
+ * answers with one of the candidates it was given).  For a query point x, k_n = k(x, X_n), g_nk = (X_nk - x_k) / ls_k^2:
+ *   mu = sum_n k_n alpha_n, dmu_k = sum_n k_n alpha_n g_nk;  v = U^T k, var = prior_var - |v|^2, w = U v,
+ *   dvar_k = -2 sum_n k_n w_n g_nk;  sigma = sqrt(|var|), dsigma_k = sign(var) dvar_k / (2 sigma) (0 when sigma == 0);
+ *   LCB: dacq = p0 dsigma - dmu;  EI: dacq = -Phi(z) dmu + phi(z) dsigma (sigma == 0: -dmu if imp > 0, else 0).
+ * gpbo_posterior_grad_f64: value and gradient at the P rows of Xq [P x d] (not candidates: no diag_add); mu_out / sigma_out /
+ *   acq_out [P] and dmu_out / dsigma_out / dacq_out [P x d], each optional.  A row with a non-finite coordinate gives NaN
+ *   in every output.  Four launches: K(Xq, X) point-major, the two dense products with U on the matrix cores, the sums.
+ * gpbo_refine_f64: projected gradient ascent of the acquisition inside the box [lower, upper], every start on its own:
+ *   x <- clip(start), (f, g) there, acq0 = f, t <- step0 / max_k(|g_k| ls_k) (frozen when that is 0 or not finite);
+ *   iters times: x' = clip(x + t g ls^2); accepted iff x' != x, f' finite and f' >= f + 1e-4 sum_k g_k (x'_k - x_k) - then
+ *   (x, f, g) <- (x', f', g'), t <- 2 t - else t <- t / 2.
+ *   Xq [P x d]: IN the starts, OUT the refined points;  acq_out / acq0_out / pg_out (double) and accepted_out (int32), [P],
+ *   each optional: the final value, the value at the clipped start, the projected-gradient norm
+ *   max_k |x_k - clip(x_k + g_k ls_k^2)| / ls_k, the number of accepted steps;  result: the largest final value, the LOWEST
+ *   start attaining it, nan_count = starts whose acq0 is NaN (such a start never moves and reports NaN; the caller raises).
+ *   All iters + 1 evaluations are enqueued without a host round trip; no atomics, no random numbers: two calls give the
+ *   same bits.
+ * 1 <= P <= GPBO_REFINE_MAX_P, 1 <= d <= GPBO_MAX_D, Np = gpbo_padded_n(N), ls > 0, finite lower <= upper, 0 <= iters <= 1000,
+ *   finite step0 > 0, U 16-byte aligned (GPBO_ERR_ARG otherwise, before any launch);  work: gpbo_posterior_grad_workspace_bytes(Np, P) /
+ *   gpbo_refine_workspace_bytes(Np, P) bytes (negative: invalid sizes), 256-byte aligned (GPBO_ERR_WORKSPACE).
+ * gpbo_refine_host_f64: factorisation + refinement on host arrays (conventions of gpbo_select_batch_host_f64: X, y, N, d,
+ *   ls, jitter1, jitter2; prior_var = (1 + jitter1) + jitter2);  Xq_host [P x d] in / out, the four optional [P] host
+ *   outputs;  info_host: 0, or the failing pivot of the factorisation - then nothing is refined and best_idx = -1. */
+#define GPBO_REFINE_MAX_P 4096
+int64_t gpbo_posterior_grad_workspace_bytes(int64_t Np, int64_t P);
+int gpbo_posterior_grad_f64(const double *Xq, int64_t P, const double *X, int64_t N, int64_t Np, int32_t d,
+                            const double *ls_host, const double *U, const double *alpha, double prior_var, int32_t acq_kind,
+                            double p0, double p1, double *mu_out, double *sigma_out, double *acq_out /* [P] */,
+                            double *dmu_out, double *dsigma_out, double *dacq_out /* [P x d] */, void *work,
+                            int64_t work_bytes, void *stream);
+int64_t gpbo_refine_workspace_bytes(int64_t Np, int64_t P);
+int gpbo_refine_f64(double *Xq /* in: starts, out: refined points [P x d] */, int64_t P, const double *lower_host,
+                    const double *upper_host, const double *X, int64_t N, int64_t Np, int32_t d, const double *ls_host,
+                    const double *U, const double *alpha, double prior_var, int32_t acq_kind, double p0, double p1,
+                    int32_t iters, double step0, double *acq_out, double *acq0_out, int32_t *accepted_out, double *pg_out,
+                    gpbo_result *result, void *work, int64_t work_bytes, void *stream);
+int gpbo_refine_host_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
+                         double jitter1, double jitter2, double *Xq_host /* in / out [P x d] */, int64_t P,
+                         const double *lower_host, const double *upper_host, int32_t acq_kind, double p0, double p1,
+                         int32_t iters, double step0, double *acq_out_host, double *acq0_out_host,
+                         int32_t *accepted_out_host, double *pg_out_host, gpbo_result *result_host, int32_t *info_host);
 
 /* ---- Host-pointer entry points: the reference's call sequence on NumPy-style arrays, no device handling by the
  * caller (device buffers and a private stream live inside the call).  What a ctypes stub in the reference binds.

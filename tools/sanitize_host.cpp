@@ -142,6 +142,25 @@ int main() {
     EXPECT(batch(7, 2, 8, 0, 0.0, (int64_t)1 << 40) == GPBO_ERR_ARG && batch(1000, 17, 8, 0, 0.0, wb) == GPBO_ERR_ARG);
     EXPECT(batch(1000, 2, 8, 2, 0.0, wb) == GPBO_ERR_ARG && batch(1000, 2, 8, 1, __builtin_nan(""), wb) == GPBO_ERR_ARG);
     EXPECT(batch(1000, 2, 8, 0, 0.0, wb - 1) == GPBO_ERR_WORKSPACE);
+    // refinement (tests/test_refine_abi_cpu.py): P range, d, Np against N, a box upside down, iters, step0, the workspace one byte short
+    {
+        const double lo[2] = {0.0, 0.0}, hi[2] = {1.0, 1.0}, up[2] = {0.0, -1.0};
+        auto refine = [&](int64_t P, int64_t Np, int32_t d, const double *h, int32_t iters, double step0, int64_t wbytes) {
+            return gpbo_refine_f64(pd, P, lo, h, pd, 100, Np, d, ls, pd, pd, 1.000101, 0, 4.0, 0.0, iters, step0, nullptr, nullptr,
+                                   nullptr, nullptr, reinterpret_cast<gpbo_result *>(p), p, wbytes, nullptr);
+        };
+        const int64_t wr = gpbo_refine_workspace_bytes(128, 8), wg = gpbo_posterior_grad_workspace_bytes(128, 8);
+        EXPECT(wr > wg && wg > 0 && gpbo_refine_workspace_bytes(128, 4097) == -1 && gpbo_posterior_grad_workspace_bytes(100, 8) == -1);
+        EXPECT(refine(0, 128, 2, hi, 30, 0.1, wr) == GPBO_ERR_ARG && refine(4097, 128, 2, hi, 30, 0.1, wr) == GPBO_ERR_ARG);
+        EXPECT(refine(8, 256, 2, hi, 30, 0.1, wr) == GPBO_ERR_ARG && refine(8, 128, 17, hi, 30, 0.1, wr) == GPBO_ERR_ARG);
+        EXPECT(refine(8, 128, 2, up, 30, 0.1, wr) == GPBO_ERR_ARG && refine(8, 128, 2, hi, 1001, 0.1, wr) == GPBO_ERR_ARG);
+        EXPECT(refine(8, 128, 2, hi, 30, __builtin_nan(""), wr) == GPBO_ERR_ARG && refine(8, 128, 2, hi, 30, 0.0, wr) == GPBO_ERR_ARG);
+        EXPECT(refine(8, 128, 2, hi, 30, 0.1, wr - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(gpbo_posterior_grad_f64(pd, 8, pd, 100, 128, 2, ls, pd, pd, 1.000101, 0, 4.0, 0.0, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, p, wg - 1, nullptr) == GPBO_ERR_WORKSPACE);
+        EXPECT(gpbo_posterior_grad_f64(pd, 8, pd, 100, 128, 2, ls, pd, pd, 1.000101, 7, 4.0, 0.0, nullptr, nullptr, nullptr, nullptr,
+                                       nullptr, nullptr, p, wg, nullptr) == GPBO_ERR_ARG);
+    }
     EXPECT(gpbo_potrf_f64(pd, 100, pd, pi, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_trtri_f64(pd, pd, 100, pd, pd, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_nlml_grid_f64(pd, pd, 177, 2, pd, 4, 1e-4, reinterpret_cast<float *>(p), nullptr) == GPBO_ERR_ARG);
