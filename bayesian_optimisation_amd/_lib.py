@@ -25,6 +25,8 @@ BATCH_MAX_Q = 64
 FANTASY_BELIEVER = 0
 FANTASY_LIE = 1
 REFINE_MAX_P = 4096
+TS_MAX_PATHS = 64
+TS_MAX_FEATURES = 16384
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -102,6 +104,14 @@ SIGNATURES = {
                                   _p, _p, _p, _p, _i64, _p]),
     "gpbo_refine_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _f64, _p, _i64, _p, _p, _i32, _f64, _f64, _i32, _f64, _p, _p,
                                        _p, _p, _p, _p]),
+    "gpbo_thompson_weights_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "gpbo_thompson_weights_f64": (C.c_int, [_p, _p, _i64, _i64, _i32, _p, _p, _f64, _f64, _p, _p, _p, _p, _i32, _i32, _p, _p, _i64,
+                                            _p]),
+    "gpbo_thompson_paths_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "gpbo_thompson_paths_f64": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i64, _p, _i64, _p, _p,
+                                          _p, _p, _i64, _p]),
+    "gpbo_thompson_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _f64, _p, _i64, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p,
+                                         _p]),
     "gpbo_acq_workspace_bytes": (_i64, []),
     "gpbo_acq_argmax_f64": (C.c_int, [_p, _p, _i64, _i32, _f64, _f64, _i64, _p, _p, _p, _i64, _p]),
     "gpbo_nlml_grid_max_n": (C.c_int, []),

@@ -267,6 +267,64 @@ extern "C" int gpbo_select_batch_host_f64(const double *X, const double *y, int6
     return GPBO_OK;
 }
 
+// Thompson sampling on host arrays: factorisation + gpbo_thompson_weights_f64 + gpbo_thompson_paths_f64 (csrc/thompson.hip).
+extern "C" int gpbo_thompson_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls, double jitter1,
+                                      double jitter2, const double *Xs, int64_t M, const double *omega, const double *phase,
+                                      const double *W, const double *E, int32_t F, int32_t S, int64_t *idx_out,
+                                      double *val_out, int64_t *nan_out, double *f_out, int32_t *info) {
+    if (!X || !y || !ls || !Xs || !omega || !phase || !W || !E || !idx_out || !val_out || !nan_out || !info)
+        return GPBO_ERR_ARG;
+    if (N < 1 || M < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    if (!(jitter1 + jitter2 >= 0.0)) return GPBO_ERR_ARG;
+    const int64_t Np = gpbo_padded_n(N);
+    const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
+    const int64_t wwts = gpbo_thompson_weights_workspace_bytes(Np, F, S);
+    const int64_t wpaths = gpbo_thompson_paths_workspace_bytes(Np, M, F, S);
+    if (wwts < 0 || wpaths < 0) return GPBO_ERR_ARG;   // F, S, M out of range
+
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N), *dXs = A.alloc<double>(M * d);
+    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
+    double *dom = A.alloc<double>((int64_t)F * d), *dph = A.alloc<double>(F), *dW = A.alloc<double>((int64_t)S * F);
+    double *dE = A.alloc<double>((int64_t)S * N), *dV = A.alloc<double>((int64_t)S * Np);
+    int32_t *dinfo = A.alloc<int32_t>(1);
+    // one workspace serves the three calls in turn (hipMalloc: 256-byte aligned)
+    int64_t wbytes = wfact > wwts ? wfact : wwts;
+    if (wpaths > wbytes) wbytes = wpaths;
+    char *dwork = A.alloc<char>(wbytes);
+    int64_t *dout = A.alloc<int64_t>(3 * (int64_t)S);   // idx | val | nan
+    double *df = f_out ? A.alloc<double>((int64_t)S * M) : nullptr;
+    if (!A.ok) return GPBO_ERR_WORKSPACE;
+    void *st = reinterpret_cast<void *>(A.stream);
+    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N) ||
+        !A.h2d(dXs, Xs, sizeof(double) * M * d) || !A.h2d(dom, omega, sizeof(double) * F * d) ||
+        !A.h2d(dph, phase, sizeof(double) * F) || !A.h2d(dW, W, sizeof(double) * S * F) ||
+        !A.h2d(dE, E, sizeof(double) * S * N))
+        return GPBO_ERR_LAUNCH;
+    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter1, jitter2, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    if (rc != GPBO_OK) return rc;
+    if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
+    if (*info != 0) {  // not positive definite: no posterior to sample from
+        for (int32_t s = 0; s < S; ++s) {
+            idx_out[s] = -1;
+            val_out[s] = __builtin_nan("");
+            nan_out[s] = 0;
+        }
+        return GPBO_OK;
+    }
+    rc = gpbo_thompson_weights_f64(dX, dy, N, Np, d, ls, dU, jitter1, jitter2, dom, dph, dW, dE, F, S, dV, dwork, wwts, st);
+    if (rc != GPBO_OK) return rc;
+    rc = gpbo_thompson_paths_f64(dXs, M, dX, N, Np, d, ls, dom, dph, dW, dV, F, S, 0, df, M, dout,
+                                 reinterpret_cast<double *>(dout + S), dout + 2 * (int64_t)S, dwork, wpaths, st);
+    if (rc != GPBO_OK) return rc;
+    bool okc = A.d2h(idx_out, dout, sizeof(int64_t) * S) && A.d2h(val_out, dout + S, sizeof(double) * S) &&
+               A.d2h(nan_out, dout + 2 * (int64_t)S, sizeof(int64_t) * S);
+    if (f_out) okc = okc && A.d2h(f_out, df, sizeof(double) * S * M);
+    if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
+    return GPBO_OK;
+}
+
 // Off-grid refinement on host arrays: factorisation + gpbo_refine_f64 (csrc/refine.hip).
 extern "C" int gpbo_refine_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls, double jitter1,
                                     double jitter2, double *Xq, int64_t P, const double *lower, const double *upper,

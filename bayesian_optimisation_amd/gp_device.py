@@ -101,6 +101,33 @@ class RefineResult:
     grid_val: Optional[float] = None
 
 
+@dataclass
+class ThompsonPaths:
+    """What DeviceGP.thompson_paths returns: S sample paths of the posterior as device tensors (include/gpbo.h).  Valid until
+    the next factorise() / append() / load_state_dict() of the surrogate that made them."""
+    omega: object                    # fp64 [F x d]
+    phase: object                    # fp64 [F]
+    W: object                        # fp64 [S x F]
+    V: object                        # fp64 [S x Np]: v_s = K^-1 (y - g_s(X) - sqrt(kappa) E[s]), factorisation order
+    n_paths: int
+    n_features: int
+    seed: int
+    epoch: tuple = ()                # the factorisation they belong to
+
+
+@dataclass
+class ThompsonResult:
+    """What DeviceGP.thompson_score / select_thompson return, one entry per path (select_thompson: per selected point)."""
+    indices: np.ndarray              # int64: idx_offset + the lowest row minimising the path (-1: no usable row)
+    values: np.ndarray               # float64: the acquisition -f_s there
+    nan_counts: np.ndarray           # int64 [n_paths]: rows whose value is NaN, per path
+    f: Optional[object] = None       # dense=True: torch fp64 device tensor [n_paths x M], the paths at the rows of Xs
+
+    @property
+    def nan_count(self) -> int:
+        return int(np.sum(self.nan_counts))
+
+
 def refine_params(P: int, d: int, iters: int, step0: float) -> tuple:
     """(iters, step0) as the C ABI takes them; refuses what gpbo_refine_f64 refuses (include/gpbo.h)."""
     if not 1 <= int(P) <= _lib.REFINE_MAX_P:
@@ -154,7 +181,8 @@ class DeviceGP:
         self.K = self.U = self.alpha = None
         # workspaces, kept from call to call and only ever grown (_workspace)
         self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
-        self._work_qei = self._work_ard = self._work_batch = self._work_refine = None
+        self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = None
+        self._epoch = 0              # counts factorise() / append() / load_state_dict(): ThompsonPaths belong to one of them
         self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
         self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
         self.U8, self._u8_valid = None, False                   # prepare_i8()
@@ -297,6 +325,7 @@ class DeviceGP:
             self.jitter1, self.jitter2 = float(jitter1), float(jitter2)
             self._owns_xy = False
             self.n_appended = 0  # columns of U built by append() since the last full factorisation
+            self._epoch += 1
             if self.K is None or self.K.shape[0] != Np or self.U.shape[0] != Np:
                 # the factor buffers (and the workspace) are kept from step to step: a BO loop refactorises
                 # at the same padded size many times, and fresh 100-MB allocations cost more than the kernels
@@ -430,6 +459,7 @@ class DeviceGP:
                 self.perm = torch.cat([self.perm[:N], torch.tensor([N], dtype=torch.int64, device=self.device)])
             self.N = N + 1
             self.n_appended += 1
+            self._epoch += 1
             del work
         return self
 
@@ -453,6 +483,7 @@ class DeviceGP:
         Np = int(self.lib.gpbo_padded_n(N))
         with torch.cuda.device(self.device):
             self.N, self.Np, self.d = N, Np, d
+            self._epoch += 1
             self.ls_h = np.ascontiguousarray(np.asarray(st["ls"], dtype=np.float64).reshape(-1))
             self.jitter1, self.jitter2 = float(st["jitter1"]), float(st["jitter2"])
             self.n_appended = int(st["n_appended"]) if "n_appended" in st else 0
@@ -862,6 +893,83 @@ class DeviceGP:
             raise ValueError(f"q must be in [1, min({_lib.BATCH_MAX_Q}, M = {M})], got {q}")
         _, mu, sigma, _ = self.score_async(Xsd, acquisition, explore, f_best, xi, dense=True, idx_offset=idx_offset)
         return self.select_batch_on_posterior(Xsd, mu, sigma, q, acquisition, explore, f_best, xi, fantasy, lie, idx_offset)
+
+    # -- Thompson sampling by pathwise posterior samples (csrc/thompson.hip) ---------------------------
+    def thompson_paths(self, n_paths: int, n_features: int = 2048, seed: int = 0) -> ThompsonPaths:
+        """n_paths samples of the posterior FUNCTION (pathwise conditioning: a random-Fourier-feature draw of the prior plus
+        the mean's own sum with v_s = K^-1 (y - g_s(X) - sqrt(kappa) E[s]) in the place of alpha).  The draws are
+        thompson.thompson_draws(d, n_features, n_paths, N, seed); the columns of E follow the CALLER's order of the
+        observations, so a seed gives the same paths under factorise(order="fps").  gpbo_thompson_weights_f64: enqueues
+        only.  The paths stay valid until the next factorise() / append() / load_state_dict()."""
+        from .thompson import path_params, thompson_draws
+
+        n_paths, n_features, seed = path_params(n_paths, n_features, seed)
+        self._need_unrolled_d("thompson_paths()")
+        if self.N < 1:
+            raise _lib.GpboError("thompson_paths() needs a factorised surrogate")
+        torch = self.torch
+        omega, phase, W, E = thompson_draws(self.d, n_features, n_paths, self.N, seed)
+        p = self._perm_host()
+        if p is not None:
+            E = E[:, p]   # row i of the factorisation is the caller's row p[i]
+        with torch.cuda.device(self.device):
+            om, ph, Wd, Ed = self._dev(omega), self._dev(phase), self._dev(W), self._dev(E)
+            V = torch.empty((n_paths, self.Np), dtype=torch.float64, device=self.device)
+            need = int(self.lib.gpbo_thompson_weights_workspace_bytes(self.Np, n_features, n_paths))
+            work = self._workspace("_work_thompson", need)
+            st = self.lib.gpbo_thompson_weights_f64(
+                self._ptr(self.X), self._ptr(self.y), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
+                self._ptr(self.U), self.jitter1, self.jitter2, self._ptr(om), self._ptr(ph), self._ptr(Wd), self._ptr(Ed),
+                n_features, n_paths, self._ptr(V), self._ptr(work), need, self._stream())
+            _lib.check(st, "gpbo_thompson_weights_f64")
+        self._keep = Ed   # alive until the stream has consumed it
+        return ThompsonPaths(om, ph, Wd, V, n_paths, n_features, seed, (id(self), self._epoch))
+
+    def thompson_score(self, paths: ThompsonPaths, Xs, dense: bool = False, idx_offset: int = 0) -> ThompsonResult:
+        """Every path at the rows of Xs in one launch (gpbo_thompson_paths_f64): per path the lowest row minimising it, the
+        acquisition -f_s there and, with dense=True, the paths themselves [n_paths x M] on the device.  One read-back
+        (synchronises).  IndexError when a value is NaN (a candidate with a non-finite coordinate), as the other
+        acquisitions raise."""
+        self._need_unrolled_d("thompson_score()")
+        if not isinstance(paths, ThompsonPaths) or paths.epoch != (id(self), self._epoch):
+            raise ValueError("these sample paths do not belong to the surrogate as it is now: call thompson_paths() again "
+                             "after factorise() / append()")
+        torch = self.torch
+        Xsd, M = self._candidates(Xs)
+        S, F = paths.n_paths, paths.n_features
+        with torch.cuda.device(self.device):
+            need = int(self.lib.gpbo_thompson_paths_workspace_bytes(self.Np, M, F, S))
+            work = self._workspace("_work_thompson", need)
+            f = torch.empty((S, M), dtype=torch.float64, device=self.device) if dense else None
+            out = torch.zeros(3 * S, dtype=torch.int64, device=self.device)   # indices | values | NaN counts: one copy
+            st = self.lib.gpbo_thompson_paths_f64(
+                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
+                self._ptr(paths.omega), self._ptr(paths.phase), self._ptr(paths.W), self._ptr(paths.V), F, S, int(idx_offset),
+                self._ptr(f), M, self._ptr(out[:S]), self._ptr(out[S: 2 * S]), self._ptr(out[2 * S:]), self._ptr(work), need,
+                self._stream())
+            _lib.check(st, "gpbo_thompson_paths_f64")
+            h = out.cpu()   # synchronises: Xsd has been consumed
+        res = ThompsonResult(indices=h[:S].numpy().copy(), values=h[S: 2 * S].view(torch.float64).numpy().copy(),
+                             nan_counts=h[2 * S:].numpy().copy(), f=f)
+        if res.nan_counts.any():
+            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+        return res
+
+    def select_thompson(self, Xs, q: int, n_paths: Optional[int] = None, n_features: int = 2048, seed: int = 0,
+                        idx_offset: int = 0) -> ThompsonResult:
+        """q candidates to evaluate in parallel by Thompson sampling: the minimisers of independent posterior sample paths.
+        n_paths (default min(64, 2 q)) paths are drawn and scored, and the first q DISTINCT winners in path order are
+        returned - FEWER than q when the paths agree: that is the posterior saying it has converged on those points, and a
+        caller who needs q points regardless tops the batch up with select_batch().  No variance pass is run.
+        ValueError on bad q / n_paths / n_features / seed before any GPU work; IndexError when a value is NaN."""
+        from .thompson import first_distinct, select_params
+
+        self._need_unrolled_d("select_thompson()")
+        Xsd, M = self._candidates(Xs)
+        q, n_paths, n_features, seed = select_params(q, n_paths, n_features, seed, M=M, d=self.d)
+        r = self.thompson_score(self.thompson_paths(n_paths, n_features, seed), Xsd, idx_offset=idx_offset)
+        keep = first_distinct(r.indices, q)
+        return ThompsonResult(indices=r.indices[keep], values=r.values[keep], nan_counts=r.nan_counts)
 
     # -- acquisition gradients and off-grid refinement (csrc/refine.hip, DESIGN 4d) -------------------------------
     def _points(self, Xq, what: str):

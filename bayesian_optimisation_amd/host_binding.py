@@ -121,6 +121,37 @@ def select_batch(X, y, ls, Xs, q: int, acquisition: str = "lcb", explore: float 
     return dict(indices=idx, values=val, nan_count=int(res[2]), info=int(info.value), mu=mu, sigma=sigma)
 
 
+def select_thompson(X, y, ls, Xs, q: int, n_paths=None, n_features: int = 2048, seed: int = 0, dense: bool = False,
+                    lib=None) -> dict:
+    """q points by Thompson sampling on host arrays (gpbo_thompson_host_f64: factorisation, path weights and the paths over
+    all candidates in one call; the draws are thompson.thompson_draws(d, n_features, n_paths, N, seed)).  Returns
+    dict(indices, values: the first q DISTINCT winners in path order - fewer than q when the paths agree -, all_indices,
+    all_values, nan_counts [n_paths], info, f [n_paths x M] with dense=True)."""
+    from .thompson import first_distinct, select_params, thompson_draws
+
+    X, y, Xs = _f64(X), _f64(y).reshape(-1), _f64(Xs)
+    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
+    if X.ndim != 2 or Xs.ndim != 2:
+        raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
+    N, d = X.shape
+    M = Xs.shape[0]
+    if Xs.shape[1] != d or ls.size != d or y.size != N:
+        raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
+    q, S, F, seed = select_params(q, n_paths, n_features, seed, M=M, d=d)
+    lib = lib or _lib.load()
+    omega, phase, W, E = (_f64(a) for a in thompson_draws(d, F, S, N, seed))
+    idx, val, nan = np.full(S, -1, dtype=np.int64), np.full(S, np.nan), np.zeros(S, dtype=np.int64)
+    f = np.empty((S, M)) if dense else None
+    info = C.c_int32(0)
+    _lib.note_hip_use()
+    st = lib.gpbo_thompson_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M, _ptr(omega),
+                                    _ptr(phase), _ptr(W), _ptr(E), F, S, _ptr(idx), _ptr(val), _ptr(nan), _ptr(f),
+                                    C.cast(C.pointer(info), C.c_void_p))
+    _lib.check(st, "gpbo_thompson_host_f64")
+    keep = first_distinct(idx, q)
+    return dict(indices=idx[keep], values=val[keep], all_indices=idx, all_values=val, nan_counts=nan, info=int(info.value), f=f)
+
+
 def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
            iters: int = 30, step0: float = 0.1, lib=None) -> dict:
     """Off-grid refinement on host arrays (gpbo_refine_host_f64: factorisation and refinement in one call).  Returns
@@ -262,6 +293,17 @@ class PointSelectorHost(PointSelector):
         if r["info"] != 0 and np.all(r["indices"] < 0):
             raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)})")
         return self._batch_indices(r["indices"], r["nan_count"])
+
+    def select_thompson(self, q, n_features=2048, seed=0):
+        """PointSelector.select_thompson on the host-pointer route (gpbo_thompson_host_f64): the same (k, ndim) multi-indices
+        for the same seed, the same errors."""
+        if self._inputs is None:
+            raise RuntimeError("call update_surrogate() first")
+        X, y, ls, Xs = self._inputs
+        r = select_thompson(X, y, ls, Xs, q, n_features=n_features, seed=seed, lib=self.lib)
+        if r["info"] != 0:
+            raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)})")
+        return self._batch_indices(r["indices"], int(np.sum(r["nan_counts"])))
 
     def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
         """PointSelector.refine_next on the host-pointer route (gpbo_refine_host_f64): the same d coordinates, the same

@@ -24,7 +24,7 @@ Differences from the reference, all deliberate:
     The screens' tolerance is verified per call on every re-scored candidate and a strided sample, not proven for each
     candidate: the route that is exact by construction is `dense_outputs=False` (the prefix bound).
     Also extra: `expected_improvement(xi)`,
-    `q_expected_improvement()`, `select_batch(q)` (q points for parallel evaluation: greedy Kriging believer / GP-BUCB /
+    `q_expected_improvement()`, `select_thompson(q)` (q points as the minimisers of posterior sample paths), `select_batch(q)` (q points for parallel evaluation: greedy Kriging believer / GP-BUCB /
     constant liar), `refine_next()` (the next point off the grid: the best candidates polished by acquisition gradients), `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
     calls go through the exact prefix bound), `kernel_params` may be preset (then no
     ARD search runs), optional multi-GPU candidate sharding when torch.distributed is initialised,
@@ -519,6 +519,28 @@ class PointSelector:
         # the candidates update_surrogate() left on the device: no second upload of M x d values
         r = self._gp.select_batch_on_posterior(self._xs_dev, self._mu_dev.clone(), self._sigma_dev.clone(), int(q),
                                                fantasy=fantasy, lie=lie, **kw)
+        return self._batch_indices(r.indices, r.nan_count)
+
+    def select_thompson(self, q, n_features=2048, seed=0):
+        """Not in the reference (one point per iteration): up to q points to evaluate in parallel by Thompson sampling on the
+        surrogate of the last update_surrogate() - the minimisers of min(64, 2 q) independent sample paths of the posterior
+        (pathwise conditioning on n_features random Fourier features, DeviceGP.select_thompson), the first q
+        DISTINCT ones in path order.  Returns their (k, ndim) int64 multi-indices, k <= q: FEWER than q when the paths agree,
+        which is the posterior saying it has converged there - top the batch up with select_batch().  One seed gives the
+        same points here and in PointSelectorHost.  No variance pass is run, so every precision= and dense_outputs=False
+        work; mean_func / cov_func / acq_func_eval stay as update_surrogate() set them.  IndexError when a candidate has a
+        non-finite coordinate; candidates sharded over more than one rank are OUT OF SCOPE: NotImplementedError."""
+        from .thompson import select_params
+
+        if self._cached is None:
+            raise RuntimeError("call update_surrogate() first")
+        Xs = np.asarray(self.predicted_pts, dtype=np.float64)
+        Xs = Xs.reshape(len(Xs), -1)
+        select_params(q, None, n_features, seed, M=len(Xs), d=Xs.shape[1])   # (refused before any GPU work)
+        if self._world()[0] > 1:
+            raise NotImplementedError("select_thompson() with candidates sharded over several ranks is not implemented")
+        # the candidates update_surrogate() left on the device where it did: no second upload of M x d values
+        r = self._gp.select_thompson(self._xs_dev if self._xs_dev is not None else Xs, q, n_features=n_features, seed=seed)
         return self._batch_indices(r.indices, r.nan_count)
 
     def _refine_inputs(self, n_starts, iters, acquisition, explore, xi):

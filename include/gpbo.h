@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -400,6 +400,53 @@ int gpbo_refine_host_f64(const double *X_host, const double *y_host, int64_t N, 
                          const double *lower_host, const double *upper_host, int32_t acq_kind, double p0, double p1,
                          int32_t iters, double step0, double *acq_out_host, double *acq0_out_host,
                          int32_t *accepted_out_host, double *pg_out_host, gpbo_result *result_host, int32_t *info_host);
+
+/* Thompson sampling by pathwise posterior samples (csrc/thompson.hip; not in the reference, whose acquisitions
+ * are functions of (mean_func, cov_func)).  Pathwise conditioning (Wilson et al. 2020) writes a sample of the posterior
+ * FUNCTION as
+ *   f_s(x) = g_s(x) + sum_n k0(x, x_n) v_s[n],   g_s(x) = sqrt(2 / F) sum_f W[s,f] cos(2 pi t_f(x)),
+ *   t_f(x) = sum_k Omega[f,k] x_k / (2 pi ls_k) + phase[f] (turns),   v_s = K^-1 (y - g_s(X) - sqrt(kappa) E[s,:]),
+ *   kappa = jitter1 + jitter2,  K = k0(X,X) + kappa I (the matrix the factorisation inverts).
+ * The random draws are INPUTS (device arrays, as Z is for gpbo_posterior_qei_f64): omega [F x d] unit normal, phase [F]
+ * uniform in [0, 1), W [S x F] and E [S x N] unit normal; column n of E belongs to row n of X as given to the call.
+ * gpbo_thompson_weights_f64: V [S x Np] = the v_s (zero on the padding) from a factorisation's X, y, U and the jitters it was
+ *   made with: g_s(X) by the paths kernel itself, the residual, then the two dense products with U (U U^T = K^-1) on the
+ *   matrix cores.  U 16-byte aligned.  Once per factorisation and set of draws.
+ * gpbo_thompson_paths_f64: every path at the M rows of Xs in one launch plus a finish; nothing of K(X*,X) is stored, the
+ *   N kernel entries and F cosines of a candidate are generated once and shared by all S paths.  The acquisition of path s
+ *   is -f_s (the project minimises the objective and maximises acquisitions):
+ *   idx_out[s] = idx_offset + the LOWEST row attaining max_c -f_s(c), or -1 when no row is usable; val_out[s] = that maximum
+ *   (NaN when none); nan_out[s] = rows whose value is NaN - a row with a non-finite coordinate is NaN in every path and is
+ *   never chosen.  f_out: optional dense [S x ldf] (row s = path s, ldf >= M).  V == NULL: the prior paths g_s alone (X is
+ *   then not read, but must still be non-null: GPBO_ERR_ARG).  Kernel entries: the fp64 path's own arithmetic - with W = 0, S = 1, V = alpha the output is the mean.
+ * 1 <= d <= GPBO_MAX_D, 1 <= F <= GPBO_TS_MAX_FEATURES, 1 <= S <= GPBO_TS_MAX_PATHS, 1 <= M <= 2^31, ls > 0, Np a multiple of
+ *   GPBO_NPAD, 1 <= N <= Np (GPBO_ERR_ARG otherwise, before any launch);  work: gpbo_thompson_weights_workspace_bytes(Np, F, S)
+ *   / gpbo_thompson_paths_workspace_bytes(Np, M, F, S) bytes (negative: invalid sizes), 256-byte aligned (GPBO_ERR_WORKSPACE).
+ *   Both calls only enqueue and never synchronise; sums run in a fixed order and only the integer NaN counters use atomics:
+ *   two calls give the same bits.
+ * gpbo_thompson_host_f64: factorisation + weights + paths on host arrays (conventions of gpbo_select_batch_host_f64: X, y, N,
+ *   d, ls, jitter1, jitter2, Xs, M; the four draw arrays on the host);  idx_out_host / val_out_host / nan_out_host [S],
+ *   f_out_host optional [S x M];  info_host: 0, or the failing pivot of the factorisation - then every index is -1. */
+#define GPBO_TS_MAX_PATHS 64
+#define GPBO_TS_MAX_FEATURES 16384
+int64_t gpbo_thompson_weights_workspace_bytes(int64_t Np, int32_t F, int32_t S);
+int gpbo_thompson_weights_f64(const double *X, const double *y, int64_t N, int64_t Np, int32_t d, const double *ls_host,
+                              const double *U, double jitter1, double jitter2, const double *omega /* [F x d] */,
+                              const double *phase /* [F] */, const double *W /* [S x F] */, const double *E /* [S x N] */,
+                              int32_t F, int32_t S, double *V /* out [S x Np], zero on the padding */, void *work,
+                              int64_t work_bytes, void *stream);
+int64_t gpbo_thompson_paths_workspace_bytes(int64_t Np, int64_t M, int32_t F, int32_t S);
+int gpbo_thompson_paths_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
+                            const double *ls_host, const double *omega, const double *phase, const double *W,
+                            const double *V /* [S x Np], or NULL: the prior paths g_s alone */, int32_t F, int32_t S,
+                            int64_t idx_offset, double *f_out /* optional [S x ldf] */, int64_t ldf,
+                            int64_t *idx_out /* [S] */, double *val_out /* [S] */, int64_t *nan_out /* [S] */, void *work,
+                            int64_t work_bytes, void *stream);
+int gpbo_thompson_host_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
+                           double jitter1, double jitter2, const double *Xs_host, int64_t M, const double *omega_host,
+                           const double *phase_host, const double *W_host, const double *E_host, int32_t F, int32_t S,
+                           int64_t *idx_out_host, double *val_out_host, int64_t *nan_out_host,
+                           double *f_out_host /* optional [S x M] */, int32_t *info_host);
 
 /* ---- Host-pointer entry points: the reference's call sequence on NumPy-style arrays, no device handling by the
  * caller (device buffers and a private stream live inside the call).  What a ctypes stub in the reference binds.

@@ -161,6 +161,32 @@ int main() {
         EXPECT(gpbo_posterior_grad_f64(pd, 8, pd, 100, 128, 2, ls, pd, pd, 1.000101, 7, 4.0, 0.0, nullptr, nullptr, nullptr, nullptr,
                                        nullptr, nullptr, p, wg, nullptr) == GPBO_ERR_ARG);
     }
+    // Thompson sampling (tests/test_thompson_abi_cpu.py): the ranges of F, S, d, M, the dense output's leading dimension, the
+    // workspaces one byte short; V == NULL alone is legal and reaches the workspace check
+    {
+        int64_t *pl = reinterpret_cast<int64_t *>(p);
+        int32_t info_t = 0;
+        auto paths = [&](int64_t M, int32_t d, int32_t F, int32_t S, const double *V, double *f_out, int64_t ldf, int64_t wbytes) {
+            return gpbo_thompson_paths_f64(pd, M, pd, 100, 128, d, ls, pd, pd, pd, V, F, S, 0, f_out, ldf, pl, pd, pl, p, wbytes,
+                                           nullptr);
+        };
+        auto weights = [&](int64_t N, int64_t Np, int32_t F, int32_t S, double j1, int64_t wbytes) {
+            return gpbo_thompson_weights_f64(pd, pd, N, Np, 2, ls, pd, j1, 1e-6, pd, pd, pd, pd, F, S, pd, p, wbytes, nullptr);
+        };
+        const int64_t wp = gpbo_thompson_paths_workspace_bytes(128, 1000, 64, 16), ww = gpbo_thompson_weights_workspace_bytes(128, 64, 16);
+        EXPECT(wp > 0 && ww > wp && gpbo_thompson_paths_workspace_bytes(128, 0, 64, 16) == -1 &&
+               gpbo_thompson_weights_workspace_bytes(128, 16385, 16) == -1 && gpbo_thompson_paths_workspace_bytes(100, 1000, 64, 16) == -1);
+        EXPECT(paths(0, 2, 64, 16, pd, nullptr, 0, wp) == GPBO_ERR_ARG && paths(1000, 17, 64, 16, pd, nullptr, 0, wp) == GPBO_ERR_ARG);
+        EXPECT(paths(1000, 2, 0, 16, pd, nullptr, 0, wp) == GPBO_ERR_ARG && paths(1000, 2, 64, 65, pd, nullptr, 0, wp) == GPBO_ERR_ARG);
+        EXPECT(paths(1000, 2, 64, 16, pd, pd, 999, wp) == GPBO_ERR_ARG);
+        EXPECT(paths(1000, 2, 64, 16, pd, nullptr, 0, wp - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(paths(1000, 2, 64, 16, nullptr, nullptr, 0, wp - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(weights(129, 128, 64, 16, 1e-4, ww) == GPBO_ERR_ARG && weights(100, 100, 64, 16, 1e-4, ww) == GPBO_ERR_ARG);
+        EXPECT(weights(100, 128, 64, 0, 1e-4, ww) == GPBO_ERR_ARG && weights(100, 128, 64, 16, -1.0, ww) == GPBO_ERR_ARG);
+        EXPECT(weights(100, 128, 64, 16, 1e-4, ww - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(gpbo_thompson_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr,
+                                      nullptr, nullptr, nullptr, &info_t) == GPBO_ERR_ARG);
+    }
     EXPECT(gpbo_potrf_f64(pd, 100, pd, pi, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_trtri_f64(pd, pd, 100, pd, pd, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_nlml_grid_f64(pd, pd, 177, 2, pd, 4, 1e-4, reinterpret_cast<float *>(p), nullptr) == GPBO_ERR_ARG);
