@@ -61,6 +61,9 @@ typedef const __attribute__((address_space(1))) void glb_void_t;
 // `g` (the tile base) is wave-uniform as well and `off` a 32-bit BYTE offset per lane: the piece is a buffer load through a
 // descriptor made of the tile base (buffer_load_dwordx4 v_off, s[desc], 0 offen lds) and needs no vector instruction to form
 // a 64-bit address; the global_load_lds form cost one v_lshl_add_u64 per piece, all six into the same register pair.
+#ifndef GPBO_SIGMA_STATIC_RING
+#define GPBO_SIGMA_STATIC_RING 1  // 0: every k tile through the run-time ring position (A/B builds; see the tile loop)
+#endif
 #ifndef GPBO_SIGMA_DMA_GLOBAL
 #define GPBO_SIGMA_DMA_GLOBAL 0   // 1: the global_load_lds form (A/B builds)
 #endif
@@ -99,7 +102,9 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
                           128 ncb observations is a LOWER bound of |v|^2, the variance from it an upper bound) */) {
     __shared__ double smem[3 * STAGE];
     // diagnostics: TV = the timing variant (1 = no barrier and no DMA, 2 = no tile skipping on the diagonal, 3 = no barrier,
-    // 4 = no DMA); VARIANT 6 = the product loop with per-tile stamps, 8 + v = timing variant v with per-tile stamps
+    // 4 = no DMA, 5 = every fragment read from stage 0, so that the fragment addresses are loop invariants, 7 = as 5 with
+    // half of the fragment reads); VARIANT 6 = the product loop with per-tile stamps, 8 + v = timing
+    // variant v with per-tile stamps
     constexpr bool STAMP = VARIANT == 6 || VARIANT >= 8;
     constexpr int TV = VARIANT >= 8 ? VARIANT - 8 : (VARIANT == 6 ? 0 : VARIANT);
     // Column split (few candidates, e.g. the re-scoring behind a screen): workgroup (x, s) of S takes the column
@@ -199,6 +204,7 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
 
     double a0[MI], b0[NI], a1[MI], b1[NI];
     auto lds_frag = [&](double (&af)[MI], double (&bf)[NI], int buf, int kk) {
+        if (TV == 5 || TV == 7) buf = 0;  // timing only: every fragment address is a loop invariant
         const double *As = smem + buf * STAGE;
         const double *Bs = As + A_TILE;
 #pragma unroll
@@ -207,19 +213,23 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
         for (int ni = 0; ni < NI; ++ni) bf[ni] = Bs[(kk + l4) * LDB + (WQ * ni + wq) * 16 + l15];
     };
     lds_frag(a0, b0, 0, 0);
+    if (TV == 7) lds_frag(a1, b1, 0, 4);  // timing only: the second fragment set is read here and never again
     int dbg_it = 0;
-    int cur = 0;
+    int ring = 0;
     // One tile.  FULL = every 16x16 tile of U in it is non-zero (all k tiles left of the diagonal block): the
     // MFMA stream is then free of branches; on the diagonal block, MFMA groups of 16-column tiles that lie wholly
     // below U's diagonal are branched over (wave-uniform).  LDS reads, barrier and DMA are the same in both.
-    auto tile_body = [&](auto full_tag, int jb, int kt) {
+    // RING = the tile's stage where the caller knows it at compile time, -1 = the run-time ring position `ring`.
+    auto tile_body = [&](auto full_tag, auto ring_tag, int jb, int kt) {
         constexpr bool FULL = decltype(full_tag)::value;
+        constexpr int RING = decltype(ring_tag)::value;
         if (STAMP && vbuf && tid == 0) {  // diagnostic: cycle stamp per tile (timing build only)
             vbuf[(int64_t)blockIdx.x * 1024 + dbg_it] = (double)__builtin_amdgcn_s_memtime();
             if (dbg_it == 0 || (jb == nJ - 1 && kt == nJ * (BN / BK) - 1))  // 100 MHz wall clock at both ends (S = 1)
                 vbuf[(int64_t)blockIdx.x * 1024 + (dbg_it == 0 ? 1000 : 1001)] = (double)__builtin_amdgcn_s_memrealtime();
             ++dbg_it;
         }
+        const int cur = RING >= 0 ? RING : ring;
         const int nxt = (cur == 2) ? 0 : cur + 1;
         // first 16-column tile of this wave that still has non-zero rows of U in this k tile (>= 4: none)
         // (wave column group wq owns the 16-column tiles WQ ni + wq of the block, so on the diagonal all waves
@@ -239,7 +249,7 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
         };
         __builtin_amdgcn_sched_barrier(0);
         mfma8(a0, b0, 0);
-        lds_frag(a1, b1, cur, 4);
+        if (TV != 7) lds_frag(a1, b1, cur, 4);
         __builtin_amdgcn_sched_barrier(0);
         mfma8(a0, b0, NI / 2);
         __builtin_amdgcn_sched_barrier(0);
@@ -269,6 +279,10 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
         // take scalar instructions only (glds16): -216 cycles per tile, 506.8 -> 494.2 ms per step on one box, same bits.
         // The rest is 80 cycles of DMA issue, a barrier that now costs nothing (the loop is no faster without it) and 264
         // cycles that remain with neither (the fragment reads and their address arithmetic).
+        // Those were split next (variants 5 and 7, which take the run-time loop; one box, two runs each): product 8,528 cycles |
+        // 29.80-29.86 ms; every fragment address a loop invariant (5; 2 adds per wave and tile instead of 12) 8,472 | 29.24-29.26;
+        // half of the reads as well (7) 8,388 | 30.02-30.03.  Cycles and launch time do not move together here: the launch
+        // time is the yardstick.
         // Tried beside it on the same box, all slower, per step: the six pieces spread over the MFMA groups of the half tile,
         // one or two per group (global form 517 / 520 ms against 507; buffer form 508 / 501 against 494: a piece issued among
         // MFMAs stalls more often than six in a row do); s_setprio 1 for waves 4-7 in front of the loop (517 against 507 with the
@@ -278,7 +292,7 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
         if (do_stage && wq == 0) stage_next();
         __builtin_amdgcn_sched_barrier(0);
         mfma8(a0, b0, 0);
-        lds_frag(a1, b1, cur, 12);
+        if (TV != 7) lds_frag(a1, b1, cur, 12);
         __builtin_amdgcn_sched_barrier(0);
         mfma8(a0, b0, NI / 2);
         __builtin_amdgcn_sched_barrier(0);
@@ -288,12 +302,28 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
         mfma8(a1, b1, NI / 2);
         __builtin_amdgcn_sched_barrier(0);
         if (do_stage && wq != 0) stage_next();
-        cur = nxt;
+        if (RING < 0) ring = nxt;
     };
     for (int rr = 0, jb = jb_of(0); jb < nJ; jb = jb_of(++rr)) {
         const int heavy = jb * (BN / BK);
-        for (int kt = 0; kt < heavy; ++kt) tile_body(std::true_type{}, jb, kt);
-        for (int kt = heavy; kt < heavy + BN / BK; ++kt) tile_body(std::false_type{}, jb, kt);
+        constexpr std::integral_constant<int, -1> any_stage{};
+        int kt = 0;
+        if (GPBO_SIGMA_STATIC_RING && TV != 5 && TV != 7) {
+            // The full tiles run three at a time from ring position 0: the stage of each is then a compile-time constant
+            // and the 12 vector adds per wave and tile that re-base the ds_read2_b64 pairs on the run-time stage fall to 6
+            // (same reads, same order, same bits).  Up to two tiles in front (until the ring is at 0) and up to two behind
+            // go through the run-time form, as the diagonal block does.  Three separate loops: one loop that branches
+            // between the two forms makes hipcc spill 430 registers.  DESIGN 8a has the forms with NO add in the loop
+            // (fragment bases kept in registers; compiler-scheduled or inline-assembly reads): all slower than this one.
+            for (; ring != 0 && kt < heavy; ++kt) tile_body(std::true_type{}, any_stage, jb, kt);
+            for (; kt + 3 <= heavy; kt += 3) {
+                tile_body(std::true_type{}, std::integral_constant<int, 0>{}, jb, kt);
+                tile_body(std::true_type{}, std::integral_constant<int, 1>{}, jb, kt + 1);
+                tile_body(std::true_type{}, std::integral_constant<int, 2>{}, jb, kt + 2);
+            }
+        }
+        for (; kt < heavy; ++kt) tile_body(std::true_type{}, any_stage, jb, kt);
+        for (int kt = heavy; kt < heavy + BN / BK; ++kt) tile_body(std::false_type{}, any_stage, jb, kt);
         // column block finished: fold |V|^2 into the row sums (GRAM: V V^T of each tile's 16 candidates into the Gram blocks)
         if (GRAM) {
 #pragma unroll
@@ -780,8 +810,8 @@ void launch_sigma(const SigmaLaunch &a, hipStream_t st) {
 void launch_sigma_variant(const SigmaLaunch &a, hipStream_t st) {
 #ifdef GPBO_DIAGNOSTICS
     static const int variant = env_int("GPBO_SIGMA_VARIANT", 0);
-    // the grouped launch has variants 1 3 4 6 9 11 12, the plain one 1 2 3 4 6; anything else is the product kernel
-    const bool have = (a.xg > 1) ? variant != 2 : variant < 9;
+    // the grouped launch has variants 1 3 4 5 6 7 9 11 12 13 15, the plain one 1 2 3 4 6; anything else is the product kernel
+    const bool have = (a.xg > 1) ? variant != 2 : (variant < 9 && variant != 5 && variant != 7);
     switch (have ? variant : 0) {
         case 1: return launch_sigma<1>(a, st);
         case 3: return launch_sigma<3>(a, st);
@@ -790,6 +820,10 @@ void launch_sigma_variant(const SigmaLaunch &a, hipStream_t st) {
         case 9: return launch_sigma<9>(a, st);
         case 11: return launch_sigma<11>(a, st);
         case 12: return launch_sigma<12>(a, st);
+        case 5: return launch_sigma<5>(a, st);
+        case 7: return launch_sigma<7>(a, st);
+        case 13: return launch_sigma<13>(a, st);
+        case 15: return launch_sigma<15>(a, st);
         default: return launch_sigma<0>(a, st);
         case 2: return launch_sigma<2>(a, st);
     }

@@ -1,5 +1,5 @@
-"""Diagnostic (needs a diagnostics build of the library, loaded through GPBO_LIB; GPBO_SIGMA_VARIANT = 6, 9, 11 or 12:
-the product loop, or the timing variants 1 / 3 / 4, with per-tile stamps): per-tile s_memtime stamps of the variance
+"""Diagnostic (needs a diagnostics build of the library, loaded through GPBO_LIB; GPBO_SIGMA_VARIANT = 6, 9, 11, 12, 13 or 15:
+the product loop, or the timing variants 1 / 3 / 4 / 5 / 7, with per-tile stamps): per-tile s_memtime stamps of the variance
 kernel's LAST launch at a shape that takes the column-group launches (N >= 2048, M >= 32768).  Prints the median
 duration of a FULL k tile (left of the diagonal block) and of a diagonal tile, in stamp ticks, over all workgroups.
 Stamped builds are compared with each other only (a stamp costs wave cycles).
