@@ -224,25 +224,7 @@ extern "C" int gpbo_nlml_grad_f64(const double *U, const double *alpha, const do
     if (rc != GPBO_OK) return rc;
 #define CALL(DD)                                                                                                          \
     hipLaunchKernelGGL(nlml_grad_kernel<DD>, dim3((unsigned)tiles), dim3(256), 0, st, U, alpha, Xsc, (int)N, (int)Np, slab)
-    switch (d) {
-        case 1: CALL(1); break;
-        case 2: CALL(2); break;
-        case 3: CALL(3); break;
-        case 4: CALL(4); break;
-        case 5: CALL(5); break;
-        case 6: CALL(6); break;
-        case 7: CALL(7); break;
-        case 8: CALL(8); break;
-        case 9: CALL(9); break;
-        case 10: CALL(10); break;
-        case 11: CALL(11); break;
-        case 12: CALL(12); break;
-        case 13: CALL(13); break;
-        case 14: CALL(14); break;
-        case 15: CALL(15); break;
-        case 16: CALL(16); break;
-        default: return GPBO_ERR_ARG;
-    }
+    GPBO_FOR_D(d, CALL)
 #undef CALL
     hipLaunchKernelGGL(nlml_grad_finish_kernel, dim3(1), dim3(256), 0, st, slab, tiles, (int)d, U, alpha, y, N, Np, info,
                        out);

@@ -296,10 +296,7 @@ extern "C" int gpbo_select_batch_f64(const double *Xs, int64_t M, const double *
 
     BatchLs ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.il2[k] = ls.isc[k] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        ls.il2[k] = 1.0 / (ls_host[k] * ls_host[k]);
-        ls.isc[k] = 1.0 / (ls_host[k] * 1.4142135623730950488);
-    }
+    (void)length_scale_scalings(ls_host, d, ls.il2, ls.isc);   // (cannot refuse: length_scales_ok above has)
     hipStream_t st = gpbo_stream(stream);
     char *w = reinterpret_cast<char *>(work);
     BatchRec *rec = reinterpret_cast<BatchRec *>(w + L.rec_off);
@@ -333,25 +330,7 @@ extern "C" int gpbo_select_batch_f64(const double *Xs, int64_t M, const double *
 #define CALL(DD)                                                                                                            \
     hipLaunchKernelGGL(batch_downdate_kernel<DD>, dim3((unsigned)L.nblk), dim3(256), 0, st, Xs, M, Xsc, (int)N, ls, beta, rec, \
                        j, T, L.ldt, mu, sigma, (int)acq_kind, p0, p1, idx_offset, part_val, part_idx, nan_count)
-        switch (d) {   // (GPBO_DISPATCH_D of kernel_build.hip is local to that unit)
-            case 1: CALL(1); break;
-            case 2: CALL(2); break;
-            case 3: CALL(3); break;
-            case 4: CALL(4); break;
-            case 5: CALL(5); break;
-            case 6: CALL(6); break;
-            case 7: CALL(7); break;
-            case 8: CALL(8); break;
-            case 9: CALL(9); break;
-            case 10: CALL(10); break;
-            case 11: CALL(11); break;
-            case 12: CALL(12); break;
-            case 13: CALL(13); break;
-            case 14: CALL(14); break;
-            case 15: CALL(15); break;
-            case 16: CALL(16); break;
-            default: return GPBO_ERR_ARG;
-        }
+        GPBO_FOR_D(d, CALL)
 #undef CALL
         GPBO_CHECK_LAUNCH();
         rc = gpbo_launch_argmax_finish(part_val, part_idx, L.nblk, nan_count, result, st);

@@ -1,15 +1,19 @@
 // Host-pointer entry points: one call = one SELECT_PARAMETERS surrogate step.
 //
 // The reference's boundary is a Python attribute protocol fed with NumPy arrays
-// (/root/reference/select_parameters.py:146-158, 282-294 -> /root/reference/point_selector.py:42-102, 197-207).
-// These two functions take exactly those arrays as plain host pointers, so a maintainer can bind the GPU path
+// (the reference's select_parameters.py:146-158, 282-294 -> point_selector.py:42-102, 197-207).
+// The functions of this file take exactly those arrays as plain host pointers, so a maintainer can bind the GPU path
 // with ctypes + NumPy alone (no PyTorch, no device-memory handling on the caller's side): device buffers are
 // allocated, filled, used and released inside the call, on the library's own stream.
-//   gpbo_select_next_host_f64  = update_surrogate() after the length scales are chosen + the acquisition arg-max
-//   gpbo_select_batch_host_f64 = the same step, then q points for parallel evaluation (not in the reference; batch.hip)
-//   gpbo_refine_host_f64       = the factorisation, then gradient refinement of given starts off the grid (refine.hip)
-//   gpbo_nlml_grid_host_f64    = tune_kernel()'s likelihood grid
-//   gpbo_nlml_grad_host_f64    = the likelihood and its gradient in the log length scales (ard="gradient")
+//   gpbo_select_next_host_f64      = update_surrogate() after the length scales are chosen + the acquisition arg-max
+//   gpbo_select_qei_host_f64       = the same step with q = 8 Monte-Carlo qEI as the acquisition
+//   gpbo_select_batch_host_f64     = the same step, then q points for parallel evaluation (not in the reference; batch.hip)
+//   gpbo_thompson_host_f64         = the factorisation, then q points as minimisers of posterior sample paths (thompson.hip)
+//   gpbo_refine_host_f64           = the factorisation, then gradient refinement of given starts off the grid (refine.hip)
+//   gpbo_nlml_grid_host_f64        = tune_kernel()'s likelihood grid (float32, the reference's det underflow)
+//   gpbo_nlml_grid_logdet_host_f64 = the same grid in fp64 with log det from the factor
+//   gpbo_nlml_grad_host_f64        = the likelihood and its gradient in the log length scales (ard="gradient")
+// Every factorising entry reads: own checks, own buffers, Surrogate (below), own calls, own read-backs.
 #include "gpbo_internal.h"
 
 #include <vector>
@@ -47,7 +51,45 @@ struct DeviceArena {
         return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) == hipSuccess;
     }
     bool sync() { return hipStreamSynchronize(stream) == hipSuccess; }
+    void *st() const { return reinterpret_cast<void *>(stream); }
 };
+
+// The factorised surrogate of one call: what every factorising entry opens with.  The sizes come first (they feed the entry's
+// own refusals, made before the arena exists); then two steps, because gpbo_select_next_host_f64 re-points X / y between the
+// upload and the factorisation.
+struct Surrogate {
+    const int64_t N, Np, wfact;   // observations, padded, the bytes the factorisation needs of `work`
+    const int32_t d;
+    double *X = nullptr, *y = nullptr, *K = nullptr, *U = nullptr, *alpha = nullptr;
+    int32_t *info = nullptr;
+    char *work = nullptr;   // the factorisation's workspace is dead once U and alpha exist: the entry's own calls reuse it
+    Surrogate(int64_t N_, int32_t d_) : N(N_), Np(gpbo_padded_n(N_)), wfact(gpbo_factorise_workspace_bytes(Np)), d(d_) {}
+    int64_t work_bytes(int64_t own) const { return wfact > own ? wfact : own; }   // (the entry adds its own slack)
+    // Step 1, after the entry's own allocations: the buffers, GPBO_ERR_WORKSPACE if ANY allocation of the call failed, and
+    // only then the first copies of the call: X and y.
+    int stage(DeviceArena &A, const double *hX, const double *hy, int64_t wbytes) {
+        X = A.alloc<double>(N * d), y = A.alloc<double>(N);
+        K = A.alloc<double>(Np * Np), U = A.alloc<double>(Np * Np), alpha = A.alloc<double>(Np);
+        info = A.alloc<int32_t>(1);
+        work = A.alloc<char>(wbytes);
+        if (!A.ok) return GPBO_ERR_WORKSPACE;
+        return A.h2d(X, hX, sizeof(double) * N * d) && A.h2d(y, hy, sizeof(double) * N) ? GPBO_OK : GPBO_ERR_LAUNCH;
+    }
+    // The factorisation, enqueued (gpbo_nlml_grad_host_f64 stops here: its kernel reads `info` on the device).
+    int factorise(DeviceArena &A, const double *ls, double jitter1, double jitter2) {
+        return gpbo_factorise_f64(X, y, N, d, ls, jitter1, jitter2, Np, K, U, alpha, info, work, wfact, A.st());
+    }
+    // Step 2: the factorisation, its info word on the host, the stream idle.  *info_out != 0: not positive definite - the
+    // entry fills its own outputs for that exit.
+    int factorise_sync(DeviceArena &A, const double *ls, double jitter1, double jitter2, int32_t *info_out) {
+        const int rc = factorise(A, ls, jitter1, jitter2);
+        if (rc != GPBO_OK) return rc;
+        return A.d2h(info_out, info, sizeof(int32_t)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+    }
+};
+
+// diagonal of cov_pred as the reference rounds it
+inline double prior_variance(double jitter1, double jitter2) { return (1.0 + jitter1) + jitter2; }
 
 }  // namespace
 
@@ -62,20 +104,15 @@ extern "C" int gpbo_select_next_host_f64(const double *X, const double *y, int64
     if (chunk == 0) chunk = (int64_t)1 << 17;
     if (!chunk_ok(chunk) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
     chunk = clamp_chunk(chunk, M);
-    const int64_t Np = gpbo_padded_n(N);
-    const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
+    Surrogate G(N, d);
+    const int64_t Np = G.Np;
     const int64_t wpost = gpbo_posterior_workspace_bytes(Np, chunk, M);
     if (wpost < 0) return GPBO_ERR_ARG;
 
     DeviceArena A;
     if (!A.ok) return GPBO_ERR_LAUNCH;
-    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N), *dXs = A.alloc<double>(M * d);   // (dX / dy: re-pointed below)
-    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
-    int32_t *dinfo = A.alloc<int32_t>(1);
+    double *dXs = A.alloc<double>(M * d);
     gpbo_result *dres = A.alloc<gpbo_result>(1);
-    // the factorisation workspace is dead once U and alpha exist: the posterior workspace reuses the allocation
-    const int64_t wbytes = (wfact > wpost ? wfact : wpost) + 256;
-    char *dwork = A.alloc<char>(wbytes);
     const bool dense = mu_out || sigma_out || acq_out;
     double *dmu = dense ? A.alloc<double>(M) : nullptr;
     double *dsig = dense ? A.alloc<double>(M) : nullptr;
@@ -105,25 +142,20 @@ extern "C" int gpbo_select_next_host_f64(const double *X, const double *y, int64
     double *dXp = fps_order ? A.alloc<double>(N * d) : nullptr;
     double *dyp = fps_order ? A.alloc<double>(N) : nullptr;
     char *dword = fps_order ? A.alloc<char>(word + 256) : nullptr;
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    void *st = reinterpret_cast<void *>(A.stream);
-
-    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N) ||
-        !A.h2d(dXs, Xs, sizeof(double) * M * d))
-        return GPBO_ERR_LAUNCH;
-    int rc;
+    int rc = G.stage(A, X, y, G.work_bytes(wpost) + 256);
+    if (rc != GPBO_OK) return rc;
+    if (!A.h2d(dXs, Xs, sizeof(double) * M * d)) return GPBO_ERR_LAUNCH;
     if (fps_order) {
         char *wo = reinterpret_cast<char *>(((uintptr_t)dword + 255) & ~(uintptr_t)255);
-        rc = gpbo_fps_order_f64(dX, dy, N, d, ls, J1, dperm, dXp, dyp, wo, word, st);
+        rc = gpbo_fps_order_f64(G.X, G.y, N, d, ls, J1, dperm, dXp, dyp, wo, word, A.st());
         if (rc != GPBO_OK) return rc;
-        dX = dXp;   // every later pass reads the observations in the factorisation's order
-        dy = dyp;
+        G.X = dXp;   // the factorisation and every later pass read the observations in this order
+        G.y = dyp;
     }
-    rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter1, jitter2, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    rc = G.factorise_sync(A, ls, jitter1, jitter2, info);
     if (rc != GPBO_OK) return rc;
-    if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
     if (cov_meas_out) {  // the reference's cov_meas attribute (point_selector.py:79), N x N without the padding
-        if (hipMemcpy2DAsync(cov_meas_out, sizeof(double) * N, dK, sizeof(double) * Np, sizeof(double) * N, (size_t)N,
+        if (hipMemcpy2DAsync(cov_meas_out, sizeof(double) * N, G.K, sizeof(double) * Np, sizeof(double) * N, (size_t)N,
                              hipMemcpyDeviceToHost, A.stream) != hipSuccess)
             return GPBO_ERR_LAUNCH;
     }
@@ -136,32 +168,31 @@ extern "C" int gpbo_select_next_host_f64(const double *X, const double *y, int64
         *result = {0.0, -1, 0, 0};
         return A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
     }
-    const double prior_var = (1.0 + jitter1) + jitter2;  // diagonal of cov_pred as the reference rounds it
+    const double prior_var = prior_variance(jitter1, jitter2);
     bool decided = false;
     if (bound_route) {
-        rc = gpbo_posterior_prefix_f64(dXs, M, dX, N, Np, d, ls, dU, dalpha, prior_var, acq_kind, p0, p1, 0, chunk, J1,
-                                       nullptr, nullptr, dub, dres, dwork, wpost, nullptr, st);
+        rc = gpbo_posterior_prefix_f64(dXs, M, G.X, N, Np, d, ls, G.U, G.alpha, prior_var, acq_kind, p0, p1, 0, chunk, J1,
+                                       nullptr, nullptr, dub, dres, G.work, wpost, nullptr, A.st());
         if (rc != GPBO_OK) return rc;
         gpbo_screen_stats stats;
         char *wr = reinterpret_cast<char *>(((uintptr_t)dresc + 255) & ~(uintptr_t)255);
         int64_t stride = M / 1024;
         if (stride < 1) stride = 1;
-        rc = gpbo_bound_select_f64(dXs, M, dub, dX, N, Np, d, ls, dU, dalpha, prior_var, acq_kind, p0, p1, 0, stride, bcap,
-                                   bchunk, J2, dres, &stats, wr, wresc, st);
+        rc = gpbo_bound_select_f64(dXs, M, dub, G.X, N, Np, d, ls, G.U, G.alpha, prior_var, acq_kind, p0, p1, 0, stride, bcap,
+                                   bchunk, J2, dres, &stats, wr, wresc, A.st());
         if (rc != GPBO_OK) return rc;
         decided = !stats.fallback;
     }
     if (!decided) {
-        rc = gpbo_posterior_acq_f64(dXs, M, dX, N, Np, d, ls, dU, dalpha, prior_var, acq_kind, p0, p1, diag_add, 0, chunk,
-                                    dmu, dsig, dacq, dres, dwork, wpost, nullptr, st);
+        rc = gpbo_posterior_acq_f64(dXs, M, G.X, N, Np, d, ls, G.U, G.alpha, prior_var, acq_kind, p0, p1, diag_add, 0, chunk,
+                                    dmu, dsig, dacq, dres, G.work, wpost, nullptr, A.st());
         if (rc != GPBO_OK) return rc;
     }
     bool okc = A.d2h(result, dres, sizeof(gpbo_result));
     if (mu_out) okc = okc && A.d2h(mu_out, dmu, sizeof(double) * M);
     if (sigma_out) okc = okc && A.d2h(sigma_out, dsig, sizeof(double) * M);
     if (acq_out) okc = okc && A.d2h(acq_out, dacq, sizeof(double) * M);
-    if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
-    return GPBO_OK;
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
 // q = 8 Monte-Carlo qEI on host arrays (same conventions as gpbo_select_next_host_f64; Z: [S x 8] base samples)
@@ -174,39 +205,31 @@ extern "C" int gpbo_select_qei_host_f64(const double *X, const double *y, int64_
     if (chunk == 0) chunk = (int64_t)1 << 15;
     if (!chunk_ok(chunk) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
     chunk = clamp_chunk(chunk, M);
-    const int64_t Np = gpbo_padded_n(N);
-    const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
+    Surrogate G(N, d);
+    const int64_t Np = G.Np;
     const int64_t wq = gpbo_qei_workspace_bytes(Np, chunk, M);
     if (wq < 0) return GPBO_ERR_ARG;
+
     DeviceArena A;
     if (!A.ok) return GPBO_ERR_LAUNCH;
-    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N), *dXs = A.alloc<double>(M * d);
-    double *dZ = A.alloc<double>((int64_t)S * 8);
-    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
-    int32_t *dinfo = A.alloc<int32_t>(1);
+    double *dXs = A.alloc<double>(M * d), *dZ = A.alloc<double>((int64_t)S * 8);
     gpbo_result *dres = A.alloc<gpbo_result>(1);
-    char *dwork = A.alloc<char>((wfact > wq ? wfact : wq) + 256);
     double *dq = qei_out ? A.alloc<double>(M / 8) : nullptr;
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    void *st = reinterpret_cast<void *>(A.stream);
-    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N) ||
-        !A.h2d(dXs, Xs, sizeof(double) * M * d) || !A.h2d(dZ, Z, sizeof(double) * S * 8))
-        return GPBO_ERR_LAUNCH;
-    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter1, jitter2, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    int rc = G.stage(A, X, y, G.work_bytes(wq) + 256);
     if (rc != GPBO_OK) return rc;
-    if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
-    if (*info != 0) {
+    if (!A.h2d(dXs, Xs, sizeof(double) * M * d) || !A.h2d(dZ, Z, sizeof(double) * S * 8)) return GPBO_ERR_LAUNCH;
+    rc = G.factorise_sync(A, ls, jitter1, jitter2, info);
+    if (rc != GPBO_OK) return rc;
+    if (*info != 0) {  // not positive definite: nothing to score
         *result = {0.0, -1, 0, 0};
         return GPBO_OK;
     }
-    const double prior_var = (1.0 + jitter1) + jitter2;
-    rc = gpbo_posterior_qei_f64(dXs, M, dX, N, Np, d, ls, dU, dalpha, prior_var, f_best, xi, dZ, S, 0, chunk, dq, dres,
-                                dwork, wq, nullptr, st);
+    rc = gpbo_posterior_qei_f64(dXs, M, G.X, N, Np, d, ls, G.U, G.alpha, prior_variance(jitter1, jitter2), f_best, xi, dZ, S, 0,
+                                chunk, dq, dres, G.work, wq, nullptr, A.st());
     if (rc != GPBO_OK) return rc;
     bool okc = A.d2h(result, dres, sizeof(gpbo_result));
     if (qei_out) okc = okc && A.d2h(qei_out, dq, sizeof(double) * (M / 8));
-    if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
-    return GPBO_OK;
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
 // Greedy q-point batch on host arrays: factorisation + the dense plain pass + gpbo_select_batch_f64 (csrc/batch.hip).
@@ -223,48 +246,41 @@ extern "C" int gpbo_select_batch_host_f64(const double *X, const double *y, int6
     if (chunk == 0) chunk = (int64_t)1 << 17;
     if (!chunk_ok(chunk) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
     chunk = clamp_chunk(chunk, M);
-    const int64_t Np = gpbo_padded_n(N);
-    const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
+    Surrogate G(N, d);
+    const int64_t Np = G.Np;
     const int64_t wpost = gpbo_posterior_workspace_bytes(Np, chunk, M);
     const int64_t wbatch = gpbo_batch_workspace_bytes(Np, M, q);
     if (wpost < 0 || wbatch < 0) return GPBO_ERR_ARG;
 
     DeviceArena A;
     if (!A.ok) return GPBO_ERR_LAUNCH;
-    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N), *dXs = A.alloc<double>(M * d);
-    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
-    int32_t *dinfo = A.alloc<int32_t>(1);
+    double *dXs = A.alloc<double>(M * d);
     gpbo_result *dres = A.alloc<gpbo_result>(1);
-    char *dwork = A.alloc<char>((wfact > wpost ? wfact : wpost) + 256);   // the factorisation's workspace is dead by the pass
-    char *dbatch = A.alloc<char>(wbatch);                                  // (hipMalloc: 256-byte aligned)
+    char *dbatch = A.alloc<char>(wbatch);   // (hipMalloc: 256-byte aligned)
     double *dmu = A.alloc<double>(M), *dsig = A.alloc<double>(M), *dval = A.alloc<double>(q);
     int64_t *didx = A.alloc<int64_t>(q);
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    void *st = reinterpret_cast<void *>(A.stream);
-    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N) ||
-        !A.h2d(dXs, Xs, sizeof(double) * M * d))
-        return GPBO_ERR_LAUNCH;
-    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter1, jitter2, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    int rc = G.stage(A, X, y, G.work_bytes(wpost) + 256);
     if (rc != GPBO_OK) return rc;
-    if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
+    if (!A.h2d(dXs, Xs, sizeof(double) * M * d)) return GPBO_ERR_LAUNCH;
+    rc = G.factorise_sync(A, ls, jitter1, jitter2, info);
+    if (rc != GPBO_OK) return rc;
     if (*info != 0) {  // not positive definite: nothing to select from
         *result = {0.0, -1, 0, 0};
         for (int32_t j = 0; j < q; ++j) idx_out[j] = -1;
         return GPBO_OK;
     }
-    const double prior_var = (1.0 + jitter1) + jitter2;
-    rc = gpbo_posterior_acq_f64(dXs, M, dX, N, Np, d, ls, dU, dalpha, prior_var, acq_kind, p0, p1, 0.0, 0, chunk, dmu, dsig,
-                                nullptr, dres, dwork, wpost, nullptr, st);
+    const double prior_var = prior_variance(jitter1, jitter2);
+    rc = gpbo_posterior_acq_f64(dXs, M, G.X, N, Np, d, ls, G.U, G.alpha, prior_var, acq_kind, p0, p1, 0.0, 0, chunk, dmu, dsig,
+                                nullptr, dres, G.work, wpost, nullptr, A.st());
     if (rc != GPBO_OK) return rc;
-    rc = gpbo_select_batch_f64(dXs, M, dX, N, Np, d, ls, dU, dalpha, jitter1, jitter2, prior_var, acq_kind, p0, p1, q, fantasy,
-                               lie, dmu, dsig, 0, didx, dval, dres, dinfo, dbatch, wbatch, st);
+    rc = gpbo_select_batch_f64(dXs, M, G.X, N, Np, d, ls, G.U, G.alpha, jitter1, jitter2, prior_var, acq_kind, p0, p1, q, fantasy,
+                               lie, dmu, dsig, 0, didx, dval, dres, G.info, dbatch, wbatch, A.st());
     if (rc != GPBO_OK) return rc;
-    bool okc = A.d2h(result, dres, sizeof(gpbo_result)) && A.d2h(info, dinfo, sizeof(int32_t)) &&
+    bool okc = A.d2h(result, dres, sizeof(gpbo_result)) && A.d2h(info, G.info, sizeof(int32_t)) &&
                A.d2h(idx_out, didx, sizeof(int64_t) * q) && A.d2h(val_out, dval, sizeof(double) * q);
     if (mu_out) okc = okc && A.d2h(mu_out, dmu, sizeof(double) * M);
     if (sigma_out) okc = okc && A.d2h(sigma_out, dsig, sizeof(double) * M);
-    if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
-    return GPBO_OK;
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
 // Thompson sampling on host arrays: factorisation + gpbo_thompson_weights_f64 + gpbo_thompson_paths_f64 (csrc/thompson.hip).
@@ -276,35 +292,28 @@ extern "C" int gpbo_thompson_host_f64(const double *X, const double *y, int64_t 
         return GPBO_ERR_ARG;
     if (N < 1 || M < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
     if (!(jitter1 + jitter2 >= 0.0)) return GPBO_ERR_ARG;
-    const int64_t Np = gpbo_padded_n(N);
-    const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
+    Surrogate G(N, d);
+    const int64_t Np = G.Np;
     const int64_t wwts = gpbo_thompson_weights_workspace_bytes(Np, F, S);
     const int64_t wpaths = gpbo_thompson_paths_workspace_bytes(Np, M, F, S);
     if (wwts < 0 || wpaths < 0) return GPBO_ERR_ARG;   // F, S, M out of range
 
     DeviceArena A;
     if (!A.ok) return GPBO_ERR_LAUNCH;
-    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N), *dXs = A.alloc<double>(M * d);
-    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
+    double *dXs = A.alloc<double>(M * d);
     double *dom = A.alloc<double>((int64_t)F * d), *dph = A.alloc<double>(F), *dW = A.alloc<double>((int64_t)S * F);
     double *dE = A.alloc<double>((int64_t)S * N), *dV = A.alloc<double>((int64_t)S * Np);
-    int32_t *dinfo = A.alloc<int32_t>(1);
-    // one workspace serves the three calls in turn (hipMalloc: 256-byte aligned)
-    int64_t wbytes = wfact > wwts ? wfact : wwts;
-    if (wpaths > wbytes) wbytes = wpaths;
-    char *dwork = A.alloc<char>(wbytes);
     int64_t *dout = A.alloc<int64_t>(3 * (int64_t)S);   // idx | val | nan
     double *df = f_out ? A.alloc<double>((int64_t)S * M) : nullptr;
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    void *st = reinterpret_cast<void *>(A.stream);
-    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N) ||
-        !A.h2d(dXs, Xs, sizeof(double) * M * d) || !A.h2d(dom, omega, sizeof(double) * F * d) ||
+    // one workspace serves the three calls in turn (hipMalloc: 256-byte aligned)
+    int rc = G.stage(A, X, y, G.work_bytes(wwts > wpaths ? wwts : wpaths));
+    if (rc != GPBO_OK) return rc;
+    if (!A.h2d(dXs, Xs, sizeof(double) * M * d) || !A.h2d(dom, omega, sizeof(double) * F * d) ||
         !A.h2d(dph, phase, sizeof(double) * F) || !A.h2d(dW, W, sizeof(double) * S * F) ||
         !A.h2d(dE, E, sizeof(double) * S * N))
         return GPBO_ERR_LAUNCH;
-    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter1, jitter2, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    rc = G.factorise_sync(A, ls, jitter1, jitter2, info);
     if (rc != GPBO_OK) return rc;
-    if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
     if (*info != 0) {  // not positive definite: no posterior to sample from
         for (int32_t s = 0; s < S; ++s) {
             idx_out[s] = -1;
@@ -313,16 +322,16 @@ extern "C" int gpbo_thompson_host_f64(const double *X, const double *y, int64_t 
         }
         return GPBO_OK;
     }
-    rc = gpbo_thompson_weights_f64(dX, dy, N, Np, d, ls, dU, jitter1, jitter2, dom, dph, dW, dE, F, S, dV, dwork, wwts, st);
+    rc = gpbo_thompson_weights_f64(G.X, G.y, N, Np, d, ls, G.U, jitter1, jitter2, dom, dph, dW, dE, F, S, dV, G.work, wwts,
+                                   A.st());
     if (rc != GPBO_OK) return rc;
-    rc = gpbo_thompson_paths_f64(dXs, M, dX, N, Np, d, ls, dom, dph, dW, dV, F, S, 0, df, M, dout,
-                                 reinterpret_cast<double *>(dout + S), dout + 2 * (int64_t)S, dwork, wpaths, st);
+    rc = gpbo_thompson_paths_f64(dXs, M, G.X, N, Np, d, ls, dom, dph, dW, dV, F, S, 0, df, M, dout,
+                                 reinterpret_cast<double *>(dout + S), dout + 2 * (int64_t)S, G.work, wpaths, A.st());
     if (rc != GPBO_OK) return rc;
     bool okc = A.d2h(idx_out, dout, sizeof(int64_t) * S) && A.d2h(val_out, dout + S, sizeof(double) * S) &&
                A.d2h(nan_out, dout + 2 * (int64_t)S, sizeof(int64_t) * S);
     if (f_out) okc = okc && A.d2h(f_out, df, sizeof(double) * S * M);
-    if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
-    return GPBO_OK;
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
 // Off-grid refinement on host arrays: factorisation + gpbo_refine_f64 (csrc/refine.hip).
@@ -337,42 +346,35 @@ extern "C" int gpbo_refine_host_f64(const double *X, const double *y, int64_t N,
     if (iters < 0 || iters > 1000 || !(step0 > 0.0) || !(step0 - step0 == 0.0)) return GPBO_ERR_ARG;
     for (int k = 0; k < d; ++k)
         if (!(lower[k] - lower[k] == 0.0) || !(upper[k] - upper[k] == 0.0) || lower[k] > upper[k]) return GPBO_ERR_ARG;
-    const int64_t Np = gpbo_padded_n(N);
-    const int64_t wfact = gpbo_factorise_workspace_bytes(Np);
+    Surrogate G(N, d);
+    const int64_t Np = G.Np;
     const int64_t wref = gpbo_refine_workspace_bytes(Np, P);
     if (wref < 0) return GPBO_ERR_ARG;
 
     DeviceArena A;
     if (!A.ok) return GPBO_ERR_LAUNCH;
-    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N), *dXq = A.alloc<double>(P * d);
-    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
-    int32_t *dinfo = A.alloc<int32_t>(1);
+    double *dXq = A.alloc<double>(P * d);
     gpbo_result *dres = A.alloc<gpbo_result>(1);
-    char *dwork = A.alloc<char>(wfact > wref ? wfact : wref);   // the factorisation's workspace is dead by the refinement
     double *dacq = A.alloc<double>(P), *dacq0 = A.alloc<double>(P), *dpg = A.alloc<double>(P);
     int32_t *dacc = A.alloc<int32_t>(P);
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    void *st = reinterpret_cast<void *>(A.stream);
-    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N) || !A.h2d(dXq, Xq, sizeof(double) * P * d))
-        return GPBO_ERR_LAUNCH;
-    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter1, jitter2, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    int rc = G.stage(A, X, y, G.work_bytes(wref));   // (hipMalloc: 256-byte aligned)
     if (rc != GPBO_OK) return rc;
-    if (!A.d2h(info, dinfo, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
+    if (!A.h2d(dXq, Xq, sizeof(double) * P * d)) return GPBO_ERR_LAUNCH;
+    rc = G.factorise_sync(A, ls, jitter1, jitter2, info);
+    if (rc != GPBO_OK) return rc;
     if (*info != 0) {  // not positive definite: nothing to refine on
         *result = {0.0, -1, 0, 0};
         return GPBO_OK;
     }
-    const double prior_var = (1.0 + jitter1) + jitter2;
-    rc = gpbo_refine_f64(dXq, P, lower, upper, dX, N, Np, d, ls, dU, dalpha, prior_var, acq_kind, p0, p1, iters, step0, dacq,
-                         dacq0, dacc, dpg, dres, dwork, wref, st);
+    rc = gpbo_refine_f64(dXq, P, lower, upper, G.X, N, Np, d, ls, G.U, G.alpha, prior_variance(jitter1, jitter2), acq_kind, p0,
+                         p1, iters, step0, dacq, dacq0, dacc, dpg, dres, G.work, wref, A.st());
     if (rc != GPBO_OK) return rc;
     bool okc = A.d2h(result, dres, sizeof(gpbo_result)) && A.d2h(Xq, dXq, sizeof(double) * P * d);
     if (acq_out) okc = okc && A.d2h(acq_out, dacq, sizeof(double) * P);
     if (acq0_out) okc = okc && A.d2h(acq0_out, dacq0, sizeof(double) * P);
     if (accepted_out) okc = okc && A.d2h(accepted_out, dacc, sizeof(int32_t) * P);
     if (pg_out) okc = okc && A.d2h(pg_out, dpg, sizeof(double) * P);
-    if (!okc || !A.sync()) return GPBO_ERR_LAUNCH;
-    return GPBO_OK;
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
 // mode 0: the reference's float32 likelihood; mode 1: fp64, log det from the factor (gpbo.h)
@@ -387,7 +389,6 @@ static int nlml_grid_host(const double *X, const double *y, int64_t N, int32_t d
     const size_t osz = mode ? sizeof(double) : sizeof(float);
     double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N);
     char *dout = A.alloc<char>((int64_t)(G * osz));
-    void *st = reinterpret_cast<void *>(A.stream);
     if (!A.ok) return GPBO_ERR_WORKSPACE;
     if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N)) return GPBO_ERR_LAUNCH;
     int rc;
@@ -395,20 +396,19 @@ static int nlml_grid_host(const double *X, const double *y, int64_t N, int32_t d
     if (!A.ok) return GPBO_ERR_WORKSPACE;
     if (!A.h2d(dcells, ls_cells, sizeof(double) * G * d)) return GPBO_ERR_LAUNCH;
     if (N <= gpbo_nlml_grid_wave_max_n()) {   // the wave-per-cell kernel (the same switch as the tensor-resident binding)
-        rc = mode ? gpbo_nlml_grid_wave_logdet_f64(dX, dy, N, d, dcells, G, jitter, reinterpret_cast<double *>(dout), st)
-                  : gpbo_nlml_grid_wave_f64(dX, dy, N, d, dcells, G, jitter, reinterpret_cast<float *>(dout), st);
+        rc = mode ? gpbo_nlml_grid_wave_logdet_f64(dX, dy, N, d, dcells, G, jitter, reinterpret_cast<double *>(dout), A.st())
+                  : gpbo_nlml_grid_wave_f64(dX, dy, N, d, dcells, G, jitter, reinterpret_cast<float *>(dout), A.st());
         if (rc != GPBO_OK) return rc;
     } else {         // one persistent workgroup per cell, the whole factorisation in one launch
         const int64_t wb = gpbo_nlml_grid_batched_workspace_bytes(N, G);
         if (wb < 0) return GPBO_ERR_ARG;
         char *dwork = A.alloc<char>(wb);
         if (!A.ok) return GPBO_ERR_WORKSPACE;
-        rc = mode ? gpbo_nlml_grid_batched_logdet_f64(dX, dy, N, d, dcells, G, jitter, reinterpret_cast<double *>(dout), dwork, wb, st)
-                  : gpbo_nlml_grid_batched_f64(dX, dy, N, d, dcells, G, jitter, reinterpret_cast<float *>(dout), dwork, wb, st);
+        rc = mode ? gpbo_nlml_grid_batched_logdet_f64(dX, dy, N, d, dcells, G, jitter, reinterpret_cast<double *>(dout), dwork, wb, A.st())
+                  : gpbo_nlml_grid_batched_f64(dX, dy, N, d, dcells, G, jitter, reinterpret_cast<float *>(dout), dwork, wb, A.st());
         if (rc != GPBO_OK) return rc;
     }
-    if (!A.d2h(out, dout, G * osz) || !A.sync()) return GPBO_ERR_LAUNCH;
-    return GPBO_OK;
+    return A.d2h(out, dout, G * osz) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
 extern "C" int gpbo_nlml_grid_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls_cells,
@@ -424,23 +424,19 @@ extern "C" int gpbo_nlml_grid_logdet_host_f64(const double *X, const double *y, 
 extern "C" int gpbo_nlml_grad_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls,
                                        double jitter, double *out) {
     if (!X || !y || !ls || !out || N < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
-    const int64_t Np = gpbo_padded_n(N);
-    const int64_t wfact = gpbo_factorise_workspace_bytes(Np), wgrad = gpbo_nlml_grad_workspace_bytes(Np, d);
+    Surrogate G(N, d);
+    const int64_t wgrad = gpbo_nlml_grad_workspace_bytes(G.Np, d);
     if (wgrad < 0) return GPBO_ERR_ARG;
+
     DeviceArena A;
     if (!A.ok) return GPBO_ERR_LAUNCH;
-    double *dX = A.alloc<double>(N * d), *dy = A.alloc<double>(N);
-    double *dK = A.alloc<double>(Np * Np), *dU = A.alloc<double>(Np * Np), *dalpha = A.alloc<double>(Np);
     double *dout = A.alloc<double>(1 + d);
-    int32_t *dinfo = A.alloc<int32_t>(1);
-    char *dwork = A.alloc<char>(wfact), *dwg = A.alloc<char>(wgrad);
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    void *st = reinterpret_cast<void *>(A.stream);
-    if (!A.h2d(dX, X, sizeof(double) * N * d) || !A.h2d(dy, y, sizeof(double) * N)) return GPBO_ERR_LAUNCH;
-    int rc = gpbo_factorise_f64(dX, dy, N, d, ls, jitter, 0.0, Np, dK, dU, dalpha, dinfo, dwork, wfact, st);
+    char *dwg = A.alloc<char>(wgrad);   // (the gradient has a workspace of its own)
+    int rc = G.stage(A, X, y, G.wfact);
     if (rc != GPBO_OK) return rc;
-    rc = gpbo_nlml_grad_f64(dU, dalpha, dy, dX, N, Np, d, ls, dinfo, dout, dwg, wgrad, st);
+    rc = G.factorise(A, ls, jitter, 0.0);   // info stays on the device: the gradient kernel answers NaN for it
     if (rc != GPBO_OK) return rc;
-    if (!A.d2h(out, dout, sizeof(double) * (1 + d)) || !A.sync()) return GPBO_ERR_LAUNCH;
-    return GPBO_OK;
+    rc = gpbo_nlml_grad_f64(G.U, G.alpha, G.y, G.X, N, G.Np, d, ls, G.info, dout, dwg, wgrad, A.st());
+    if (rc != GPBO_OK) return rc;
+    return A.d2h(out, dout, sizeof(double) * (1 + d)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }

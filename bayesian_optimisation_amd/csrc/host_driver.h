@@ -1,6 +1,7 @@
 // Host-side plumbing shared by the scoring drivers (sigma_acq.hip, posterior_f32.hip, ozaki.hip, rescore.hip, host_api.hip)
 // and the launchers below them: size arithmetic, the argument refusals, environment switches, the profile-slot bookkeeping,
-// the dense outputs of a chunk, the model / acquisition views.  Host only: no device code in this file.
+// the dense outputs of a chunk, the model / acquisition views, the length-scale scalings, the dispatch over d.
+// Host only: no device code in this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,6 +32,43 @@ inline bool length_scales_ok(const double *ls, int d) {
         if (!(ls[k] > 0.0)) return false;
     return true;
 }
+
+// ---- the length scales as the kernels take them: il2[k] = 1 / ls_k^2 (the arithmetic of kxx_kernel), isc[k] = 1 / (ls_k sqrt 2)
+// (the arithmetic of kstar_mu_kernel), k < d; either may be null.  EXACTLY these expressions: the values feed kernels whose
+// outputs are compared bit for bit.  The entries k >= d are the caller's.  false: a length scale that is not positive.
+inline bool length_scale_scalings(const double *ls_host, int d, double *il2, double *isc) {
+    for (int k = 0; k < d; ++k) {
+        const double l = ls_host[k];
+        if (!(l > 0.0)) return false;
+        if (il2) il2[k] = 1.0 / (l * l);
+        if (isc) isc[k] = 1.0 / (l * 1.4142135623730950488);
+    }
+    return true;
+}
+
+// ---- one kernel instance per feature count: CALL(1) ... CALL(GPBO_MAX_D) by the run-time d, inside a function that returns a
+// status.  (kernel_build.hip, ozaki.hip and kstar_mfma.hip join when their counter passes are next re-collected.)
+#define GPBO_FOR_D(d, CALL)           \
+    switch ((d)) {                    \
+        case 1: CALL(1); break;       \
+        case 2: CALL(2); break;       \
+        case 3: CALL(3); break;       \
+        case 4: CALL(4); break;       \
+        case 5: CALL(5); break;       \
+        case 6: CALL(6); break;       \
+        case 7: CALL(7); break;       \
+        case 8: CALL(8); break;       \
+        case 9: CALL(9); break;       \
+        case 10: CALL(10); break;     \
+        case 11: CALL(11); break;     \
+        case 12: CALL(12); break;     \
+        case 13: CALL(13); break;     \
+        case 14: CALL(14); break;     \
+        case 15: CALL(15); break;     \
+        case 16: CALL(16); break;     \
+        default: return GPBO_ERR_ARG; \
+    }
+static_assert(GPBO_MAX_D == 16, "GPBO_FOR_D lists the feature counts 1 ... GPBO_MAX_D");
 
 // ---- environment switches (include/gpbo.h lists them; a caller that wants one read per process keeps it in a static const)
 inline const char *env_str(const char *name) { return getenv(name); }

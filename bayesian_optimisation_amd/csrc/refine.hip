@@ -353,13 +353,11 @@ bool make_box(const double *ls_host, const double *lower, const double *upper, i
         box->lo[k] = box->hi[k] = 0.0;
         box->ls[k] = box->l2[k] = box->il2[k] = box->isc[k] = 1.0;
     }
+    if (!length_scale_scalings(ls_host, d, box->il2, box->isc)) return false;
     for (int k = 0; k < d; ++k) {
         const double l = ls_host[k];
-        if (!(l > 0.0)) return false;
         box->ls[k] = l;
         box->l2[k] = l * l;
-        box->il2[k] = 1.0 / (l * l);
-        box->isc[k] = 1.0 / (l * 1.4142135623730950488);
         if (lower) {
             if (!std::isfinite(lower[k]) || !std::isfinite(upper[k]) || lower[k] > upper[k]) return false;
             box->lo[k] = lower[k];
@@ -388,38 +386,17 @@ int evaluate(const Eval &e, const double *pts, int mode, double step0, RefinePoi
     hipLaunchKernelGGL(refine_grad_step_kernel<DD>, dim3((unsigned)e.P), dim3(256), 0, e.st, e.Ks, e.Vt, e.Wt, e.Np, e.alpha,  \
                        e.X, e.N, pts, e.box, e.prior_var, e.kind, e.p0, e.p1, mode, step0, rec, trial, mu_out, sigma_out,     \
                        acq_out, dmu_out, dsigma_out, dacq_out)
-#define DISPATCH(WHAT)                                                                                                      \
-    switch (e.d) {                                                                                                          \
-        case 1: WHAT(1); break;                                                                                             \
-        case 2: WHAT(2); break;                                                                                             \
-        case 3: WHAT(3); break;                                                                                             \
-        case 4: WHAT(4); break;                                                                                             \
-        case 5: WHAT(5); break;                                                                                             \
-        case 6: WHAT(6); break;                                                                                             \
-        case 7: WHAT(7); break;                                                                                             \
-        case 8: WHAT(8); break;                                                                                             \
-        case 9: WHAT(9); break;                                                                                             \
-        case 10: WHAT(10); break;                                                                                           \
-        case 11: WHAT(11); break;                                                                                           \
-        case 12: WHAT(12); break;                                                                                           \
-        case 13: WHAT(13); break;                                                                                           \
-        case 14: WHAT(14); break;                                                                                           \
-        case 15: WHAT(15); break;                                                                                           \
-        case 16: WHAT(16); break;                                                                                           \
-        default: return GPBO_ERR_ARG;                                                                                       \
-    }
-    DISPATCH(KS)
+    GPBO_FOR_D(e.d, KS)
     GPBO_CHECK_LAUNCH();
     // U is upper triangular; both products run dense (the GEMM's triangular skips are for the lower case)
     int rc = gpbo_gemm_launch_tri(0, e.Pp, e.Np, e.Np, 1.0, e.Ks, e.Np, 0, e.U, e.Np, 0, 0.0, e.Vt, e.Np, 0, 1, 0, 0, e.st);
     if (rc != GPBO_OK) return rc;
     rc = gpbo_gemm_launch_tri(1, e.Pp, e.Np, e.Np, 1.0, e.Vt, e.Np, 0, e.U, e.Np, 0, 0.0, e.Wt, e.Np, 0, 1, 0, 0, e.st);
     if (rc != GPBO_OK) return rc;
-    DISPATCH(GS)
+    GPBO_FOR_D(e.d, GS)
     GPBO_CHECK_LAUNCH();
 #undef KS
 #undef GS
-#undef DISPATCH
     return GPBO_OK;
 }
 

@@ -331,10 +331,8 @@ int run_paths(const double *Xs, int64_t M, const double *X, int64_t N, int64_t N
     unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
     TsScale sc;
     for (int k = 0; k < GPBO_MAX_D; ++k) sc.isc[k] = sc.tl[k] = 1.0;
-    for (int k = 0; k < d; ++k) {
-        sc.isc[k] = 1.0 / (ls_host[k] * 1.4142135623730950488);
-        sc.tl[k] = 6.283185307179586477 * ls_host[k];
-    }
+    (void)length_scale_scalings(ls_host, d, nullptr, sc.isc);   // (cannot refuse: the arguments have been checked)
+    for (int k = 0; k < d; ++k) sc.tl[k] = 6.283185307179586477 * ls_host[k];
     const int Sp = (int)L.Sp, G = group_of(S);
     const int Nk = V ? (int)N : 0;
     if (V) {
@@ -352,25 +350,7 @@ int run_paths(const double *Xs, int64_t M, const double *X, int64_t N, int64_t N
 #define CALL(DD)                                                                                                              \
     launch_paths<DD>(G, grid, st, Xs, M, Xsc, Nk, sc, Vt, Om, phase, Wt, (int)F, (int)S, Sp, amp, idx_offset, f_out, ldf,        \
                      want_argmax ? part_val : nullptr, part_idx, L.nblk, nan_count)
-    switch (d) {   // (GPBO_DISPATCH_D of kernel_build.hip is local to that unit)
-        case 1: CALL(1); break;
-        case 2: CALL(2); break;
-        case 3: CALL(3); break;
-        case 4: CALL(4); break;
-        case 5: CALL(5); break;
-        case 6: CALL(6); break;
-        case 7: CALL(7); break;
-        case 8: CALL(8); break;
-        case 9: CALL(9); break;
-        case 10: CALL(10); break;
-        case 11: CALL(11); break;
-        case 12: CALL(12); break;
-        case 13: CALL(13); break;
-        case 14: CALL(14); break;
-        case 15: CALL(15); break;
-        case 16: CALL(16); break;
-        default: return GPBO_ERR_ARG;
-    }
+    GPBO_FOR_D(d, CALL)
 #undef CALL
     GPBO_CHECK_LAUNCH();
     if (!want_argmax) return GPBO_OK;

@@ -108,10 +108,7 @@ extern "C" int gpbo_append_f64(double *X, double *y, int64_t N, int32_t d, const
     if (work_bytes < gpbo_append_workspace_bytes(Np)) return GPBO_ERR_WORKSPACE;
     LsInv2 ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.il2[k] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        if (!(ls_host[k] > 0.0)) return GPBO_ERR_ARG;
-        ls.il2[k] = 1.0 / (ls_host[k] * ls_host[k]);
-    }
+    if (!length_scale_scalings(ls_host, d, ls.il2, nullptr)) return GPBO_ERR_ARG;
     hipStream_t st = gpbo_stream(stream);
     double *kvec = reinterpret_cast<double *>(work);
     double *l = kvec + Np;

@@ -19,6 +19,8 @@ from . import _lib
 
 JITTER_KERNEL = 1e-4    # point_selector.py:193
 JITTER_ASSEMBLY = 1e-6  # point_selector.py:78-79
+# the IndexError of an acquisition with NaN in it: the reference's own failure, in NumPy's words (point_selector.py:207)
+NAN_ACQUISITION = "index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)"
 PRIOR_VAR = (1.0 + JITTER_KERNEL) + JITTER_ASSEMBLY  # diagonal of cov_pred as the reference rounds it
 
 DEFAULT_CHUNK = 1 << 17
@@ -952,7 +954,7 @@ class DeviceGP:
         res = ThompsonResult(indices=h[:S].numpy().copy(), values=h[S: 2 * S].view(torch.float64).numpy().copy(),
                              nan_counts=h[2 * S:].numpy().copy(), f=f)
         if res.nan_counts.any():
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+            raise IndexError(NAN_ACQUISITION)
         return res
 
     def select_thompson(self, Xs, q: int, n_paths: Optional[int] = None, n_features: int = 2048, seed: int = 0,
@@ -1049,7 +1051,7 @@ class DeviceGP:
             raise ValueError("give both lower and upper, or neither")
         s = self.score(Xsd, acquisition=acquisition, explore=explore, f_best=f_best, xi=xi, dense=True)
         if s.nan_count > 0:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+            raise IndexError(NAN_ACQUISITION)
         with torch.cuda.device(self.device):
             order = torch.sort(s.acq, descending=True, stable=True).indices[:n_starts]   # plumbing
             starts = Xsd[order].contiguous()

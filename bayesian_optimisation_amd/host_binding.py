@@ -1,7 +1,7 @@
 """The drop-in class bound through the host-pointer C entry points only: NumPy + ctypes, no PyTorch.
 
 This is the ctypes stub a maintainer of the reference would write against include/gpbo.h
-(gpbo_select_next_host_f64, gpbo_nlml_grid_host_f64, gpbo_nlml_grad_host_f64): the arrays the reference already holds
+(the gpbo_*_host_f64 entry points): the arrays the reference already holds
 (/root/reference/select_parameters.py:149-153, 285-289) go in as host pointers, `mean_func`, `cov_func`,
 `acq_func_eval` and the selected index come back.  Every call allocates and frees its device buffers inside the
 library, which costs a few milliseconds per step against the tensor-resident `PointSelector`; the numbers are the
@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, acq_params, fantasy_params, refine_box, refine_params
+from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, NAN_ACQUISITION, acq_params, fantasy_params, refine_box, refine_params
 from .point_selector import PointSelector
 
 
@@ -28,6 +28,32 @@ def _f64(a):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else C.c_void_p(0)
+
+
+def _problem(X, y, ls, Xs=None):
+    """(X, y, ls, N, d) - with candidates (X, y, ls, Xs, N, d, M) - as contiguous fp64 arrays: the one shape check of the
+    binding, made before anything touches the device."""
+    X, y = _f64(X), _f64(y).reshape(-1)
+    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
+    Xs = None if Xs is None else _f64(Xs)
+    ok = X.ndim == 2 and ls.size == X.shape[1] and y.size == X.shape[0]
+    if not ok or (Xs is not None and (Xs.ndim != 2 or Xs.shape[1] != X.shape[1])):
+        raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
+    return (X, y, ls, *X.shape) if Xs is None else (X, y, ls, Xs, *X.shape, Xs.shape[0])
+
+
+class _Result:
+    """The gpbo_result record and the info word a host entry writes, and their decoding."""
+
+    def __init__(self):
+        self._res = (C.c_int64 * 4)()
+        self._info = C.c_int32(0)
+        self.res_ptr = C.cast(self._res, C.c_void_p)
+        self.info_ptr = C.cast(C.pointer(self._info), C.c_void_p)
+
+    def decode(self) -> dict:
+        best_val = float(np.frombuffer(self._res, dtype=np.float64, count=1)[0])
+        return dict(best_val=best_val, best_idx=int(self._res[1]), nan_count=int(self._res[2]), info=int(self._info.value))
 
 
 def nlml_grid(X, y, ls_cells, jitter: float = JITTER_KERNEL, lib=None, likelihood: str = "reference") -> np.ndarray:
@@ -52,11 +78,7 @@ def nlml_and_grad(X, y, ls, jitter: float = JITTER_KERNEL, lib=None):
     """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I on host arrays: gpbo_nlml_grad_host_f64 (factorisation and
     gradient kernel in one call).  NaN in every output when K is not positive definite.  d <= 16."""
     lib = lib or _lib.load()
-    X, y = _f64(X), _f64(y).reshape(-1)
-    N, d = X.shape
-    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
-    if ls.size != d or y.size != N:
-        raise ValueError("shapes: X (N, d), y (N,), ls (d,)")
+    X, y, ls, N, d = _problem(X, y, ls)
     out = np.empty(1 + d)
     _lib.note_hip_use()
     _lib.check(lib.gpbo_nlml_grad_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), float(jitter), _ptr(out)),
@@ -68,28 +90,37 @@ def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_
                 dense: bool = True, want_cov_meas: bool = False, chunk: int = 0, lib=None) -> dict:
     """One surrogate step on host arrays.  Returns dict(best_val, best_idx, nan_count, info, mu, sigma, acq, cov_meas)."""
     lib = lib or _lib.load()
-    X, y, Xs = _f64(X), _f64(y).reshape(-1), _f64(Xs)
-    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
-    N, d = X.shape
-    M = Xs.shape[0]
-    if Xs.shape[1] != d or ls.size != d or y.size != N:
-        raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
+    X, y, ls, Xs, N, d, M = _problem(X, y, ls, Xs)
     kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
     mu = np.empty(M) if dense else None
     sigma = np.empty(M) if dense else None
     acq = np.empty(M) if dense else None
     cov = np.empty((N, N)) if want_cov_meas else None
-    res = (C.c_int64 * 4)()
-    info = C.c_int32(0)
+    out = _Result()
     diag_add = JITTER_KERNEL if Xs.shape == X.shape else 0.0          # point_selector.py:173 shape-coincidence quirk
     _lib.note_hip_use()
     st = lib.gpbo_select_next_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M,
                                        kind, p0, p1, diag_add, int(chunk), _ptr(mu), _ptr(sigma), _ptr(acq), _ptr(cov),
-                                       C.cast(res, C.c_void_p), C.cast(C.pointer(info), C.c_void_p))
+                                       out.res_ptr, out.info_ptr)
     _lib.check(st, "gpbo_select_next_host_f64")
-    best_val = float(np.frombuffer(res, dtype=np.float64, count=1)[0])
-    return dict(best_val=best_val, best_idx=int(res[1]), nan_count=int(res[2]), info=int(info.value), mu=mu, sigma=sigma,
-                acq=acq, cov_meas=cov)
+    return dict(out.decode(), mu=mu, sigma=sigma, acq=acq, cov_meas=cov)
+
+
+def select_qei(X, y, ls, Xs, Z, f_best: float, xi: float = 0.0, chunk: int = 0, lib=None) -> dict:
+    """q = 8 Monte-Carlo Expected Improvement on host arrays (gpbo_select_qei_host_f64): the candidates in consecutive
+    batches of 8 (M a multiple of 8), Z [S x 8] the base samples.  Returns dict(best_val, best_idx: the first batch with
+    the largest qEI, nan_count, info, qei [M / 8])."""
+    lib = lib or _lib.load()
+    X, y, ls, Xs, N, d, M = _problem(X, y, ls, Xs)
+    Z = _f64(Z)
+    qei = np.empty(M // 8)
+    out = _Result()
+    _lib.note_hip_use()
+    st = lib.gpbo_select_qei_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M,
+                                      float(f_best), float(xi), _ptr(Z), len(Z), int(chunk), _ptr(qei), out.res_ptr,
+                                      out.info_ptr)
+    _lib.check(st, "gpbo_select_qei_host_f64")
+    return dict(out.decode(), qei=qei)
 
 
 def select_batch(X, y, ls, Xs, q: int, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
@@ -97,12 +128,7 @@ def select_batch(X, y, ls, Xs, q: int, acquisition: str = "lcb", explore: float 
     """Greedy q-point batch on host arrays (gpbo_select_batch_host_f64).  Returns dict(indices, values, nan_count, info,
     mu, sigma); mu / sigma (dense=True) are the posterior the q-th member was chosen from."""
     lib = lib or _lib.load()
-    X, y, Xs = _f64(X), _f64(y).reshape(-1), _f64(Xs)
-    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
-    N, d = X.shape
-    M = Xs.shape[0]
-    if Xs.shape[1] != d or ls.size != d or y.size != N:
-        raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
+    X, y, ls, Xs, N, d, M = _problem(X, y, ls, Xs)
     q = int(q)
     if d > _lib.MAX_D or not 1 <= q <= min(_lib.BATCH_MAX_Q, M):
         raise ValueError(f"select_batch needs d <= {_lib.MAX_D} and q in [1, min({_lib.BATCH_MAX_Q}, M = {M})]")
@@ -111,14 +137,14 @@ def select_batch(X, y, ls, Xs, q: int, acquisition: str = "lcb", explore: float 
     idx, val = np.full(q, -1, dtype=np.int64), np.full(q, np.nan)
     mu = np.empty(M) if dense else None
     sigma = np.empty(M) if dense else None
-    res = (C.c_int64 * 4)()
-    info = C.c_int32(0)
+    out = _Result()
     _lib.note_hip_use()
     st = lib.gpbo_select_batch_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M, kind,
                                         p0, p1, int(chunk), q, fkind, fl, _ptr(idx), _ptr(val), _ptr(mu), _ptr(sigma),
-                                        C.cast(res, C.c_void_p), C.cast(C.pointer(info), C.c_void_p))
+                                        out.res_ptr, out.info_ptr)
     _lib.check(st, "gpbo_select_batch_host_f64")
-    return dict(indices=idx, values=val, nan_count=int(res[2]), info=int(info.value), mu=mu, sigma=sigma)
+    r = out.decode()
+    return dict(indices=idx, values=val, nan_count=r["nan_count"], info=r["info"], mu=mu, sigma=sigma)
 
 
 def select_thompson(X, y, ls, Xs, q: int, n_paths=None, n_features: int = 2048, seed: int = 0, dense: bool = False,
@@ -129,27 +155,21 @@ def select_thompson(X, y, ls, Xs, q: int, n_paths=None, n_features: int = 2048, 
     all_values, nan_counts [n_paths], info, f [n_paths x M] with dense=True)."""
     from .thompson import first_distinct, select_params, thompson_draws
 
-    X, y, Xs = _f64(X), _f64(y).reshape(-1), _f64(Xs)
-    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
-    if X.ndim != 2 or Xs.ndim != 2:
-        raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
-    N, d = X.shape
-    M = Xs.shape[0]
-    if Xs.shape[1] != d or ls.size != d or y.size != N:
-        raise ValueError("shapes: X (N, d), y (N,), ls (d,), Xs (M, d)")
+    X, y, ls, Xs, N, d, M = _problem(X, y, ls, Xs)
     q, S, F, seed = select_params(q, n_paths, n_features, seed, M=M, d=d)
     lib = lib or _lib.load()
     omega, phase, W, E = (_f64(a) for a in thompson_draws(d, F, S, N, seed))
     idx, val, nan = np.full(S, -1, dtype=np.int64), np.full(S, np.nan), np.zeros(S, dtype=np.int64)
     f = np.empty((S, M)) if dense else None
-    info = C.c_int32(0)
+    out = _Result()
     _lib.note_hip_use()
     st = lib.gpbo_thompson_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M, _ptr(omega),
                                     _ptr(phase), _ptr(W), _ptr(E), F, S, _ptr(idx), _ptr(val), _ptr(nan), _ptr(f),
-                                    C.cast(C.pointer(info), C.c_void_p))
+                                    out.info_ptr)
     _lib.check(st, "gpbo_thompson_host_f64")
     keep = first_distinct(idx, q)
-    return dict(indices=idx[keep], values=val[keep], all_indices=idx, all_values=val, nan_counts=nan, info=int(info.value), f=f)
+    return dict(indices=idx[keep], values=val[keep], all_indices=idx, all_values=val, nan_counts=nan, info=out.decode()["info"],
+                f=f)
 
 
 def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
@@ -157,27 +177,22 @@ def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: fl
     """Off-grid refinement on host arrays (gpbo_refine_host_f64: factorisation and refinement in one call).  Returns
     dict(x [P x d], acq, acq0, accepted, pg, best, best_val, nan_count, info)."""
     lib = lib or _lib.load()
-    X, y = _f64(X), _f64(y).reshape(-1)
-    ls = _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
-    N, d = X.shape
+    X, y, ls, N, d = _problem(X, y, ls)
     x = np.array(np.asarray(starts, dtype=np.float64).reshape(-1, d), dtype=np.float64, order="C")   # a copy: in / out
     P = x.shape[0]
-    if ls.size != d or y.size != N:
-        raise ValueError("shapes: X (N, d), y (N,), ls (d,), starts (P, d)")
     iters, step0 = refine_params(P, d, iters, step0)
     lo, hi = refine_box(lower, upper, d)
     kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
     acq, acq0, pg, accepted = np.empty(P), np.empty(P), np.empty(P), np.empty(P, dtype=np.int32)
-    res = (C.c_int64 * 4)()
-    info = C.c_int32(0)
+    out = _Result()
     _lib.note_hip_use()
     st = lib.gpbo_refine_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(x), P, _ptr(lo), _ptr(hi),
                                   kind, p0, p1, iters, step0, _ptr(acq), _ptr(acq0), _ptr(accepted), _ptr(pg),
-                                  C.cast(res, C.c_void_p), C.cast(C.pointer(info), C.c_void_p))
+                                  out.res_ptr, out.info_ptr)
     _lib.check(st, "gpbo_refine_host_f64")
-    best_val = float(np.frombuffer(res, dtype=np.float64, count=1)[0])
-    return dict(x=x, acq=acq, acq0=acq0, accepted=accepted, pg=pg, best=int(res[1]), best_val=best_val, nan_count=int(res[2]),
-                info=int(info.value))
+    r = out.decode()
+    return dict(x=x, acq=acq, acq0=acq0, accepted=accepted, pg=pg, best=r["best_idx"], best_val=r["best_val"],
+                nan_count=r["nan_count"], info=r["info"])
 
 
 class _GridOnly:
@@ -210,15 +225,22 @@ class PointSelectorHost(PointSelector):
         self._chunk = int(chunk)
         self._inputs = None
 
+    def _surrogate_inputs(self):
+        if self._inputs is None:
+            raise RuntimeError("call update_surrogate() first")
+        return self._inputs
+
+    def _factorised(self, r):
+        """The result dict of a host call, or the error of a covariance matrix that is not positive definite."""
+        if r["info"] != 0:
+            raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(self._inputs[0])}); "
+                                        "the reference's np.linalg.inv would raise or return garbage here")
+        return r
+
     def _score(self, acquisition, want_cov_meas=False, **kw):
         X, y, ls, Xs = self._inputs
-        r = select_next(X, y, ls, Xs, acquisition=acquisition, dense=True, want_cov_meas=want_cov_meas,
-                        chunk=self._chunk, lib=self.lib, **kw)
-        if r["info"] != 0:
-            raise np.linalg.LinAlgError(
-                f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)}); "
-                "the reference's np.linalg.inv would raise or return garbage here")
-        return r
+        return self._factorised(select_next(X, y, ls, Xs, acquisition=acquisition, dense=True, want_cov_meas=want_cov_meas,
+                                            chunk=self._chunk, lib=self.lib, **kw))
 
     def update_surrogate(self):
         """point_selector.py:42-102."""
@@ -248,73 +270,50 @@ class PointSelectorHost(PointSelector):
         acq, (best_val, best_idx, nan_count) = self._cached[key]
         self.acq_func_eval = acq
         if nan_count > 0 or best_idx >= int(np.prod(fd)) or best_idx < 0:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+            raise IndexError(NAN_ACQUISITION)
         return np.array(np.unravel_index(best_idx, fd), dtype=np.int64)
 
     def q_expected_improvement(self, n_samples=512, seed=7, xi=0.0):
         """q = 8 Monte-Carlo Expected Improvement on the host-pointer route (same definition and return value as
         PointSelector.q_expected_improvement: the (8, ndim) multi-indices of the first batch with the largest qEI)."""
-        if self._inputs is None:
-            raise RuntimeError("call update_surrogate() first")
-        X, y, ls, Xs = self._inputs
+        X, y, ls, Xs = self._surrogate_inputs()
         fd = [int(v) for v in self.feature_domain]
         M = int(np.prod(fd))
         if M % 8:
             raise ValueError("q_expected_improvement needs a candidate count that is a multiple of 8")
-        Z = _f64(np.random.default_rng(seed).standard_normal((int(n_samples), 8)))
-        X, y, Xs, ls = _f64(X), _f64(y).reshape(-1), _f64(Xs), _f64(np.asarray(ls, dtype=np.float64).reshape(-1))
-        qei = np.empty(M // 8)
-        res = (C.c_int64 * 4)()
-        info = C.c_int32(0)
-        _lib.note_hip_use()
-        st = self.lib.gpbo_select_qei_host_f64(_ptr(X), _ptr(y), X.shape[0], X.shape[1], _ptr(ls), JITTER_KERNEL,
-                                               JITTER_ASSEMBLY, _ptr(Xs), M, float(np.min(y)), float(xi), _ptr(Z),
-                                               int(n_samples), self._chunk, _ptr(qei), C.cast(res, C.c_void_p),
-                                               C.cast(C.pointer(info), C.c_void_p))
-        _lib.check(st, "gpbo_select_qei_host_f64")
-        if info.value != 0:
-            raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {info.value} of {len(X)})")
-        self.acq_func_eval = qei
-        if int(res[2]) > 0 or int(res[1]) >= M // 8 or int(res[1]) < 0:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
-        flat = int(res[1]) * 8 + np.arange(8)
+        Z = np.random.default_rng(seed).standard_normal((int(n_samples), 8))
+        r = self._factorised(select_qei(X, y, ls, Xs, Z, float(np.min(y)), xi=xi, chunk=self._chunk, lib=self.lib))
+        self.acq_func_eval = r["qei"]
+        if r["nan_count"] > 0 or r["best_idx"] >= M // 8 or r["best_idx"] < 0:
+            raise IndexError(NAN_ACQUISITION)
+        flat = r["best_idx"] * 8 + np.arange(8)
         return np.stack(np.unravel_index(flat, fd), axis=1).astype(np.int64)
 
     def select_batch(self, q, acquisition="lcb", explore=4, xi=0.0, fantasy="believer", lie=None):
         """PointSelector.select_batch on the host-pointer route (gpbo_select_batch_host_f64: factorisation, plain pass and
         selection in one call): the same (q, ndim) multi-indices, the same errors."""
-        if self._inputs is None:
-            raise RuntimeError("call update_surrogate() first")
-        X, y, ls, Xs = self._inputs
+        X, y, ls, Xs = self._surrogate_inputs()
         if Xs.shape == X.shape:
             raise ValueError("select_batch() does not support candidates of the observations' shape (the N == M quirk)")
         r = select_batch(X, y, ls, Xs, q, fantasy=fantasy, lie=lie, chunk=self._chunk, lib=self.lib,
                          **self._batch_acq(acquisition, explore, xi))
-        if r["info"] != 0 and np.all(r["indices"] < 0):
-            raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)})")
+        if np.all(r["indices"] < 0):   # (with members chosen, info is the selection's own report)
+            self._factorised(r)
         return self._batch_indices(r["indices"], r["nan_count"])
 
     def select_thompson(self, q, n_features=2048, seed=0):
         """PointSelector.select_thompson on the host-pointer route (gpbo_thompson_host_f64): the same (k, ndim) multi-indices
         for the same seed, the same errors."""
-        if self._inputs is None:
-            raise RuntimeError("call update_surrogate() first")
-        X, y, ls, Xs = self._inputs
-        r = select_thompson(X, y, ls, Xs, q, n_features=n_features, seed=seed, lib=self.lib)
-        if r["info"] != 0:
-            raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)})")
+        X, y, ls, Xs = self._surrogate_inputs()
+        r = self._factorised(select_thompson(X, y, ls, Xs, q, n_features=n_features, seed=seed, lib=self.lib))
         return self._batch_indices(r["indices"], int(np.sum(r["nan_counts"])))
 
     def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
         """PointSelector.refine_next on the host-pointer route (gpbo_refine_host_f64): the same d coordinates, the same
         errors."""
-        if self._inputs is None:
-            raise RuntimeError("call update_surrogate() first")
+        X, y, ls, _ = self._surrogate_inputs()
         kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
-        X, y, ls, _ = self._inputs
-        r = refine(X, y, ls, starts, lo, hi, iters=int(iters), lib=self.lib, **kw)
-        if r["info"] != 0:
-            raise np.linalg.LinAlgError(f"covariance matrix is not positive definite (pivot {r['info']} of {len(X)})")
+        r = self._factorised(refine(X, y, ls, starts, lo, hi, iters=int(iters), lib=self.lib, **kw))
         if r["nan_count"] > 0 or r["best"] < 0:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+            raise IndexError(NAN_ACQUISITION)
         return r["x"][r["best"]].copy()

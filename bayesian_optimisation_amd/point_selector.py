@@ -39,7 +39,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import distributed as D
-from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, DeviceGP
+from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, NAN_ACQUISITION, DeviceGP
 
 COV_PRED_MAX_M = 4096          # cov_pred is M x M: 128 MiB at this size
 COV_MEAS_PRED_MAX = 1 << 24    # entries of the (M, N) cross covariance kept for inspection
@@ -444,7 +444,7 @@ class PointSelector:
         self.acq_func_eval = acq
         if nan_count > 0 or best_idx >= int(np.prod(fd)):
             # the reference: amax is NaN, the comparison is empty, [0] raises (point_selector.py:207)
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+            raise IndexError(NAN_ACQUISITION)
         return np.array(np.unravel_index(best_idx, fd), dtype=np.int64)
 
     def lower_confidence_bound(self, explore=4):
@@ -475,7 +475,7 @@ class PointSelector:
         qei = D.gather_concat_tensors([res.acq], M // 8)[0].cpu().numpy()
         self.acq_func_eval = qei
         if nan_count > 0 or best_idx >= M // 8:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+            raise IndexError(NAN_ACQUISITION)
         res.best_idx = best_idx
         flat = res.best_idx * 8 + np.arange(8)
         return np.stack(np.unravel_index(flat, fd), axis=1).astype(np.int64)
@@ -491,7 +491,7 @@ class PointSelector:
     def _batch_indices(self, indices, nan_count):
         fd = [int(v) for v in self.feature_domain]
         if nan_count > 0 or np.any(indices < 0) or np.any(indices >= int(np.prod(fd))):
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+            raise IndexError(NAN_ACQUISITION)
         return np.stack(np.unravel_index(indices, fd), axis=1).astype(np.int64)
 
     def select_batch(self, q, acquisition="lcb", explore=4, xi=0.0, fantasy="believer", lie=None):
@@ -583,7 +583,7 @@ class PointSelector:
         kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
         r = self._gp.refine(starts, lo, hi, iters=int(iters), **kw)
         if r.nan_count > 0 or r.best < 0:
-            raise IndexError("index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)")
+            raise IndexError(NAN_ACQUISITION)
         return r.x[r.best].cpu().numpy().astype(np.float64)
 
     def expected_improvement(self, xi=0.0):

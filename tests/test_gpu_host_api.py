@@ -1,6 +1,6 @@
-"""The host-pointer entry points (gpbo_select_next_host_f64, gpbo_nlml_grid_host_f64) and the NumPy + ctypes
-class built on them: same numbers as the tensor-resident path, same answers as the reference's golden vectors,
-and no PyTorch in the process."""
+"""The host-pointer entry points (csrc/host_api.hip) and the NumPy + ctypes class built on them: same numbers as the
+tensor-resident path, same answers as the reference's golden vectors, no PyTorch in the process, the bits recorded
+before the entries shared one prologue, and the not-positive-definite exit of every factorising entry."""
 import os
 import subprocess
 import sys
@@ -229,3 +229,70 @@ def test_host_binding_q_expected_improvement_matches_the_tensor_resident_class()
     assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])
     ref = O.qei_mc(X, y, Xs, ls, O.qei_base_samples(256, 8, 7), float(np.min(y)))
     np.testing.assert_allclose(out[0][1], ref, rtol=0, atol=1e-9)
+
+
+# ---- every host entry, bit for bit what it computed before the entries shared one prologue (tests/golden/host_api_*.npz) ----
+def _golden_cases():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("make_host_api_golden", os.path.join(REPO, "tests", "golden", "make_host_api_golden.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+HG = _golden_cases()
+
+
+@pytest.mark.parametrize("case", sorted(HG.CASES))
+def test_every_host_entry_gives_the_recorded_bits(case):
+    want = dict(np.load(HG.path(case), allow_pickle=False))
+    got = HG.CASES[case]()
+    assert set(got) == set(want)
+    for key in sorted(want):
+        a, b = np.asarray(got[key]), want[key]
+        assert a.shape == b.shape and a.dtype == b.dtype, key
+        if a.ndim == 0:
+            assert a[()] == b[()], (key, a, b)
+        assert np.array_equal(a, b, equal_nan=a.dtype.kind == "f"), key
+        assert HG.same_bits(a, b), key
+
+
+@pytest.fixture(scope="module")
+def not_pd():
+    """N = 6, d = 2, M = 16 with a NaN coordinate in observation 3: the factorisation stops at pivot 4."""
+    X, y, Xs, ls = make_problem(6, 16, 2)
+    X = X.copy()
+    X[3, 1] = np.nan
+    return X, y, ls, Xs
+
+
+def test_not_positive_definite_exit_of_select_next_and_qei(not_pd):
+    X, y, ls, Xs = not_pd
+    for dense in (True, False):
+        r = H.select_next(X, y, ls, Xs, dense=dense)
+        assert (r["info"], r["best_idx"], r["nan_count"]) == (4, -1, 0), r
+    Z = np.random.default_rng(7).standard_normal((64, 8))
+    r = H.select_qei(X, y, ls, Xs, Z, float(np.min(y)))
+    assert (r["info"], r["best_idx"], r["nan_count"]) == (4, -1, 0), r
+
+
+def test_not_positive_definite_exit_of_select_batch_and_select_thompson(not_pd):
+    X, y, ls, Xs = not_pd
+    for kw in (dict(), dict(fantasy="liar", lie=0.0)):
+        r = H.select_batch(X, y, ls, Xs, 3, **kw)
+        assert r["info"] == 4 and np.array_equal(r["indices"], [-1, -1, -1]), r
+    r = H.select_thompson(X, y, ls, Xs, 2, n_features=64)
+    assert r["info"] == 4 and len(r["indices"]) == 0
+    assert len(r["all_indices"]) == 4 and np.all(r["all_indices"] == -1)
+    assert np.all(np.isnan(r["all_values"])) and np.all(r["nan_counts"] == 0)
+
+
+def test_not_positive_definite_exit_of_refine_and_nlml_and_grad(not_pd):
+    X, y, ls, Xs = not_pd
+    starts = np.ascontiguousarray(Xs[:4])
+    r = H.refine(X, y, ls, starts, Xs.min(axis=0), Xs.max(axis=0), iters=5)
+    assert r["info"] == 4 and r["best"] == -1
+    assert r["x"].tobytes() == starts.tobytes()
+    nlml, grad = H.nlml_and_grad(X, y, ls)
+    assert np.isnan(nlml) and grad.shape == (2,) and np.all(np.isnan(grad))

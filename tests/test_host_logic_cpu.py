@@ -84,6 +84,23 @@ def test_host_binding_checks_shapes_before_touching_the_device():
         H.select_next(X, y, [1.0, 1.0], Xs, acquisition="ucb")
     with pytest.raises(ValueError):
         H.select_next(X, y, [1.0, 1.0], Xs, acquisition="ei")            # EI needs the incumbent
+    # every other entry of the binding: a wrong ls length, a wrong y length, a wrong Xs width
+    with_candidates = {"select_batch": lambda X, y, ls, Xs: H.select_batch(X, y, ls, Xs, 2),
+                       "select_thompson": lambda X, y, ls, Xs: H.select_thompson(X, y, ls, Xs, 2, n_features=64),
+                       "select_qei": lambda X, y, ls, Xs: H.select_qei(X, y, ls, Xs, np.zeros((4, 8)), 0.0)}
+    without = {"refine": lambda X, y, ls: H.refine(X, y, ls, Xs[:2], Xs.min(axis=0), Xs.max(axis=0)),
+               "nlml_and_grad": lambda X, y, ls: H.nlml_and_grad(X, y, ls)}
+    for name, call in {**with_candidates, **without}.items():
+        more = (Xs,) if name in with_candidates else ()
+        with pytest.raises(ValueError):
+            call(X, y, [1.0, 1.0, 1.0], *more)
+        with pytest.raises(ValueError):
+            call(X, y[:4], [1.0, 1.0], *more)
+        with pytest.raises(ValueError):
+            call(np.zeros(5), y, [1.0], *more)                           # X is not 2-D
+    for name, call in with_candidates.items():
+        with pytest.raises(ValueError):
+            call(X, y, [1.0, 1.0], np.zeros((7, 3)))
 
 
 def test_precision_and_q_ei_argument_checks():

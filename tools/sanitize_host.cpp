@@ -210,6 +210,12 @@ int main() {
     EXPECT(gpbo_select_qei_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, 0, nullptr, 0, 0, nullptr, &res,
                                     &info_h) == GPBO_ERR_ARG);
     EXPECT(gpbo_nlml_grid_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr) == GPBO_ERR_ARG);
+    EXPECT(gpbo_nlml_grid_logdet_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr) == GPBO_ERR_ARG);
+    EXPECT(gpbo_nlml_grad_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, nullptr) == GPBO_ERR_ARG);
+    EXPECT(gpbo_select_batch_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, nullptr, nullptr,
+                                      nullptr, nullptr, &res, &info_h) == GPBO_ERR_ARG);
+    EXPECT(gpbo_refine_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0, 0, 0, 0, 0, nullptr,
+                                nullptr, nullptr, nullptr, &res, &info_h) == GPBO_ERR_ARG);
     if (fails) {
         std::fprintf(stderr, "sanitize_host: %d check(s) failed\n", fails);
         return 1;
