@@ -43,8 +43,6 @@ struct BatchRec {
     int32_t pad;
 };
 
-constexpr int64_t kNone = std::numeric_limits<int64_t>::max();
-
 // k_j[n] = k(x_n, x_j) in the factorisation's own order (0 on the padding), the scaled x_j and the scalars of step j.
 // grid ceil(Np / 256), block 256.  A member that does not exist (idx < 0: see batch_record_kernel) gives k_j = 0.
 __global__ __launch_bounds__(256) void batch_pivot_kernel(const double *__restrict__ Xs, int64_t M,
@@ -109,8 +107,8 @@ __global__ __launch_bounds__(256) void batch_downdate_kernel(const double *__res
     const int tid = threadIdx.x, lane = tid & 63;
     if (rec->bad) {   // uniform over the launch: nothing is updated, nothing can be chosen
         if (tid == 0) {
-            part_val[blockIdx.x] = -std::numeric_limits<double>::infinity();
-            part_idx[blockIdx.x] = kNone;
+            part_val[blockIdx.x] = gpbo_none::val;
+            part_idx[blockIdx.x] = gpbo_none::idx;
         }
         return;
     }
@@ -202,20 +200,13 @@ __global__ __launch_bounds__(256) void batch_downdate_kernel(const double *__res
     }
     const unsigned long long mask_a = __ballot(nan_a), mask_b = __ballot(nan_b);
     if (lane == 0 && (mask_a | mask_b)) atomicAdd(nan_count, (unsigned long long)(__popcll(mask_a) + __popcll(mask_b)));
-    double bv = use_a ? acq_a : -std::numeric_limits<double>::infinity();
-    int64_t bi = use_a ? idx_offset + c0 : kNone;
+    double bv = use_a ? acq_a : gpbo_none::val;
+    int64_t bi = use_a ? idx_offset + c0 : gpbo_none::idx;
     if (use_b && gpbo_better(acq_b, idx_offset + c0 + 1, bv, bi)) { bv = acq_b; bi = idx_offset + c0 + 1; }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bv, off);
-        const int64_t oi = __shfl_xor(bi, off);
-        if (gpbo_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; }
+    gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     gpbo_syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (gpbo_better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
+        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
         part_val[blockIdx.x] = bv;
         part_idx[blockIdx.x] = bi;
     }
@@ -228,7 +219,7 @@ __global__ void batch_record_kernel(gpbo_result *__restrict__ result, int j, int
                                     int64_t *__restrict__ idx_out, double *__restrict__ val_out) {
     if (result->nan_count > rec->nan_total) rec->nan_total = result->nan_count;
     const int64_t bi = result->best_idx;
-    if (rec->bad || bi == kNone) {
+    if (rec->bad || bi == gpbo_none::idx) {
         rec->bad = 1;
         rec->idx[j] = -1;
         idx_out[j] = -1;

@@ -44,6 +44,44 @@ __device__ __forceinline__ bool gpbo_better(double v2, int64_t i2, double v, int
     return (v2 > v) || (v2 == v && i2 < i);
 }
 
+// the empty record of that order: every candidate beats it, and a reduction over nothing returns it
+namespace gpbo_none {
+constexpr double val = -__builtin_huge_val();
+constexpr int64_t idx = INT64_MAX;
+}  // namespace gpbo_none
+
+// arg-max of a wave: afterwards every lane holds the wave's record (64-lane butterfly; all lanes must be active)
+__device__ __forceinline__ void gpbo_wave_argmax(double &bv, int64_t &bi) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const double ov = __shfl_xor(bv, off);
+        const int64_t oi = __shfl_xor(bi, off);
+        if (gpbo_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+}
+
+// arg-max of a workgroup in two pieces around the CALLER'S barrier: every wave posts its record to entry wave * stride
+// of the caller's LDS arrays (the helpers declare no __shared__ object: see sigma_acq_kernel), then one thread folds the
+// nwaves entries in wave order.  stride > 1: several reductions interleaved in one array (thompson_paths_kernel).
+__device__ __forceinline__ void gpbo_argmax_post(double bv, int64_t bi, int lane, int wave, double *s_val, int64_t *s_idx,
+                                                 int stride = 1) {
+    gpbo_wave_argmax(bv, bi);
+    if (lane == 0) { s_val[wave * stride] = bv; s_idx[wave * stride] = bi; }
+}
+__device__ __forceinline__ void gpbo_argmax_fold(const double *s_val, const int64_t *s_idx, int nwaves, double &bv, int64_t &bi,
+                                                 int stride = 1) {
+    bv = s_val[0];
+    bi = s_idx[0];
+    for (int w = 1; w < nwaves; ++w)
+        if (gpbo_better(s_val[w * stride], s_idx[w * stride], bv, bi)) { bv = s_val[w * stride]; bi = s_idx[w * stride]; }
+}
+
+// NaN count of a wave's candidates: one atomicAdd per wave that has any
+__device__ __forceinline__ void gpbo_count_nan(bool is_nan, int lane, unsigned long long *counter) {
+    const unsigned long long nan_mask = __ballot(is_nan);
+    if (lane == 0 && nan_mask) atomicAdd(counter, (unsigned long long)__popcll(nan_mask));
+}
+
 // acquisition value from the posterior mean and standard deviation (point_selector.py:204; EI: SURVEY.md 8 a10)
 __device__ __forceinline__ double gpbo_acquisition(int kind, double mu, double sigma, double p0, double p1) {
     if (kind == GPBO_ACQ_LCB) return p0 * sigma - mu;
@@ -76,9 +114,41 @@ __device__ __forceinline__ double gpbo_acquisition_ub(int kind, double mu, doubl
     return (t1 + t2) + pad + 1e-300;
 }
 
-// launchers implemented in the individual .hip files (host side, enqueue only)
-// prefix bound: variance floor / pad (see sigma_acq_kernel's epilogue)
+// prefix bound: variance floor / pad (see gpbo_candidate_epilogue)
 #define GPBO_BOUND_VAR_PAD 1e-8
+
+// What every variance kernel does for chunk-local candidate c once its |v_c|^2 = ssq is known (all 64 lanes of a wave call
+// it together; valid = c is a real candidate): the mean from the nsl per-slice partials in index order, sigma, the
+// acquisition, the optional dense stores, the NaN count, and this candidate's seed (bv, bi) for the arg-max.
+// var_pad > 0 is the prefix bound (ssq is then a LOWER bound of |v_c|^2): the plain pass takes sqrt(|var|), and a variance
+// that rounding has pushed a hair below zero (a candidate on top of an observation) can have a LARGER magnitude than the
+// prefix's: clamp and pad, so that the bound holds whenever the plain variance is above -1e-9 (observed: 1e-13), and round
+// the acquisition outward (gpbo_acquisition_ub).  var_out receives the signed (padded) variance.
+__device__ __forceinline__ void gpbo_candidate_epilogue(double ssq, const double *__restrict__ mu_part, int nsl, int64_t ldk,
+                                                        int64_t c, bool valid, double prior_var, double var_pad, int acq_kind,
+                                                        double p0, double p1, int64_t idx_base, double *__restrict__ mu_out,
+                                                        double *__restrict__ sigma_out, double *__restrict__ acq_out,
+                                                        double *__restrict__ var_out, int lane,
+                                                        unsigned long long *__restrict__ nan_count, double &bv, int64_t &bi) {
+    double mu = 0.0;
+    for (int s = 0; s < nsl; ++s) mu += mu_part[(int64_t)s * ldk + c];
+    double var = prior_var - ssq;
+    if (var_pad > 0.0) var = fmax(var, 0.0) + var_pad;
+    const double sigma = sqrt(fabs(var));  // abs, then sqrt: point_selector.py:98
+    const double acq = (var_pad > 0.0) ? gpbo_acquisition_ub(acq_kind, mu, sigma, p0, p1) : gpbo_acquisition(acq_kind, mu, sigma, p0, p1);
+    if (valid) {
+        if (mu_out) mu_out[c] = mu;
+        if (sigma_out) sigma_out[c] = sigma;
+        if (acq_out) acq_out[c] = acq;
+        if (var_out) var_out[c] = var;
+    }
+    const bool is_nan = valid && (acq != acq);
+    gpbo_count_nan(is_nan, lane, nan_count);
+    bv = (valid && !is_nan) ? acq : gpbo_none::val;
+    bi = (valid && !is_nan) ? idx_base + c : gpbo_none::idx;
+}
+
+// launchers implemented in the individual .hip files (host side, enqueue only)
 // K(X*,X) with the distances on the matrix cores (kstar_mfma.hip): prefix-bound route only
 int64_t gpbo_kstar_mfma_prep_bytes(int64_t Np);
 int gpbo_kstar_mfma_slice(int64_t Np);

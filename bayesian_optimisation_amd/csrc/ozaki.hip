@@ -32,7 +32,6 @@
 // products: -0.5 %), removing bytes does (column groups, below: -9 %).
 #include "gpbo_internal.h"
 
-#include <limits>
 
 namespace {
 
@@ -544,35 +543,17 @@ __global__ __launch_bounds__(512) void sigma_i8_kernel(
         const int64_t c = (int64_t)tile * BM + tid;
         const bool valid = c < Mc;
         const double ssq = ((red[tid] + red[BM + tid]) + red[2 * BM + tid]) + red[3 * BM + tid];
-        double mu = 0.0;
-        for (int s = 0; s < nsl; ++s) mu += mu_part[(int64_t)s * ldk + c];
-        const double var = prior_var - ssq;
-        const double sigma = sqrt(fabs(var));
-        const double acq = gpbo_acquisition(acq_kind, mu, sigma, p0, p1);
-        if (valid) {
-            if (mu_out) mu_out[c] = mu;
-            if (sigma_out) sigma_out[c] = sigma;
-            if (acq_out) acq_out[c] = acq;
-            if (var_out) var_out[c] = var;
-        }
-        const bool is_nan = valid && (acq != acq);
-        const unsigned long long nan_mask = __ballot(is_nan);
-        if (lane == 0 && nan_mask) atomicAdd(nan_count, (unsigned long long)__popcll(nan_mask));
-        double bv = (valid && !is_nan) ? acq : -std::numeric_limits<double>::infinity();
-        int64_t bi = (valid && !is_nan) ? idx_base + c : std::numeric_limits<int64_t>::max();
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int64_t oi = __shfl_xor(bi, off);
-            if (gpbo_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; }
+        double bv;
+        int64_t bi;
+        gpbo_candidate_epilogue(ssq, mu_part, nsl, ldk, c, valid, prior_var, 0.0, acq_kind, p0, p1, idx_base, mu_out, sigma_out,
+                                acq_out, var_out, lane, nan_count, bv, bi);
+        gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     }
     __syncthreads();
     if (tid == 0) {
-        double bv = s_val[0];
-        int64_t bi = s_idx[0];
-        if (gpbo_better(s_val[1], s_idx[1], bv, bi)) { bv = s_val[1]; bi = s_idx[1]; }
+        double bv;
+        int64_t bi;
+        gpbo_argmax_fold(s_val, s_idx, BM / 64, bv, bi);
         part_val[tile] = bv;
         part_idx[tile] = bi;
     }

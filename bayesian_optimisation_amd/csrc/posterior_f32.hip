@@ -18,7 +18,6 @@
 #include "gpbo_internal.h"
 
 #include <cstdlib>
-#include <limits>
 #include <type_traits>
 
 namespace {
@@ -40,8 +39,6 @@ struct LsArgs32 {
 __device__ __forceinline__ void glds16f(const float *g, float *l) {
     __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)l, 16, 0, 0);
 }
-
-__device__ __forceinline__ bool better(double v2, int64_t i2, double v, int64_t i) { return gpbo_better(v2, i2, v, i); }
 
 // ---- U32 / alpha32: fp32 copies of the fp64 factors, re-padded to Np32 (identity / zeros on the padding)
 __global__ __launch_bounds__(256) void prepare_f32_kernel(const double *__restrict__ U, const double *__restrict__ alpha,
@@ -209,36 +206,17 @@ __global__ __launch_bounds__(512) void sigma_acq_f32_kernel(
         const int64_t c = cand0 + tid;
         const bool valid = c < Mc;
         const float ssq = red[tid] + red[BM + tid];
-        double mu = 0.0;  // same fixed-order sum of the same fp64 partials as the fp64 path
-        for (int s = 0; s < nsl; ++s) mu += mu_part[(int64_t)s * ldk + c];
-        const double var = prior_var - (double)ssq;
-        const double sigma = sqrt(fabs(var));
-        const double acq = gpbo_acquisition(acq_kind, mu, sigma, p0, p1);
-        if (valid) {
-            if (mu_out) mu_out[c] = mu;
-            if (sigma_out) sigma_out[c] = sigma;
-            if (acq_out) acq_out[c] = acq;
-            if (var_out) var_out[c] = var;
-        }
-        const bool is_nan = valid && (acq != acq);
-        const unsigned long long nan_mask = __ballot(is_nan);
-        if (lane == 0 && nan_mask) atomicAdd(nan_count, (unsigned long long)__popcll(nan_mask));
-        double bv = (valid && !is_nan) ? acq : -std::numeric_limits<double>::infinity();
-        int64_t bi = (valid && !is_nan) ? idx_base + c : std::numeric_limits<int64_t>::max();
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int64_t oi = __shfl_xor(bi, off);
-            if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; }
+        double bv;  // (the mean: the same fixed-order sum of the same fp64 partials as the fp64 path)
+        int64_t bi;
+        gpbo_candidate_epilogue((double)ssq, mu_part, nsl, ldk, c, valid, prior_var, 0.0, acq_kind, p0, p1, idx_base, mu_out,
+                                sigma_out, acq_out, var_out, lane, nan_count, bv, bi);
+        gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     }
     __syncthreads();
     if (tid == 0) {
-        double bv = s_val[0];
-        int64_t bi = s_idx[0];
-        for (int w = 1; w < BM / 64; ++w)
-            if (better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
+        double bv;
+        int64_t bi;
+        gpbo_argmax_fold(s_val, s_idx, BM / 64, bv, bi);
         part_val[blockIdx.x] = bv;
         part_idx[blockIdx.x] = bi;
     }

@@ -49,7 +49,6 @@ struct RefinePoint {
 enum { MODE_EVAL = 0, MODE_START = 1, MODE_STEP = 2 };
 
 constexpr double kArmijo = 1e-4;
-constexpr int64_t kNone = std::numeric_limits<int64_t>::max();
 constexpr int KS_POINTS = 8;   // points per workgroup of refine_ks_kernel (Pp is a multiple of 64)
 
 __device__ __forceinline__ double clip(double v, double lo, double hi) {   // NaN stays NaN (as numpy.clip)
@@ -285,8 +284,8 @@ __global__ __launch_bounds__(256) void refine_finish_kernel(const RefinePoint *_
     __shared__ double s_val[4];
     __shared__ int64_t s_idx[4], s_nan[4];
     const int tid = threadIdx.x, lane = tid & 63;
-    double bv = -std::numeric_limits<double>::infinity();
-    int64_t bi = kNone, nans = 0;
+    double bv = gpbo_none::val;
+    int64_t bi = gpbo_none::idx, nans = 0;
     for (int p = tid; p < P; p += 256) {
         const RefinePoint *r = rec + p;
         double pg = 0.0;
@@ -308,21 +307,15 @@ __global__ __launch_bounds__(256) void refine_finish_kernel(const RefinePoint *_
         if (f == f && gpbo_better(f, p, bv, bi)) { bv = f; bi = p; }
     }
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bv, off);
-        const int64_t oi = __shfl_xor(bi, off);
-        nans += __shfl_xor(nans, off);
-        if (gpbo_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; s_nan[tid >> 6] = nans; }
+    for (int off = 1; off < 64; off <<= 1) nans += __shfl_xor(nans, off);
+    if (lane == 0) s_nan[tid >> 6] = nans;
+    gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     gpbo_syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w) {
-            nans += s_nan[w];
-            if (gpbo_better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
-        }
-        result->best_val = (bi == kNone) ? __builtin_nan("") : bv;
-        result->best_idx = (bi == kNone) ? -1 : bi;
+        for (int w = 1; w < 4; ++w) nans += s_nan[w];
+        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
+        result->best_val = (bi == gpbo_none::idx) ? __builtin_nan("") : bv;
+        result->best_idx = (bi == gpbo_none::idx) ? -1 : bi;
         result->nan_count = nans;
         result->reserved = 0;
     }

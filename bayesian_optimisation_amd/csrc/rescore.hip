@@ -215,8 +215,8 @@ __global__ __launch_bounds__(SB) void rescore_finish_kernel(const double *__rest
     __shared__ double s_val[SB / 64], s_err[SB / 64];
     __shared__ int64_t s_idx[SB / 64];
     __shared__ unsigned long long s_nan[SB / 64];
-    double bv = -std::numeric_limits<double>::infinity(), err = 0.0;
-    int64_t bi = std::numeric_limits<int64_t>::max();
+    double bv = gpbo_none::val, err = 0.0;
+    int64_t bi = gpbo_none::idx;
     unsigned long long nans = 0;
     for (int64_t i = threadIdx.x; i < K; i += SB) {
         const double a = acq[i], sg = sigma[i];
@@ -230,18 +230,16 @@ __global__ __launch_bounds__(SB) void rescore_finish_kernel(const double *__rest
     }
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bv, off);
-        const int64_t oi = __shfl_xor(bi, off);
         err = fmax(err, __shfl_xor(err, off));
         nans += __shfl_xor(nans, off);
-        if (gpbo_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
     }
     const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { s_val[w] = bv; s_idx[w] = bi; s_err[w] = err; s_nan[w] = nans; }
+    if ((threadIdx.x & 63) == 0) { s_err[w] = err; s_nan[w] = nans; }
+    gpbo_argmax_post(bv, bi, threadIdx.x & 63, w, s_val, s_idx);
     __syncthreads();
     if (threadIdx.x == 0) {
+        gpbo_argmax_fold(s_val, s_idx, SB / 64, bv, bi);
         for (int q = 1; q < SB / 64; ++q) {
-            if (gpbo_better(s_val[q], s_idx[q], bv, bi)) { bv = s_val[q]; bi = s_idx[q]; }
             err = fmax(err, s_err[q]);
             nans += s_nan[q];
         }

@@ -21,7 +21,6 @@
 #include "gpbo_internal.h"
 
 #include <cstdlib>
-#include <limits>
 #include <mutex>
 #include <type_traits>
 
@@ -75,11 +74,6 @@ __device__ __forceinline__ void glds16(const double *g, unsigned off, double *l)
     const __amdgpu_buffer_rsrc_t desc = __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(g), 0, -1, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(desc, (lds_void_t *)l, 16, (int)off, 0, 0, 0);
 #endif
-}
-
-__device__ __forceinline__ bool better(double v2, int64_t i2, double v, int64_t i) { return gpbo_better(v2, i2, v, i); }
-__device__ __forceinline__ double acquisition(int kind, double mu, double sigma, double p0, double p1) {
-    return gpbo_acquisition(kind, mu, sigma, p0, p1);
 }
 
 // GRAM (config 5, q = 8 Monte-Carlo qEI): the tiles of V are computed TRANSPOSED (the two operands of every product swapped:
@@ -398,40 +392,17 @@ __global__ __launch_bounds__(NW * 64) void sigma_acq_kernel(
         double ssq = red[tid];
 #pragma unroll
         for (int q = 1; q < WQ; ++q) ssq += red[q * BM + tid];
-        double mu = 0.0;
-        for (int s = 0; s < nsl; ++s) mu += mu_part[(int64_t)s * ldk + c];
-        double var = prior_var - ssq;
-        // prefix bound (ncb > 0): the plain pass takes sqrt(|var|), and a variance that rounding has pushed a hair below
-        // zero (a candidate on top of an observation) can have a LARGER magnitude than the prefix's: clamp and pad, so that
-        // the bound holds whenever the plain variance is above -1e-9 (observed: 1e-13)
-        if (ncb > 0) var = fmax(var, 0.0) + GPBO_BOUND_VAR_PAD;
-        const double sigma = sqrt(fabs(var));  // abs, then sqrt: point_selector.py:98
-        // (prefix bound: the acquisition rounded outward, so that it bounds what the plain pass computes - gpbo_internal.h)
-        const double acq = (ncb > 0) ? gpbo_acquisition_ub(acq_kind, mu, sigma, p0, p1) : acquisition(acq_kind, mu, sigma, p0, p1);
-        if (valid) {
-            if (mu_out) mu_out[c] = mu;
-            if (sigma_out) sigma_out[c] = sigma;
-            if (acq_out) acq_out[c] = acq;
-        }
-        const bool is_nan = valid && (acq != acq);
-        const unsigned long long nan_mask = __ballot(is_nan);
-        if (lane == 0 && nan_mask) atomicAdd(nan_count, (unsigned long long)__popcll(nan_mask));
-        double bv = (valid && !is_nan) ? acq : -std::numeric_limits<double>::infinity();
-        int64_t bi = (valid && !is_nan) ? idx_base + c : std::numeric_limits<int64_t>::max();
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int64_t oi = __shfl_xor(bi, off);
-            if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
-        if (lane == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; }
+        double bv;
+        int64_t bi;
+        gpbo_candidate_epilogue(ssq, mu_part, nsl, ldk, c, valid, prior_var, ncb > 0 ? GPBO_BOUND_VAR_PAD : 0.0, acq_kind, p0, p1,
+                                idx_base, mu_out, sigma_out, acq_out, nullptr, lane, nan_count, bv, bi);
+        gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     }
     __syncthreads();
     if (tid == 0) {
-        double bv = s_val[0];
-        int64_t bi = s_idx[0];
-        for (int w = 1; w < BM / 64; ++w)
-            if (better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
+        double bv;
+        int64_t bi;
+        gpbo_argmax_fold(s_val, s_idx, BM / 64, bv, bi);
         part_val[blockIdx.x] = bv;
         part_idx[blockIdx.x] = bi;
     }
@@ -445,21 +416,14 @@ __global__ __launch_bounds__(256) void argmax_finish_kernel(const double *__rest
     __shared__ double s_val[4];
     __shared__ int64_t s_idx[4];
     const int tid = threadIdx.x, lane = tid & 63;
-    double bv = -std::numeric_limits<double>::infinity();
-    int64_t bi = std::numeric_limits<int64_t>::max();
+    double bv = gpbo_none::val;
+    int64_t bi = gpbo_none::idx;
     for (int64_t p = tid; p < nparts; p += 256)
-        if (better(part_val[p], part_idx[p], bv, bi)) { bv = part_val[p]; bi = part_idx[p]; }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bv, off);
-        const int64_t oi = __shfl_xor(bi, off);
-        if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; }
+        if (gpbo_better(part_val[p], part_idx[p], bv, bi)) { bv = part_val[p]; bi = part_idx[p]; }
+    gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
+        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
         result->best_val = bv;
         result->best_idx = bi;
         result->nan_count = (int64_t)*nan_count;
@@ -467,8 +431,8 @@ __global__ __launch_bounds__(256) void argmax_finish_kernel(const double *__rest
     }
 }
 
-// Epilogue of a column-split variance launch: |v|^2 = sum of the S partials in index order, then exactly the
-// epilogue of sigma_acq_kernel (mean from the per-slice partials, sigma, acquisition, dense stores, block arg-max).
+// Epilogue of a column-split variance launch: |v|^2 = sum of the S partials in index order, then the epilogue
+// sigma_acq_kernel calls too (mean from the per-slice partials, sigma, acquisition, dense stores, block arg-max).
 __global__ __launch_bounds__(256) void split_finish_kernel(const double *__restrict__ ss_part, int S, int64_t ldk,
                                                            const double *__restrict__ mu_part, int nsl, int64_t Mc,
                                                            double prior_var, int acq_kind, double p0, double p1,
@@ -483,35 +447,15 @@ __global__ __launch_bounds__(256) void split_finish_kernel(const double *__restr
     const int tid = threadIdx.x, lane = tid & 63;
     const int64_t c = (int64_t)blockIdx.x * 256 + tid;
     const bool valid = c < Mc;
-    double ssq = 0.0, mu = 0.0;
+    double ssq = 0.0, bv;
+    int64_t bi;
     for (int q = 0; q < S; ++q) ssq += ss_part[(int64_t)q * ldk + c];
-    for (int q = 0; q < nsl; ++q) mu += mu_part[(int64_t)q * ldk + c];
-    double var = prior_var - ssq;
-    if (var_pad > 0.0) var = fmax(var, 0.0) + var_pad;
-    const double sigma = sqrt(fabs(var));
-    const double acq = (var_pad > 0.0) ? gpbo_acquisition_ub(acq_kind, mu, sigma, p0, p1) : acquisition(acq_kind, mu, sigma, p0, p1);
-    if (valid) {
-        if (mu_out) mu_out[c] = mu;
-        if (sigma_out) sigma_out[c] = sigma;
-        if (acq_out) acq_out[c] = acq;
-        if (var_out) var_out[c] = var;
-    }
-    const bool is_nan = valid && (acq != acq);
-    const unsigned long long nan_mask = __ballot(is_nan);
-    if (lane == 0 && nan_mask) atomicAdd(nan_count, (unsigned long long)__popcll(nan_mask));
-    double bv = (valid && !is_nan) ? acq : -std::numeric_limits<double>::infinity();
-    int64_t bi = (valid && !is_nan) ? idx_base + c : std::numeric_limits<int64_t>::max();
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bv, off);
-        const int64_t oi = __shfl_xor(bi, off);
-        if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; }
+    gpbo_candidate_epilogue(ssq, mu_part, nsl, ldk, c, valid, prior_var, var_pad, acq_kind, p0, p1, idx_base, mu_out, sigma_out,
+                            acq_out, var_out, lane, nan_count, bv, bi);
+    gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
+        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
         part_val[blockIdx.x] = bv;
         part_idx[blockIdx.x] = bi;
     }
@@ -527,30 +471,22 @@ __global__ __launch_bounds__(256) void acq_argmax_kernel(const double *__restric
     __shared__ double s_val[4];
     __shared__ int64_t s_idx[4];
     const int tid = threadIdx.x, lane = tid & 63;
-    double bv = -std::numeric_limits<double>::infinity();
-    int64_t bi = std::numeric_limits<int64_t>::max();
+    double bv = gpbo_none::val;
+    int64_t bi = gpbo_none::idx;
     unsigned long long nans = 0;
     for (int64_t c = (int64_t)blockIdx.x * 256 + tid; c < M; c += (int64_t)gridDim.x * 256) {
-        const double a = acquisition(acq_kind, mu[c], sigma[c], p0, p1);
+        const double a = gpbo_acquisition(acq_kind, mu[c], sigma[c], p0, p1);
         if (acq_out) acq_out[c] = a;
         if (a != a) ++nans;
-        else if (better(a, idx_base + c, bv, bi)) { bv = a; bi = idx_base + c; }
+        else if (gpbo_better(a, idx_base + c, bv, bi)) { bv = a; bi = idx_base + c; }
     }
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bv, off);
-        const int64_t oi = __shfl_xor(bi, off);
-        nans += __shfl_xor(nans, off);
-        if (better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) {
-        s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi;
-        if (nans) atomicAdd(nan_count, nans);
-    }
+    for (int off = 1; off < 64; off <<= 1) nans += __shfl_xor(nans, off);
+    if (lane == 0 && nans) atomicAdd(nan_count, nans);
+    gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
+        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
         part_val[blockIdx.x] = bv;
         part_idx[blockIdx.x] = bi;
     }
@@ -736,15 +672,14 @@ __global__ __launch_bounds__(256) void qei_kernel(const double *__restrict__ G, 
     if (lane == 0) {
         if (valid && qei_out) qei_out[b] = qei;
         if (valid && nanflag) atomicAdd(nan_count, 1ULL);
-        s_val[wid] = (valid && !nanflag) ? qei : -std::numeric_limits<double>::infinity();
-        s_idx[wid] = (valid && !nanflag) ? batch_base + b : std::numeric_limits<int64_t>::max();
+        s_val[wid] = (valid && !nanflag) ? qei : gpbo_none::val;   // one batch per wave: its record needs no butterfly
+        s_idx[wid] = (valid && !nanflag) ? batch_base + b : gpbo_none::idx;
     }
     __syncthreads();
     if (tid == 0) {
-        double bv = s_val[0];
-        int64_t bi = s_idx[0];
-        for (int w = 1; w < 4; ++w)
-            if (better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
+        double bv;
+        int64_t bi;
+        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
         part_val[blockIdx.x] = bv;
         part_idx[blockIdx.x] = bi;
     }

@@ -356,13 +356,13 @@ __global__ __launch_bounds__(FG) void fps_step_kernel(const double *__restrict__
     __shared__ int64_t s_idx[FG / 64];
     __shared__ double s_c[GPBO_MAX_D];
     __shared__ int s_last;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     const double ninf = -std::numeric_limits<double>::infinity();
     const int64_t member = stt->member;
     if (tid < d) s_c[tid] = stt->centre[tid];
     __syncthreads();
-    double bv = ninf;
-    int64_t bi = std::numeric_limits<int64_t>::max();
+    double bv = gpbo_none::val;
+    int64_t bi = gpbo_none::idx;
     for (int64_t i = (int64_t)blockIdx.x * FG + tid; i < N; i += (int64_t)gridDim.x * FG) {
         double dist = 0.0;
         for (int k = 0; k < d; ++k) {
@@ -380,17 +380,10 @@ __global__ __launch_bounds__(FG) void fps_step_kernel(const double *__restrict__
         }
         if (gpbo_better(m, i, bv, bi)) { bv = m; bi = i; }
     }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bv, off);
-        const int64_t oi = __shfl_xor(bi, off);
-        if (gpbo_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { s_val[w] = bv; s_idx[w] = bi; }
+    gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     __syncthreads();
     if (tid == 0) {
-        for (int q = 1; q < FG / 64; ++q)
-            if (gpbo_better(s_val[q], s_idx[q], bv, bi)) { bv = s_val[q]; bi = s_idx[q]; }
+        gpbo_argmax_fold(s_val, s_idx, FG / 64, bv, bi);
         // The partials are published by a RELEASE on the ticket and read behind an ACQUIRE fence by the workgroup that takes
         // the last one (a proper release / acquire edge instead of relying on the cache policy of sc1 stores).
         // The release writes this XCD's dirty L2 lines back (the running minima just stored): ~1 us per launch, accepted -
@@ -402,24 +395,17 @@ __global__ __launch_bounds__(FG) void fps_step_kernel(const double *__restrict__
     __syncthreads();
     if (s_last) {  // every workgroup's partial has been released: reduce them (the order does not matter: largest value,
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        double v = ninf;   // lowest index among equals) and publish the next member
-        int64_t p = std::numeric_limits<int64_t>::max();
+        double v = gpbo_none::val;   // lowest index among equals) and publish the next member
+        int64_t p = gpbo_none::idx;
         for (unsigned b = tid; b < gridDim.x; b += FG) {
             const double ov = __hip_atomic_load(pval + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int64_t oi = __hip_atomic_load(pidx + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (gpbo_better(ov, oi, v, p)) { v = ov; p = oi; }
         }
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const double ov = __shfl_xor(v, off);
-            const int64_t oi = __shfl_xor(p, off);
-            if (gpbo_better(ov, oi, v, p)) { v = ov; p = oi; }
-        }
-        if (lane == 0) { s_val[w] = v; s_idx[w] = p; }
+        gpbo_argmax_post(v, p, lane, tid >> 6, s_val, s_idx);
         __syncthreads();
         if (tid == 0) {
-            for (int q = 1; q < FG / 64; ++q)
-                if (gpbo_better(s_val[q], s_idx[q], v, p)) { v = s_val[q]; p = s_idx[q]; }
+            gpbo_argmax_fold(s_val, s_idx, FG / 64, v, p);
             if (j < J) perm[j] = p;
             stt->member = p;
             stt->ticket = 0;

@@ -35,7 +35,6 @@ struct TsScale {
     double tl[GPBO_MAX_D];    // 2 pi ls_k
 };
 
-constexpr int64_t kNone = std::numeric_limits<int64_t>::max();
 constexpr int TS_CANDS = 512;          // candidates per workgroup: 256 threads, two adjacent candidates each
 constexpr int TS_GROUP = 16;           // paths per launch row (accumulators per candidate in registers)
 constexpr int TS_GROUP_SMALL = 4;      // ... for S <= 4
@@ -108,7 +107,7 @@ __global__ __launch_bounds__(256) void thompson_paths_kernel(
     __shared__ double tab[GPBO_EXP_E];
     __shared__ double s_val[4][G];
     __shared__ int64_t s_idx[4][G];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     if (tid < GPBO_EXP_E) tab[tid] = kExp2Tab256[tid * (256 / GPBO_EXP_E)];
     const int g0 = blockIdx.y * G;
     const int64_t c0 = ((int64_t)blockIdx.x * 256 + tid) * 2;
@@ -191,26 +190,19 @@ __global__ __launch_bounds__(256) void thompson_paths_kernel(
                 if (lane == 0 && (mask_a | mask_b))
                     atomicAdd(nan_count + s, (unsigned long long)(__popcll(mask_a) + __popcll(mask_b)));
                 const bool use_a = va && !nan_a, use_b = vb && !nan_b;
-                double bv = use_a ? -a : -std::numeric_limits<double>::infinity();
-                int64_t bi = use_a ? idx_offset + c0 : kNone;
+                double bv = use_a ? -a : gpbo_none::val;
+                int64_t bi = use_a ? idx_offset + c0 : gpbo_none::idx;
                 if (use_b && gpbo_better(-b, idx_offset + c0 + 1, bv, bi)) { bv = -b; bi = idx_offset + c0 + 1; }
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const double ov = __shfl_xor(bv, off);
-                    const int64_t oi = __shfl_xor(bi, off);
-                    if (gpbo_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-                }
-                if (lane == 0) { s_val[wid][g] = bv; s_idx[wid][g] = bi; }
+                gpbo_argmax_post(bv, bi, lane, tid >> 6, &s_val[0][g], &s_idx[0][g], G);
             }
         }
     }
     if (!part_val) return;
     gpbo_syncthreads();
-    if (tid < G && g0 + tid < S) {
-        double bv = s_val[0][tid];
-        int64_t bi = s_idx[0][tid];
-        for (int w = 1; w < 4; ++w)
-            if (gpbo_better(s_val[w][tid], s_idx[w][tid], bv, bi)) { bv = s_val[w][tid]; bi = s_idx[w][tid]; }
+    if (tid < G && g0 + tid < S) {   // a thread per path folds the waves' entries of that path
+        double bv;
+        int64_t bi;
+        gpbo_argmax_fold(&s_val[0][tid], &s_idx[0][tid], 4, bv, bi, G);
         part_val[(int64_t)(g0 + tid) * nblk + blockIdx.x] = bv;
         part_idx[(int64_t)(g0 + tid) * nblk + blockIdx.x] = bi;
     }
@@ -226,26 +218,19 @@ __global__ __launch_bounds__(256) void thompson_finish_kernel(const double *__re
     __shared__ int64_t s_idx[4];
     const int tid = threadIdx.x, lane = tid & 63;
     const int64_t s = blockIdx.x;
-    double bv = -std::numeric_limits<double>::infinity();
-    int64_t bi = kNone;
+    double bv = gpbo_none::val;
+    int64_t bi = gpbo_none::idx;
     for (int64_t p = tid; p < nblk; p += 256) {
         const double v = part_val[s * nblk + p];
         const int64_t i = part_idx[s * nblk + p];
         if (gpbo_better(v, i, bv, bi)) { bv = v; bi = i; }
     }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double ov = __shfl_xor(bv, off);
-        const int64_t oi = __shfl_xor(bi, off);
-        if (gpbo_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) { s_val[tid >> 6] = bv; s_idx[tid >> 6] = bi; }
+    gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     gpbo_syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w)
-            if (gpbo_better(s_val[w], s_idx[w], bv, bi)) { bv = s_val[w]; bi = s_idx[w]; }
-        idx_out[s] = (bi == kNone) ? -1 : bi;
-        val_out[s] = (bi == kNone) ? __builtin_nan("") : bv;
+        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
+        idx_out[s] = (bi == gpbo_none::idx) ? -1 : bi;
+        val_out[s] = (bi == gpbo_none::idx) ? __builtin_nan("") : bv;
         nan_out[s] = (int64_t)nan_count[s];
     }
 }

@@ -928,6 +928,40 @@ def test_large_call_column_groups_agree_with_the_ungrouped_kernel_and_the_oracle
     assert np.array_equal(other.sigma.cpu().numpy(), big.sigma.cpu().numpy()) and other.best_idx == big.best_idx
 
 
+def test_large_call_column_groups_break_ties_to_the_lowest_index_and_count_nan():
+    """The epilogue behind the eight column groups (split_finish_kernel) keeps the rules of the plain kernel's: copies of the
+    winning candidate tie bit for bit and the lowest index is selected; candidates with a NaN coordinate are counted and
+    never selected."""
+    X, y, Xs, ls = make_problem(2048, 33000, 8)
+    gp = DeviceGP(chunk=1 << 14).factorise(X, y, ls)
+    winner = gp.score(Xs).best_idx
+    Xs = Xs.copy()
+    Xs[[31000, 9, 20000]] = Xs[winner]
+    tied = gp.score(Xs)
+    assert tied.best_idx == min(9, winner) and tied.nan_count == 0
+    Xs[3 if tied.best_idx != 3 else 4, 2] = np.nan        # (two rows that are neither the winner nor one of its copies)
+    Xs[32999 if tied.best_idx != 32999 else 32998, 5] = np.nan
+    r = gp.score(Xs)
+    assert r.nan_count == 2 and r.best_idx == tied.best_idx and r.best_val == tied.best_val
+
+
+def test_second_acquisition_breaks_ties_to_the_lowest_index_and_counts_nan():
+    """acq_argmax_kernel on dense mu / sigma (no factorisation needed): M = 805 is four workgroups, the last wave partial.
+    The values are the two roundings of NumPy's line, the maximum planted in three workgroups is reported at its lowest
+    row, NaN rows are counted and skipped; with nothing but NaN the result is the empty record."""
+    M, rng = 805, np.random.default_rng(11)
+    mu, sigma = rng.uniform(-1.0, 1.0, M), rng.uniform(0.0, 1.0, M)
+    mu[[700, 70, 300]], sigma[[700, 70, 300]] = -100.0, 8.0     # 4 * 8 + 100 = 132 exactly; every other row is below 5
+    mu[[0, 450, 804]] = np.nan
+    gp = DeviceGP()
+    dev = gp._dev
+    r = gp.acquisition_on_posterior(dev(mu), dev(sigma), acquisition="lcb", explore=4.0, idx_offset=1000)
+    assert np.array_equal(r.acq.cpu().numpy(), 4.0 * sigma - mu, equal_nan=True)
+    assert r.best_idx == 1070 and r.best_val == 132.0 and r.nan_count == 3
+    e = gp.acquisition_on_posterior(dev(np.full(M, np.nan)), dev(sigma), acquisition="lcb", explore=4.0, idx_offset=1000)
+    assert e.nan_count == 805 and e.best_val == -np.inf and e.best_idx == np.iinfo(np.int64).max
+
+
 def test_ard_coordinate_search_d8_n512_logdet_mode_picks_finite_cells():
     """d = 8, N = 512 (BASELINE config 2's surrogate): in the reference's likelihood most cells are -inf here (its determinant
     underflows) and the search returns the first such cell; PointSelector(likelihood="logdet") searches the same axes on
