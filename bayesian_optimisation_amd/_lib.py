@@ -27,6 +27,8 @@ FANTASY_LIE = 1
 REFINE_MAX_P = 4096
 TS_MAX_PATHS = 64
 TS_MAX_FEATURES = 16384
+HYPER_MEAN = 1      # gpbo_nlml_hyper_f64: fit the constant mean
+HYPER_SCALE = 2     # ... and the signal variance
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -126,6 +128,11 @@ SIGNATURES = {
     "gpbo_nlml_grad_workspace_bytes": (_i64, [_i64, _i32]),
     "gpbo_nlml_grad_f64": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _p, _p, _p, _i64, _p]),
     "gpbo_nlml_grad_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _p]),
+    "gpbo_nlml_hyper_workspace_bytes": (_i64, [_i64, _i32]),
+    "gpbo_nlml_hyper_f64": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _f64, _i32, _p, _p, _p, _p, _i64, _p]),
+    "gpbo_nlml_hyper_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _i32, _p]),
+    "gpbo_loo_workspace_bytes": (_i64, [_i64]),
+    "gpbo_loo_f64": (C.c_int, [_p, _p, _p, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p]),
     "gpbo_gemm_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
                                 _i32, _i32, _p]),
 }

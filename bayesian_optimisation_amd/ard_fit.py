@@ -146,3 +146,36 @@ def fit_length_scales(objective, ls0, lower, upper, max_iter: int = 100, gtol: f
     res.pg_norm = float(np.max(np.abs(z - _project(z - g, lo, hi))))
     res.converged = reason in ("gtol", "ftol")
     return res
+
+
+@dataclass
+class HyperFitResult(FitResult):
+    """fit_hyperparameters: the FitResult of the joint fit (ls: the d length scales; pg_norm: over all d + 1 variables) and
+    the rest of the fitted model y ~ N(mean 1, scale^2 (K0(ls) + noise I))."""
+    noise: float = float("nan")     # fitted noise-to-signal ratio rho
+    mean: float = float("nan")      # profiled constant mean m at (ls, noise), in the units of y
+    scale: float = float("nan")     # profiled signal standard deviation s at (ls, noise), in the units of y
+
+
+def fit_hyperparameters(objective, ls0, ls_lower, ls_upper, noise0, noise_lower, noise_upper, **opts) -> HyperFitResult:
+    """Minimise objective(ls, noise) -> (value, gradient [d + 1] with respect to (log ls, log noise), mean, scale^2) over
+    ls_lower <= ls <= ls_upper and noise_lower <= noise <= noise_upper: fit_length_scales on the concatenated positive vector
+    (ls, noise), same method, same options (**opts), same errors.  mean and scale^2 are whatever the objective reports at a
+    point (the package: the closed-form profile values of csrc/hyper.hip); those of the final point are returned."""
+    ls0 = np.asarray(ls0, dtype=np.float64).reshape(-1)
+    d = ls0.size
+    cat = lambda v, s: np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1), [float(s)]])   # noqa: E731
+    if np.asarray(ls_lower).size != d or np.asarray(ls_upper).size != d:
+        raise ValueError("ls0, ls_lower and ls_upper must hold one value per feature")
+    seen = {}
+
+    def joint(v):
+        f, g, mean, scale2 = objective(v[:d].copy(), float(v[d]))
+        seen[v.tobytes()] = (float(mean), float(scale2))
+        return f, g
+
+    r = fit_length_scales(joint, cat(ls0, noise0), cat(ls_lower, noise_lower), cat(ls_upper, noise_upper), **opts)
+    mean, scale2 = seen[np.asarray(r.ls, dtype=np.float64).tobytes()]   # the final point is one that was evaluated
+    return HyperFitResult(ls=r.ls[:d].copy(), nlml=r.nlml, trace=r.trace, n_eval=r.n_eval, n_iter=r.n_iter,
+                          converged=r.converged, reason=r.reason, pg_norm=r.pg_norm, noise=float(r.ls[d]), mean=mean,
+                          scale=float(np.sqrt(scale2)))

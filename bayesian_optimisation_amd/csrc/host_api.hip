@@ -13,6 +13,7 @@
 //   gpbo_nlml_grid_host_f64        = tune_kernel()'s likelihood grid (float32, the reference's det underflow)
 //   gpbo_nlml_grid_logdet_host_f64 = the same grid in fp64 with log det from the factor
 //   gpbo_nlml_grad_host_f64        = the likelihood and its gradient in the log length scales (ard="gradient")
+//   gpbo_nlml_hyper_host_f64       = the likelihood over length scales, noise, signal variance and mean (ard="hyper"; hyper.hip)
 // Every factorising entry reads: own checks, own buffers, Surrogate (below), own calls, own read-backs.
 #include "gpbo_internal.h"
 
@@ -439,4 +440,25 @@ extern "C" int gpbo_nlml_grad_host_f64(const double *X, const double *y, int64_t
     rc = gpbo_nlml_grad_f64(G.U, G.alpha, G.y, G.X, N, G.Np, d, ls, G.info, dout, dwg, wgrad, A.st());
     if (rc != GPBO_OK) return rc;
     return A.d2h(out, dout, sizeof(double) * (1 + d)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+}
+
+extern "C" int gpbo_nlml_hyper_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls, double noise,
+                                        int32_t flags, double *out) {
+    if (!X || !y || !ls || !out || N < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    if (!(noise > 0.0 && noise < __builtin_huge_val()) || (flags & ~(GPBO_HYPER_MEAN | GPBO_HYPER_SCALE))) return GPBO_ERR_ARG;
+    Surrogate G(N, d);
+    const int64_t whyp = gpbo_nlml_hyper_workspace_bytes(G.Np, d);
+    if (whyp < 0) return GPBO_ERR_ARG;
+
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    double *dout = A.alloc<double>(4 + d);
+    char *dwh = A.alloc<char>(whyp);   // (a workspace of its own, as the gradient's; hipMalloc: 256-byte aligned)
+    int rc = G.stage(A, X, y, G.wfact);
+    if (rc != GPBO_OK) return rc;
+    rc = G.factorise(A, ls, noise, 0.0);   // info stays on the device: the finish kernel answers NaN for it
+    if (rc != GPBO_OK) return rc;
+    rc = gpbo_nlml_hyper_f64(G.U, G.alpha, G.y, G.X, N, G.Np, d, ls, noise, flags, G.info, dout, nullptr, dwh, whyp, A.st());
+    if (rc != GPBO_OK) return rc;
+    return A.d2h(out, dout, sizeof(double) * (4 + d)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }

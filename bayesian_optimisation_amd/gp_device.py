@@ -183,7 +183,7 @@ class DeviceGP:
         self.K = self.U = self.alpha = None
         # workspaces, kept from call to call and only ever grown (_workspace)
         self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
-        self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = None
+        self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = self._work_loo = None
         self._epoch = 0              # counts factorise() / append() / load_state_dict(): ThompsonPaths belong to one of them
         self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
         self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
@@ -879,7 +879,7 @@ class DeviceGP:
 
     def select_batch(self, Xs, q: int, acquisition: str = "lcb", explore: float = 4.0, f_best: Optional[float] = None,
                      xi: float = 0.0, fantasy: str = "believer", lie: Optional[float] = None, idx_offset: int = 0,
-                     diag_add: float = 0.0) -> BatchResult:
+                     diag_add: float = 0.0, prior_var: float = PRIOR_VAR) -> BatchResult:
         """q candidates to evaluate in parallel, chosen greedily: the first is score()'s, each further one the arg-max
         after conditioning the surrogate on a fantasy observation at the one before it - its current mean
         (fantasy="believer": Kriging believer, GP-BUCB under LCB) or the constant `lie` (fantasy="liar") - with the members
@@ -893,8 +893,10 @@ class DeviceGP:
         fantasy_params(fantasy, lie)   # (refused before the N^2 pass is spent)
         if not 1 <= int(q) <= min(_lib.BATCH_MAX_Q, M):
             raise ValueError(f"q must be in [1, min({_lib.BATCH_MAX_Q}, M = {M})], got {q}")
-        _, mu, sigma, _ = self.score_async(Xsd, acquisition, explore, f_best, xi, dense=True, idx_offset=idx_offset)
-        return self.select_batch_on_posterior(Xsd, mu, sigma, q, acquisition, explore, f_best, xi, fantasy, lie, idx_offset)
+        _, mu, sigma, _ = self.score_async(Xsd, acquisition, explore, f_best, xi, dense=True, idx_offset=idx_offset,
+                                           prior_var=prior_var)
+        return self.select_batch_on_posterior(Xsd, mu, sigma, q, acquisition, explore, f_best, xi, fantasy, lie, idx_offset,
+                                              prior_var)
 
     # -- Thompson sampling by pathwise posterior samples (csrc/thompson.hip) ---------------------------
     def thompson_paths(self, n_paths: int, n_features: int = 2048, seed: int = 0) -> ThompsonPaths:
@@ -1036,7 +1038,8 @@ class DeviceGP:
         return RefineResult(x=x, acq=vals[0], acq0=vals[1], accepted=accepted, pg=vals[2], best=i, best_val=v, nan_count=n)
 
     def select_refined(self, Xs, n_starts: int = 64, lower=None, upper=None, acquisition: str = "lcb", explore: float = 4.0,
-                       f_best: Optional[float] = None, xi: float = 0.0, iters: int = 30, step0: float = 0.1) -> RefineResult:
+                       f_best: Optional[float] = None, xi: float = 0.0, iters: int = 30, step0: float = 0.1,
+                       prior_var: float = PRIOR_VAR) -> RefineResult:
         """The dense score() of the candidates Xs, then refine() from the n_starts candidates with the largest acquisition
         (stable descending sort: ties keep the lower index first).  lower / upper omitted: the per-feature minimum / maximum
         of Xs.  Returns refine()'s result with grid_idx / grid_val = score()'s arg-max and its value."""
@@ -1049,7 +1052,7 @@ class DeviceGP:
         refine_params(n_starts, self.d, iters, step0)
         if (lower is None) != (upper is None):
             raise ValueError("give both lower and upper, or neither")
-        s = self.score(Xsd, acquisition=acquisition, explore=explore, f_best=f_best, xi=xi, dense=True)
+        s = self.score(Xsd, acquisition=acquisition, explore=explore, f_best=f_best, xi=xi, dense=True, prior_var=prior_var)
         if s.nan_count > 0:
             raise IndexError(NAN_ACQUISITION)
         with torch.cuda.device(self.device):
@@ -1057,7 +1060,7 @@ class DeviceGP:
             starts = Xsd[order].contiguous()
             if lower is None:
                 lower, upper = Xsd.min(dim=0).values.cpu().numpy(), Xsd.max(dim=0).values.cpu().numpy()
-        r = self.refine(starts, lower, upper, acquisition, explore, f_best, xi, iters, step0)
+        r = self.refine(starts, lower, upper, acquisition, explore, f_best, xi, iters, step0, prior_var)
         r.grid_idx, r.grid_val = s.best_idx, s.best_val
         return r
 
@@ -1224,6 +1227,94 @@ class DeviceGP:
         finally:
             if self._fit_bytes() > self.ARD_KEEP_WORKSPACE_BYTES:
                 self._fit_bufs = None
+
+    # -- ML-II over all hyperparameters (ard="hyper"; csrc/hyper.hip) and leave-one-out prediction ---------------------
+    def nlml_hyper(self, X, y, ls, noise: float, fit_mean: bool = True, fit_scale: bool = True):
+        """(L, dL / d(log ls, log noise) [d + 1], mean, scale^2) of the model y ~ N(mean 1, scale^2 (k(X,X) + noise I)) with
+        mean and scale^2 at their closed-form optima (fit_mean / fit_scale False: held at 0 / 1): gpbo_nlml_hyper_f64 on a
+        factorisation of the raw y with (jitter1, jitter2) = (noise, 0) in the fit's own buffers (the surrogate held by this
+        object is not touched).  NaN in every output when the matrix is not positive definite or scale^2 is not positive
+        (one observation, a constant y).  d <= 16."""
+        torch = self.torch
+        Xd, yd = self._dev(X), self._dev(y).reshape(-1)
+        if Xd.dim() != 2:
+            raise ValueError("X must be (N, d)")
+        N, d = int(Xd.shape[0]), int(Xd.shape[1])
+        if d > _lib.MAX_D:
+            raise ValueError(f"the likelihood gradient supports d <= {_lib.MAX_D}, got {d}")
+        if yd.numel() != N:
+            raise ValueError("y must have one value per row of X")
+        ls_h = np.ascontiguousarray(np.asarray(ls, dtype=np.float64).reshape(-1))
+        if ls_h.size != d:
+            raise ValueError(f"length scales: expected {d} values, got {ls_h.size}")
+        if not np.all(ls_h > 0):
+            raise ValueError("length scales must be positive")
+        noise = float(noise)
+        if not (np.isfinite(noise) and noise > 0.0):
+            raise ValueError(f"noise must be positive and finite, got {noise!r}")
+        flags = (_lib.HYPER_MEAN if fit_mean else 0) | (_lib.HYPER_SCALE if fit_scale else 0)
+        Np = int(self.lib.gpbo_padded_n(N))
+        with torch.cuda.device(self.device):
+            fb = self._fit_buffers(Np, d)
+            if "work_hyper" not in fb:
+                wh = int(self.lib.gpbo_nlml_hyper_workspace_bytes(Np, fb["d"]))
+                if wh < 0:
+                    raise _lib.GpboError("gpbo_nlml_hyper_workspace_bytes: invalid sizes")
+                fb["work_hyper"] = torch.empty((wh + 7) // 8, dtype=torch.float64, device=self.device)
+                fb["wh"] = wh
+                fb["out_hyper"] = torch.empty(4 + fb["d"], dtype=torch.float64, device=self.device)
+            lsp = ls_h.ctypes.data_as(C.c_void_p)
+            st = self.lib.gpbo_factorise_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, noise, 0.0, Np,
+                                             self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
+                                             self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
+            _lib.check(st, "gpbo_factorise_f64")
+            st = self.lib.gpbo_nlml_hyper_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N, Np,
+                                              d, lsp, noise, flags, self._ptr(fb["info"]), self._ptr(fb["out_hyper"]), None,
+                                              self._ptr(fb["work_hyper"]), fb["wh"], self._stream())
+            _lib.check(st, "gpbo_nlml_hyper_f64")
+            out = fb["out_hyper"][: 4 + d].cpu().numpy()   # synchronises
+        return float(out[0]), out[1: 2 + d].copy(), float(out[2 + d]), float(out[3 + d])
+
+    def fit_hyperparameters(self, X, y, ls0, ls_lower, ls_upper, noise0: float = 1e-2, noise_lower: float = 1e-6,
+                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, **opts):
+        """ML-II fit of the length scales and the noise-to-signal ratio inside their boxes, mean and signal variance profiled
+        out (ard_fit.fit_hyperparameters: projected L-BFGS in the d + 1 log variables, every evaluation one factorisation and
+        one nlml_hyper).  Returns the HyperFitResult.  The fit's buffers are released afterwards when larger than
+        ARD_KEEP_WORKSPACE_BYTES."""
+        from .ard_fit import fit_hyperparameters
+
+        Xd, yd = self._dev(X), self._dev(y).reshape(-1)   # uploaded once for all evaluations
+        try:
+            return fit_hyperparameters(lambda ls, noise: self.nlml_hyper(Xd, yd, ls, noise, fit_mean, fit_scale), ls0,
+                                       ls_lower, ls_upper, noise0, noise_lower, noise_upper, **opts)
+        finally:
+            if self._fit_bytes() > self.ARD_KEEP_WORKSPACE_BYTES:
+                self._fit_bufs = None
+
+    def loo(self, scale2: float = 1.0):
+        """Leave-one-out prediction of every observation from the factorisation held by this object (gpbo_loo_f64: the diagonal
+        of K^-1 is the row sums of squares of U, so nothing is refitted): device tensors (mu [N], var [N], kinv_diag [N]) in
+        the CALLER's row order (factorise(order="fps") is undone), mu_i = y_i - alpha_i / kinv_diag_i and
+        var_i = scale2 / kinv_diag_i in the units of the y that was factorised.  Enqueues only."""
+        torch = self.torch
+        if self.N < 1:
+            raise _lib.GpboError("loo() needs a factorised surrogate")
+        scale2 = float(scale2)
+        if not (np.isfinite(scale2) and scale2 > 0.0):
+            raise ValueError(f"scale2 must be positive and finite, got {scale2!r}")
+        with torch.cuda.device(self.device):
+            need = int(self.lib.gpbo_loo_workspace_bytes(self.Np))
+            work = self._workspace("_work_loo", need)
+            out = torch.empty((3, self.N), dtype=torch.float64, device=self.device)
+            st = self.lib.gpbo_loo_f64(self._ptr(self.U), self._ptr(self.alpha), self._ptr(self.y), self.N, self.Np, scale2,
+                                       self._ptr(out[0]), self._ptr(out[1]), self._ptr(out[2]), self._ptr(work), need,
+                                       self._stream())
+            _lib.check(st, "gpbo_loo_f64")
+            if self.perm is not None:   # row i of the factorisation is the caller's row perm[i]
+                back = torch.empty_like(out)
+                back[:, self.perm[: self.N]] = out
+                out = back
+        return out[0], out[1], out[2]
 
     # -- dense covariance blocks for inspection (small problems only) --------------------------------------
     def cov_meas_host(self) -> np.ndarray:

@@ -86,9 +86,29 @@ def nlml_and_grad(X, y, ls, jitter: float = JITTER_KERNEL, lib=None):
     return float(out[0]), out[1:].copy()
 
 
+def nlml_hyper(X, y, ls, noise: float, fit_mean: bool = True, fit_scale: bool = True, lib=None):
+    """(L, dL / d(log ls, log noise) [d + 1], mean, scale^2) of y ~ N(mean 1, scale^2 (k(X,X) + noise I)) on host arrays:
+    gpbo_nlml_hyper_host_f64 (factorisation and the kernels of csrc/hyper.hip in one call).  NaN in every output when the
+    matrix is not positive definite or scale^2 is not positive.  d <= 16."""
+    lib = lib or _lib.load()
+    X, y, ls, N, d = _problem(X, y, ls)
+    noise = float(noise)
+    if d > _lib.MAX_D or not (np.isfinite(noise) and noise > 0.0) or not np.all(ls > 0):
+        raise ValueError(f"nlml_hyper needs d <= {_lib.MAX_D}, positive length scales and a positive finite noise")
+    flags = (_lib.HYPER_MEAN if fit_mean else 0) | (_lib.HYPER_SCALE if fit_scale else 0)
+    out = np.empty(4 + d)
+    _lib.note_hip_use()
+    _lib.check(lib.gpbo_nlml_hyper_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), float(noise), flags, _ptr(out)),
+               "gpbo_nlml_hyper_host_f64")
+    return float(out[0]), out[1: 2 + d].copy(), float(out[2 + d]), float(out[3 + d])
+
+
 def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
-                dense: bool = True, want_cov_meas: bool = False, chunk: int = 0, lib=None) -> dict:
-    """One surrogate step on host arrays.  Returns dict(best_val, best_idx, nan_count, info, mu, sigma, acq, cov_meas)."""
+                dense: bool = True, want_cov_meas: bool = False, chunk: int = 0, lib=None,
+                jitter1: float = JITTER_KERNEL, jitter2: float = JITTER_ASSEMBLY, diag_add=None) -> dict:
+    """One surrogate step on host arrays.  Returns dict(best_val, best_idx, nan_count, info, mu, sigma, acq, cov_meas).
+    jitter1 / jitter2: the two diagonal terms of the factorised matrix (prior variance (1 + jitter1) + jitter2); diag_add:
+    None for the reference's N == M rule, or the value itself."""
     lib = lib or _lib.load()
     X, y, ls, Xs, N, d, M = _problem(X, y, ls, Xs)
     kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
@@ -97,10 +117,11 @@ def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_
     acq = np.empty(M) if dense else None
     cov = np.empty((N, N)) if want_cov_meas else None
     out = _Result()
-    diag_add = JITTER_KERNEL if Xs.shape == X.shape else 0.0          # point_selector.py:173 shape-coincidence quirk
+    if diag_add is None:
+        diag_add = JITTER_KERNEL if Xs.shape == X.shape else 0.0      # point_selector.py:173 shape-coincidence quirk
     _lib.note_hip_use()
-    st = lib.gpbo_select_next_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M,
-                                       kind, p0, p1, diag_add, int(chunk), _ptr(mu), _ptr(sigma), _ptr(acq), _ptr(cov),
+    st = lib.gpbo_select_next_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), float(jitter1), float(jitter2), _ptr(Xs), M,
+                                       kind, p0, p1, float(diag_add), int(chunk), _ptr(mu), _ptr(sigma), _ptr(acq), _ptr(cov),
                                        out.res_ptr, out.info_ptr)
     _lib.check(st, "gpbo_select_next_host_f64")
     return dict(out.decode(), mu=mu, sigma=sigma, acq=acq, cov_meas=cov)
@@ -196,8 +217,8 @@ def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: fl
 
 
 class _GridOnly:
-    """What PointSelector.tune_kernel needs from its surrogate object: the likelihood grid (ard="grid") or the likelihood
-    and its gradient (ard="gradient")."""
+    """What PointSelector.tune_kernel needs from its surrogate object: the likelihood grid (ard="grid"), the likelihood
+    and its gradient (ard="gradient") or the likelihood over all hyperparameters (ard="hyper")."""
 
     def __init__(self, lib):
         self.lib = lib
@@ -214,12 +235,28 @@ class _GridOnly:
         X, y = _f64(X), _f64(y).reshape(-1)
         return fit_length_scales(lambda ls: self.nlml_and_grad(X, y, ls, jitter), ls0, lower, upper, **opts)
 
+    def nlml_hyper(self, X, y, ls, noise, fit_mean: bool = True, fit_scale: bool = True):
+        return nlml_hyper(X, y, ls, noise, fit_mean, fit_scale, self.lib)
+
+    def fit_hyperparameters(self, X, y, ls0, ls_lower, ls_upper, noise0: float = 1e-2, noise_lower: float = 1e-6,
+                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, **opts):
+        from .ard_fit import fit_hyperparameters
+
+        X, y = _f64(X), _f64(y).reshape(-1)
+        return fit_hyperparameters(lambda ls, noise: self.nlml_hyper(X, y, ls, noise, fit_mean, fit_scale), ls0, ls_lower,
+                                   ls_upper, noise0, noise_lower, noise_upper, **opts)
+
+
+_HostFit = _GridOnly   # (the likelihood side of the host route: grid, gradient fit, hyperparameter fit)
+
 
 class PointSelectorHost(PointSelector):
     """`PointSelector` with the same attribute protocol (point_selector.py:13-207), on the host-pointer entry points."""
 
-    def __init__(self, verbose: bool = False, chunk: int = 0, likelihood: str = "reference", ard: str = "grid"):
-        super().__init__(device=None, verbose=verbose, shard_candidates=False, likelihood=likelihood, ard=ard)
+    def __init__(self, verbose: bool = False, chunk: int = 0, likelihood: str = "reference", ard: str = "grid",
+                 noise0: float = 1e-2, noise_bounds=(1e-6, 1.0)):
+        super().__init__(device=None, verbose=verbose, shard_candidates=False, likelihood=likelihood, ard=ard, noise0=noise0,
+                         noise_bounds=noise_bounds)
         self.lib = _lib.load()
         self._gp = _GridOnly(self.lib)
         self._chunk = int(chunk)
@@ -239,8 +276,26 @@ class PointSelectorHost(PointSelector):
 
     def _score(self, acquisition, want_cov_meas=False, **kw):
         X, y, ls, Xs = self._inputs
-        return self._factorised(select_next(X, y, ls, Xs, acquisition=acquisition, dense=True, want_cov_meas=want_cov_meas,
-                                            chunk=self._chunk, lib=self.lib, **kw))
+        if self._ard != "hyper":
+            return self._factorised(select_next(X, y, ls, Xs, acquisition=acquisition, dense=True,
+                                                want_cov_meas=want_cov_meas, chunk=self._chunk, lib=self.lib, **kw))
+        # the fitted model: (y - m) / s under K = k(X,X) + rho I, no N == M quirk; in and out in the units of y
+        r = self._factorised(select_next(X, self._to_model(y), ls, Xs, acquisition=acquisition, dense=True,
+                                         want_cov_meas=want_cov_meas, chunk=self._chunk, lib=self.lib, jitter1=self.noise,
+                                         jitter2=0.0, diag_add=0.0, **self._acq_kw(kw)))
+        r["mu"] = self.y_mean + self.y_scale * r["mu"]
+        r["sigma"] = self.y_scale * r["sigma"]
+        r["acq"] = self._acq_to_y(acquisition, r["acq"])
+        r["best_val"] = float(self._acq_to_y(acquisition, r["best_val"]))
+        return r
+
+    def _not_in_hyper_mode(self, what: str):
+        if self._ard == "hyper":
+            raise ValueError(f"PointSelectorHost(ard='hyper') supports update_surrogate(), lower_confidence_bound() and "
+                             f"expected_improvement(); {what} needs PointSelector")
+
+    def loo(self):
+        raise ValueError("loo() needs PointSelector (the factorisation does not outlive a host-pointer call)")
 
     def update_surrogate(self):
         """point_selector.py:42-102."""
@@ -276,6 +331,7 @@ class PointSelectorHost(PointSelector):
     def q_expected_improvement(self, n_samples=512, seed=7, xi=0.0):
         """q = 8 Monte-Carlo Expected Improvement on the host-pointer route (same definition and return value as
         PointSelector.q_expected_improvement: the (8, ndim) multi-indices of the first batch with the largest qEI)."""
+        self._not_in_hyper_mode("q_expected_improvement()")
         X, y, ls, Xs = self._surrogate_inputs()
         fd = [int(v) for v in self.feature_domain]
         M = int(np.prod(fd))
@@ -292,6 +348,7 @@ class PointSelectorHost(PointSelector):
     def select_batch(self, q, acquisition="lcb", explore=4, xi=0.0, fantasy="believer", lie=None):
         """PointSelector.select_batch on the host-pointer route (gpbo_select_batch_host_f64: factorisation, plain pass and
         selection in one call): the same (q, ndim) multi-indices, the same errors."""
+        self._not_in_hyper_mode("select_batch()")
         X, y, ls, Xs = self._surrogate_inputs()
         if Xs.shape == X.shape:
             raise ValueError("select_batch() does not support candidates of the observations' shape (the N == M quirk)")
@@ -304,6 +361,7 @@ class PointSelectorHost(PointSelector):
     def select_thompson(self, q, n_features=2048, seed=0):
         """PointSelector.select_thompson on the host-pointer route (gpbo_thompson_host_f64): the same (k, ndim) multi-indices
         for the same seed, the same errors."""
+        self._not_in_hyper_mode("select_thompson()")
         X, y, ls, Xs = self._surrogate_inputs()
         r = self._factorised(select_thompson(X, y, ls, Xs, q, n_features=n_features, seed=seed, lib=self.lib))
         return self._batch_indices(r["indices"], int(np.sum(r["nan_counts"])))
@@ -311,6 +369,7 @@ class PointSelectorHost(PointSelector):
     def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
         """PointSelector.refine_next on the host-pointer route (gpbo_refine_host_f64): the same d coordinates, the same
         errors."""
+        self._not_in_hyper_mode("refine_next()")
         X, y, ls, _ = self._surrogate_inputs()
         kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
         r = self._factorised(refine(X, y, ls, starts, lo, hi, iters=int(iters), lib=self.lib, **kw))

@@ -31,7 +31,9 @@ Differences from the reference, all deliberate:
     `incremental=True` / `state_path=...` (append new observations to the previous factorisation in O(N^2)
     while the length scales stay the same, within one process or across jobs through a state file), and
     `ard="gradient"` (fit the length scales by maximising the marginal likelihood with its gradient instead of the grid
-    search; INTEGRATION.md "ARD fit modes").
+    search; INTEGRATION.md "ARD fit modes"), and `ard="hyper"` (fit noise, signal variance and a constant mean together with
+    the length scales; every attribute and acquisition value is then in the units of `measured_vals`: INTEGRATION.md
+    "Fitting the whole model").
 There is no CPU implementation behind this class.
 """
 from __future__ import annotations
@@ -39,7 +41,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import distributed as D
-from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, NAN_ACQUISITION, DeviceGP
+from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, NAN_ACQUISITION, PRIOR_VAR, DeviceGP
 
 COV_PRED_MAX_M = 4096          # cov_pred is M x M: 128 MiB at this size
 COV_MEAS_PRED_MAX = 1 << 24    # entries of the (M, N) cross covariance kept for inspection
@@ -63,7 +65,7 @@ def _plot_hooks():
 class PointSelector:
     def __init__(self, device=None, verbose: bool = False, shard_candidates: bool = True, precision: str = "fp64",
                  incremental: bool = False, state_path=None, dense_outputs: bool = True, likelihood: str = "reference",
-                 ard: str = "grid"):
+                 ard: str = "grid", noise0: float = 1e-2, noise_bounds=(1e-6, 1.0)):
         # attribute protocol of point_selector.py:15-40
         self.feature_domain = None
         self.predicted_pts = None
@@ -99,10 +101,30 @@ class PointSelector:
         # ard="grid" (default): tune_kernel searches the length-scale grid as the reference does (point_selector.py:104-163);
         # "gradient" (not in the reference): ML-II fit of all d length scales at once inside the box the search axes span,
         # projected L-BFGS on the fp64 log-det likelihood and its gradient (ard_fit.py, csrc/ard_grad.hip)
-        if ard not in ("grid", "gradient"):
-            raise ValueError("ard must be 'grid' (the reference's grid search) or 'gradient' (ML-II fit of the length scales)")
+        # "hyper" (not in the reference, whose model is frozen at unit signal variance, zero mean and a diagonal term of
+        # 1e-4 + 1e-6): the same fit over d + 1 variables - the length scales and the noise-to-signal ratio rho, started at
+        # noise0 inside noise_bounds - with the constant mean m and the signal variance s^2 at their closed-form optima
+        # (csrc/hyper.hip).  The surrogate is then the GP of (y - m) / s with K = k(X,X) + rho I and prior variance 1 + rho,
+        # and everything this class reports is mapped back to the units of y.
+        if ard not in ("grid", "gradient", "hyper"):
+            raise ValueError("ard must be 'grid' (the reference's grid search), 'gradient' (ML-II fit of the length scales) or "
+                             "'hyper' (ML-II fit of length scales, noise, signal variance and mean)")
         self._ard = ard
-        self.last_fit = None           # ard="gradient": the last fit (ard_fit.FitResult.as_dict())
+        nlo, nhi = (float(v) for v in noise_bounds)
+        if not (0.0 < nlo <= nhi < np.inf) or not nlo <= float(noise0) <= nhi:
+            raise ValueError("noise_bounds must satisfy 0 < lower <= upper < inf and hold noise0")
+        self._noise0, self._noise_bounds = float(noise0), (nlo, nhi)
+        if ard == "hyper":
+            if precision != "fp64":
+                raise ValueError("ard='hyper' needs precision='fp64' (the screens are tuned to the reference's prior variance)")
+            if incremental or state_path is not None:
+                raise ValueError("ard='hyper' refits the model at every update: incremental / state_path are not available")
+            if not dense_outputs:
+                raise ValueError("ard='hyper' needs dense_outputs=True (the prefix bound assumes the reference's jitters)")
+        self.noise = None              # ard="hyper": fitted noise-to-signal ratio rho (noise variance = rho y_scale^2)
+        self.y_mean = None             # ard="hyper": fitted constant mean m, in the units of measured_vals
+        self.y_scale = None            # ard="hyper": fitted signal standard deviation s, in the units of measured_vals
+        self.last_fit = None           # ard="gradient" / "hyper": the last fit (ard_fit.FitResult.as_dict())
         # dense_outputs=False (not in the reference): a caller that needs the next point only.  mean_func / cov_func /
         # acq_func_eval stay None and the acquisition calls return the same multi-index through the exact prefix bound
         # (DeviceGP.score_bound: fp64 branch and bound, the full pass when the bound does not separate the candidates).
@@ -184,10 +206,16 @@ class PointSelector:
 
         ls = self._select_kernel_params(X)
 
-        self._factorise_or_append(gp, X, y, ls)                           # :79, :89 (raises LinAlgError)
+        hyper = self._ard == "hyper"
+        if hyper:
+            # the fitted model: the GP of (y - m) / s with K = k(X,X) + rho I; the N == M quirk is a reference artefact
+            gp.factorise(X, self._to_model(y), ls, self.noise, 0.0, check=True, order="arrival")
+            self.last_update = "factorise"
+        else:
+            self._factorise_or_append(gp, X, y, ls)                       # :79, :89 (raises LinAlgError)
 
         M, N = len(Xs), len(X)
-        diag_add = JITTER_KERNEL if Xs.shape == X.shape else 0.0          # :173 shape-coincidence quirk
+        diag_add = JITTER_KERNEL if Xs.shape == X.shape and not hyper else 0.0   # :173 shape-coincidence quirk
         world, rank = self._world()
         lo, hi = D.shard_bounds(M, world, rank)
         if not self._dense:
@@ -210,11 +238,15 @@ class PointSelector:
         else:
             self._screen_ctx = None
             self._xs_dev = gp._dev(Xs[lo:hi])
-            res = gp.score(self._xs_dev, acquisition="lcb", explore=4.0, dense=True, idx_offset=lo, diag_add=diag_add)
-        self._mu_dev, self._sigma_dev = res.mu, res.sigma
+            res = gp.score(self._xs_dev, acquisition="lcb", explore=4.0, dense=True, idx_offset=lo, diag_add=diag_add,
+                           prior_var=self._prior_var())
+        self._mu_dev, self._sigma_dev = res.mu, res.sigma                 # (ard="hyper": in model units)
         best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
         # sharded: the three dense arrays are gathered on the device (one collective), then copied to the host once
         mu, sigma, acq = (t.cpu().numpy() for t in D.gather_concat_tensors([res.mu, res.sigma, res.acq], M))
+        if hyper:
+            mu, sigma, acq = self.y_mean + self.y_scale * mu, self.y_scale * sigma, self._acq_to_y("lcb", acq)
+            best = (float(self._acq_to_y("lcb", best[0])),) + tuple(best[1:])
         fd = [int(v) for v in self.feature_domain]
         self.mean_func = mu.reshape(fd)                                   # :97
         self.cov_func = sigma.reshape(fd)                                 # :98 (a standard deviation)
@@ -229,13 +261,47 @@ class PointSelector:
         if M * N <= COV_MEAS_PRED_MAX:
             self._lazy["cov_meas_pred"] = lambda: gp.cov_meas_pred_host(Xs, diag_add)
         if M <= COV_PRED_MAX_M:
-            self._lazy["cov_pred"] = lambda: gp.kxx_host(Xs, ls, JITTER_KERNEL, JITTER_ASSEMBLY)
+            j1, j2 = (self.noise, 0.0) if hyper else (JITTER_KERNEL, JITTER_ASSEMBLY)
+            self._lazy["cov_pred"] = lambda: gp.kxx_host(Xs, ls, j1, j2)
 
         self.measured_pts = self.measured_pts.tolist()                    # :101-102
         self.measured_vals = self.measured_vals.tolist()
 
+    # -- ard="hyper": the units of y <-> the units of the model (the GP of (y - y_mean) / y_scale) -----------------------
+    def _to_model(self, v):
+        return (np.asarray(v, dtype=np.float64) - self.y_mean) / self.y_scale
+
+    def _prior_var(self) -> float:
+        """Diagonal of cov_pred: the reference's (1 + 1e-4) + 1e-6, or 1 + rho of the fitted model (the same meaning: the
+        variance of an OBSERVATION at a point nothing is known about)."""
+        return 1.0 + self.noise if self._ard == "hyper" else PRIOR_VAR
+
+    def _acq_kw(self, kw: dict) -> dict:
+        """Acquisition keywords given in the units of y, as the kernels take them: EI's f_best and xi are standardised."""
+        if self._ard != "hyper":
+            return kw
+        kw = dict(kw)
+        if kw.get("f_best") is not None:
+            kw["f_best"] = float(self._to_model(kw["f_best"]))
+        if "xi" in kw:
+            kw["xi"] = float(kw["xi"]) / self.y_scale
+        return kw
+
+    def _acq_to_y(self, kind, acq):
+        """Acquisition values of the model in the units of y: LCB = s acq - m (explore s sigma - (m + s mu)), EI / qEI = s acq.
+        Both maps increase, so the arg-max and its tie rule are those of the kernels."""
+        if self._ard != "hyper":
+            return acq
+        return self.y_scale * acq - self.y_mean if kind == "lcb" else self.y_scale * acq
+
     def _select_kernel_params(self, X) -> np.ndarray:
         """point_selector.py:60-73: preset, ARD grid search (n > 1) or the middle of each length-scale axis."""
+        if self._ard == "hyper" and self._preset_kernel_params:
+            raise ValueError("ard='hyper' fits the length scales with the rest of the model: set_kernel_params() is not available")
+        if self._ard == "hyper" and len(X[:, 0]) < 2:
+            # nothing to fit from one observation: the mean is that observation, unit scale, the starting noise
+            self.noise, self.y_mean, self.y_scale = self._noise0, float(np.asarray(self.measured_vals, dtype=np.float64)[0]), 1.0
+            self.last_fit = None
         if self._preset_kernel_params:
             pass
         elif len(X[:, 0]) > 1:                                           # :60
@@ -329,7 +395,7 @@ class PointSelector:
         plot2, plot1 = _plot_hooks()
         if self._gp is None:
             self._gp = DeviceGP(self._device)
-        if self._ard == "gradient":
+        if self._ard in ("gradient", "hyper"):
             self._fit_kernel(X, y)
             return
         if self._ls_cells is not None:
@@ -410,11 +476,20 @@ class PointSelector:
             lower = np.array([a.min() for a in axes])
             upper = np.array([a.max() for a in axes])
             ls0 = np.array([a[len(a) // 2] for a in axes])
-        res = self._gp.fit_length_scales(X, y, ls0, lower, upper)
+        if self._ard == "hyper":
+            # the same box and start for the length scales; the noise-to-signal ratio joins them, mean and scale are profiled
+            if np.ptp(y) == 0.0:
+                raise np.linalg.LinAlgError("the likelihood is not finite: constant measured_vals leave no signal variance to fit")
+            res = self._gp.fit_hyperparameters(X, y, ls0, lower, upper, self._noise0, *self._noise_bounds)
+            self.noise, self.y_mean, self.y_scale = float(res.noise), float(res.mean), float(res.scale)
+        else:
+            res = self._gp.fit_length_scales(X, y, ls0, lower, upper)
         self.kernel_params = np.asarray(res.ls, dtype=np.float64).reshape(shape)
         self.hyperparam_obj = [float(v) for v in res.trace]
         self.nlogml = np.asarray(res.trace, dtype=np.float64)
         self.last_fit = res.as_dict()
+        if self._ard == "hyper":
+            self.last_fit.update(y_mean=self.y_mean, y_scale=self.y_scale)
         self._log(f"ARD fit: {res.reason} after {res.n_iter} steps / {res.n_eval} evaluations, nlml {res.nlml:.12g}")
 
     # ------------------------------------------------------------------------------------------
@@ -436,10 +511,10 @@ class PointSelector:
                 self.last_screen = dict(self._gp.last_screen, sigma_abs_tol=SCREEN_SIGMA_TOL[self._precision])
             else:
                 res = self._gp.acquisition_on_posterior(self._mu_dev, self._sigma_dev, acquisition=kind,
-                                                        idx_offset=lo, **kw)
+                                                        idx_offset=lo, **self._acq_kw(kw))
             best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
-            acq = D.gather_concat_tensors([res.acq], int(np.prod(fd)))[0].cpu().numpy()
-            self._cached[key] = (acq.reshape(fd), best)
+            acq = self._acq_to_y(kind, D.gather_concat_tensors([res.acq], int(np.prod(fd)))[0].cpu().numpy())
+            self._cached[key] = (acq.reshape(fd), (float(self._acq_to_y(kind, best[0])),) + tuple(best[1:]))
         acq, (best_val, best_idx, nan_count) = self._cached[key]
         self.acq_func_eval = acq
         if nan_count > 0 or best_idx >= int(np.prod(fd)):
@@ -470,9 +545,11 @@ class PointSelector:
         Xs = np.asarray(self.predicted_pts, dtype=np.float64)
         world, rank = self._world()
         blo, bhi = D.shard_bounds(M // 8, world, rank)          # whole batches per rank, contiguous
-        res = self._gp.score_qei(Xs[blo * 8: bhi * 8], Z, f_best, xi=float(xi), dense=True, batch_offset=blo)
+        kw = self._acq_kw(dict(f_best=f_best, xi=float(xi)))
+        res = self._gp.score_qei(Xs[blo * 8: bhi * 8], Z, kw["f_best"], xi=kw["xi"], dense=True, batch_offset=blo,
+                                 prior_var=self._prior_var())
         best_val, best_idx, nan_count = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
-        qei = D.gather_concat_tensors([res.acq], M // 8)[0].cpu().numpy()
+        qei = self._acq_to_y("qei", D.gather_concat_tensors([res.acq], M // 8)[0].cpu().numpy())
         self.acq_func_eval = qei
         if nan_count > 0 or best_idx >= M // 8:
             raise IndexError(NAN_ACQUISITION)
@@ -515,10 +592,12 @@ class PointSelector:
             raise ValueError("select_batch() does not support candidates of the observations' shape (the N == M quirk)")
         if self._world()[0] > 1:
             raise NotImplementedError("select_batch() with candidates sharded over several ranks is not implemented")
-        kw = self._batch_acq(acquisition, explore, xi)
+        kw = self._acq_kw(self._batch_acq(acquisition, explore, xi))
+        if self._ard == "hyper" and lie is not None and np.isfinite(float(lie)):
+            lie = float(self._to_model(lie))   # a fantasy observation is a value of y
         # the candidates update_surrogate() left on the device: no second upload of M x d values
         r = self._gp.select_batch_on_posterior(self._xs_dev, self._mu_dev.clone(), self._sigma_dev.clone(), int(q),
-                                               fantasy=fantasy, lie=lie, **kw)
+                                               fantasy=fantasy, lie=lie, prior_var=self._prior_var(), **kw)
         return self._batch_indices(r.indices, r.nan_count)
 
     def select_thompson(self, q, n_features=2048, seed=0):
@@ -581,10 +660,25 @@ class PointSelector:
         acquisition contains NaN.  With sharded candidates every rank refines the same global starts on the replicated
         factorisation (same bits on every rank, no collective)."""
         kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
-        r = self._gp.refine(starts, lo, hi, iters=int(iters), **kw)
+        r = self._gp.refine(starts, lo, hi, iters=int(iters), prior_var=self._prior_var(), **self._acq_kw(kw))
         if r.nan_count > 0 or r.best < 0:
             raise IndexError(NAN_ACQUISITION)
         return r.x[r.best].cpu().numpy().astype(np.float64)
+
+    def loo(self):
+        """Not in the reference: leave-one-out prediction of every observation from the surrogate of the last
+        update_surrogate() - (mean [N], standard deviation [N], standardised residual [N]) as host arrays in the order of
+        measured_pts, in the units of measured_vals.  Nothing is refitted: the diagonal of K^-1 comes from the factor
+        (DeviceGP.loo).  The standard deviation is that of a NOISY observation at the left-out point (the model's K holds the
+        noise), which is what the left-out value is compared with.  With ard="hyper" the residuals of a well-specified model are
+        unit normal; the frozen model of the other modes is only calibrated for data that are already standardised."""
+        if self._cached is None:
+            raise RuntimeError("call update_surrogate() first")
+        m, s = (self.y_mean, self.y_scale) if self._ard == "hyper" else (0.0, 1.0)
+        mu, var, _ = self._gp.loo(1.0)
+        mean = m + s * mu.cpu().numpy()
+        sd = s * np.sqrt(var.cpu().numpy())
+        return mean, sd, (np.asarray(self.measured_vals, dtype=np.float64).reshape(-1) - mean) / sd
 
     def expected_improvement(self, xi=0.0):
         """Not in the reference (docs/README.md:363-365 'future work'): EI for minimisation,

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -543,6 +543,41 @@ int gpbo_nlml_grad_f64(const double *U, const double *alpha, const double *y, co
                        void *stream);
 int gpbo_nlml_grad_host_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
                             double jitter, double *out_host);
+
+/* ML-II over ALL hyperparameters (ard="hyper"; not in the reference, whose model is frozen at unit signal variance, zero mean and a
+ * diagonal term of 1e-4 + 1e-6: point_selector.py:78-79, :193).  Model: y ~ N(m 1, s^2 Kt), Kt = K0(ls) + noise I, noise > 0 the
+ * noise-to-signal ratio; mean and scale are profiled out in closed form, so the optimiser sees log ls and log noise.  From a
+ * factorisation made by gpbo_factorise_f64 with (jitter1, jitter2) = (noise, 0) and the RAW y - U, alpha = a = Kt^-1 y, info -
+ * and b = Kt^-1 1 (computed inside the call):
+ *   m = (1 . a) / (1 . b) with GPBO_HYPER_MEAN, else 0;  r = y - m;  alpha' = a - m b;
+ *   s^2 = (r . alpha') / N with GPBO_HYPER_SCALE, else 1;
+ *   out[0]         = L = 1/2 [(r . alpha') / s^2 + N log s^2 + log det Kt + N log 2 pi]
+ *   out[1 + k]     = dL / dlog ls_k = 1/2 sum_ij W_ij K0_ij (x_ik - x_jk)^2 / ls_k^2,  W = Kt^-1 - alpha' alpha'^T / s^2,  k < d
+ *   out[1 + d]     = dL / dlog noise = 1/2 noise (tr Kt^-1 - |alpha'|^2 / s^2),  tr Kt^-1 = sum_i sum_{j >= i} U_ij^2 over rows i < N
+ *   out[2 + d]     = m;   out[3 + d] = s^2
+ * out: [d + 4] doubles, device; every entry NaN when *info != 0, when 1 . b is not positive and finite or when s^2 is not (one
+ * observation with both flags, a constant y).  alpha_std_out: optional [Np], receives alpha' / s (zero on the padding) - the
+ * alpha of a factorisation of (y - m) / s with the same U.  The length-scale gradients come from gpbo_nlml_grad_f64 on
+ * (alpha' / s, r / s).  Np = gpbo_padded_n(N), 1 <= d <= GPBO_MAX_D, ls > 0, noise positive and finite, flags a combination of the
+ * two bits, U and work 16-byte aligned (GPBO_ERR_ARG otherwise, before any launch);  work: gpbo_nlml_hyper_workspace_bytes(Np, d)
+ * bytes (negative: invalid sizes; GPBO_ERR_WORKSPACE when too small).  Enqueues only, never synchronises; no atomics, every sum
+ * in a fixed order: two calls give the same bits.
+ * gpbo_nlml_hyper_host_f64: factorisation + the above on host arrays in one call (out_host [d + 4]).
+ * gpbo_loo_f64: leave-one-out prediction from a factorisation (U, alpha) of y: kappa_i = (K^-1)_ii = sum_{j >= i} U_ij^2,
+ *   mu_out[i] = y_i - alpha_i / kappa_i, var_out[i] = scale2 / kappa_i, kinv_diag_out[i] = kappa_i; each output optional [N];
+ *   scale2 positive and finite; work: gpbo_loo_workspace_bytes(Np) bytes, 16-byte aligned. */
+#define GPBO_HYPER_MEAN 1  /* fit the constant mean m */
+#define GPBO_HYPER_SCALE 2 /* fit the signal variance s^2 */
+int64_t gpbo_nlml_hyper_workspace_bytes(int64_t Np, int32_t d);
+int gpbo_nlml_hyper_f64(const double *U, const double *alpha, const double *y, const double *X, int64_t N, int64_t Np,
+                        int32_t d, const double *ls_host, double noise, int32_t flags, const int32_t *info,
+                        double *out /* [d + 4] */, double *alpha_std_out /* optional [Np] */, void *work, int64_t work_bytes,
+                        void *stream);
+int gpbo_nlml_hyper_host_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
+                             double noise, int32_t flags, double *out_host /* [d + 4] */);
+int64_t gpbo_loo_workspace_bytes(int64_t Np);
+int gpbo_loo_f64(const double *U, const double *alpha, const double *y, int64_t N, int64_t Np, double scale2, double *mu_out,
+                 double *var_out, double *kinv_diag_out, void *work, int64_t work_bytes, void *stream);
 
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;
