@@ -29,6 +29,17 @@ TS_MAX_PATHS = 64
 TS_MAX_FEATURES = 16384
 HYPER_MEAN = 1      # gpbo_nlml_hyper_f64: fit the constant mean
 HYPER_SCALE = 2     # ... and the signal variance
+# covariance families of the gpbo_*_kern_f64 entry points (include/gpbo.h: GPBO_KERNEL_*)
+KERNEL_IDS = {"se": 0, "matern32": 1, "matern52": 2}
+
+
+def kernel_id(kernel: str) -> int:
+    """GPBO_KERNEL_* of a family by name; ValueError for anything else."""
+    try:
+        return KERNEL_IDS[kernel]
+    except (KeyError, TypeError):
+        raise ValueError(f"kernel must be one of {sorted(KERNEL_IDS)}, got {kernel!r}") from None
+
 
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -133,6 +144,18 @@ SIGNATURES = {
     "gpbo_nlml_hyper_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _f64, _i32, _p]),
     "gpbo_loo_workspace_bytes": (_i64, [_i64]),
     "gpbo_loo_f64": (C.c_int, [_p, _p, _p, _i64, _i64, _f64, _p, _p, _p, _p, _i64, _p]),
+    # the Matern families: each is its twin above with `int32_t kernel` after ls_host
+    "gpbo_kxx_kern_f64": (C.c_int, [_p, _i64, _i32, _p, _i32, _f64, _f64, _p, _i64, _p]),
+    "gpbo_kstar_mu_kern_f64": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _i32, _p, _f64, _i64, _p, _i64, _p, _p]),
+    "gpbo_factorise_kern_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _f64, _f64, _i64, _p, _p, _p, _p, _p, _i64, _p]),
+    "gpbo_posterior_acq_kern_f64": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _i32, _p, _p, _f64, _i32, _f64, _f64, _f64,
+                                              _i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
+    "gpbo_nlml_grad_kern_f64": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _i32, _p, _p, _p, _i64, _p]),
+    "gpbo_nlml_hyper_kern_f64": (C.c_int, [_p, _p, _p, _p, _i64, _i64, _i32, _p, _i32, _f64, _i32, _p, _p, _p, _p, _i64, _p]),
+    "gpbo_select_next_host_kern_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _f64, _f64, _p, _i64, _i32, _f64, _f64, _f64,
+                                                 _i64, _p, _p, _p, _p, _p, _p]),
+    "gpbo_nlml_grad_host_kern_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _f64, _p]),
+    "gpbo_nlml_hyper_host_kern_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _f64, _i32, _p]),
     "gpbo_gemm_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
                                 _i32, _i32, _p]),
 }

@@ -18,6 +18,9 @@
 // off-diagonal tiles counted twice; the workgroup's d sums go to its own slot of a slab in the workspace.
 // nlml_grad_finish_kernel (one workgroup) adds the slab in a fixed order and writes out[0] = NLML, out[1 + k] = the
 // gradient: no atomics, so two calls give the same bits.  info != 0 (K not positive definite): every output NaN.
+// Other covariance families (gpbo_nlml_grad_kern_f64): dk / dlog l_k = g(r) (x_ik - x_jk)^2 / l_k^2 with g = k for the squared
+// exponential, 3 exp(-a) for Matern 3/2 and 5/3 (1 + a) exp(-a) for Matern 5/2, so only the factor the epilogue regenerates
+// changes; in the scaled coordinates s = r^2 / 2, a = sqrt(6 s) or sqrt(10 s).  Nothing is divided by r.
 #include "gpbo_internal.h"
 #include "exp_neg.h"
 
@@ -36,10 +39,24 @@ __device__ __forceinline__ void tile_of(int64_t t, int &I, int &J) {
     J = (int)(t - (int64_t)i * (i + 1) / 2);
 }
 
-template <int D>
-__global__ __launch_bounds__(256) void nlml_grad_kernel(const double *__restrict__ U, const double *__restrict__ alpha,
-                                                        const double *__restrict__ Xsc, int N, int Np,
-                                                        double *__restrict__ slab) {
+// g(r) of the family from s = r^2 / 2 (see the header)
+template <int KERN>
+__device__ __forceinline__ double dlog_factor(double s, const double *tab) {
+    if constexpr (KERN == GPBO_KERNEL_SE) {
+        return exp_neg(s, tab);
+    } else if constexpr (KERN == GPBO_KERNEL_MATERN32) {
+        return 3.0 * exp_neg(sqrt_nonneg(6.0 * s), tab);
+    } else {
+        const double a = sqrt_nonneg(10.0 * s);
+        return (5.0 / 3.0) * ((1.0 + a) * exp_neg(a, tab));
+    }
+}
+
+// The body of the tile kernels below, one per family (inlined into each: the squared-exponential kernel keeps its name and its
+// instructions).
+template <int D, int KERN>
+__device__ __forceinline__ void nlml_grad_tile(const double *__restrict__ U, const double *__restrict__ alpha,
+                                               const double *__restrict__ Xsc, int N, int Np, double *__restrict__ slab) {
     __shared__ double As[GT * GLDA];
     __shared__ double Bs[GT * GLDA];
     __shared__ double xr[GT * D], xc[GT * D];   // scaled points of the tile's rows (block I) and columns (block J)
@@ -132,7 +149,7 @@ __global__ __launch_bounds__(256) void nlml_grad_kernel(const double *__restrict
                     s += dd[k];
                 }
                 const double w = acc[i][j][r] - ar[lr] * aj;
-                const double wk = w * exp_neg(s, tab);
+                const double wk = w * dlog_factor<KERN>(s, tab);
 #pragma unroll
                 for (int k = 0; k < D; ++k) g[k] = fma(wk, dd[k], g[k]);
             }
@@ -151,6 +168,22 @@ __global__ __launch_bounds__(256) void nlml_grad_kernel(const double *__restrict
         const double s = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
         slab[(int64_t)blockIdx.x * D + tid] = (I == J) ? s : 2.0 * s;   // (J, I) is the same sum
     }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void nlml_grad_kernel(const double *__restrict__ U, const double *__restrict__ alpha,
+                                                        const double *__restrict__ Xsc, int N, int Np,
+                                                        double *__restrict__ slab) {
+    nlml_grad_tile<D, GPBO_KERNEL_SE>(U, alpha, Xsc, N, Np, slab);
+}
+
+// the same tiles with a Matern factor in the epilogue (gpbo_nlml_grad_kern_f64)
+template <int D, int KERN>
+__global__ __launch_bounds__(256) void nlml_grad_matern_kernel(const double *__restrict__ U, const double *__restrict__ alpha,
+                                                               const double *__restrict__ Xsc, int N, int Np,
+                                                               double *__restrict__ slab) {
+    static_assert(KERN == GPBO_KERNEL_MATERN32 || KERN == GPBO_KERNEL_MATERN52, "a Matern family");
+    nlml_grad_tile<D, KERN>(U, alpha, Xsc, N, Np, slab);
 }
 
 // out[0] = NLML from diag(U) and y . alpha; out[1 + k] = sum of the slab's column k, tiles in order
@@ -210,7 +243,14 @@ extern "C" int64_t gpbo_nlml_grad_workspace_bytes(int64_t Np, int32_t d) {
 extern "C" int gpbo_nlml_grad_f64(const double *U, const double *alpha, const double *y, const double *X, int64_t N,
                                   int64_t Np, int32_t d, const double *ls_host, const int32_t *info, double *out,
                                   void *work, int64_t work_bytes, void *stream) {
+    return gpbo_nlml_grad_kern_f64(U, alpha, y, X, N, Np, d, ls_host, GPBO_KERNEL_SE, info, out, work, work_bytes, stream);
+}
+
+extern "C" int gpbo_nlml_grad_kern_f64(const double *U, const double *alpha, const double *y, const double *X, int64_t N,
+                                       int64_t Np, int32_t d, const double *ls_host, int32_t kernel, const int32_t *info,
+                                       double *out, void *work, int64_t work_bytes, void *stream) {
     if (!U || !alpha || !y || !X || !ls_host || !info || !out || !work) return GPBO_ERR_ARG;
+    if (!kernel_ok(kernel, d)) return GPBO_ERR_ARG;
     if (N < 1 || Np != gpbo_padded_n(N) || Np > (1 << 20) || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
     for (int k = 0; k < d; ++k)
         if (!(ls_host[k] > 0.0)) return GPBO_ERR_ARG;
@@ -222,10 +262,16 @@ extern "C" int gpbo_nlml_grad_f64(const double *U, const double *alpha, const do
     hipStream_t st = gpbo_stream(stream);
     int rc = gpbo_scale_points_launch(X, N, Np, d, ls_host, Xsc, nullptr, stream);
     if (rc != GPBO_OK) return rc;
-#define CALL(DD)                                                                                                          \
-    hipLaunchKernelGGL(nlml_grad_kernel<DD>, dim3((unsigned)tiles), dim3(256), 0, st, U, alpha, Xsc, (int)N, (int)Np, slab)
+#define GRAD_LAUNCH(DD, KK)                                                                                                      \
+    hipLaunchKernelGGL((nlml_grad_matern_kernel<DD, KK>), dim3((unsigned)tiles), dim3(256), 0, st, U, alpha, Xsc, (int)N, (int)Np, \
+                       slab)
+#define CALL(DD)                                                                   \
+    if (kernel == GPBO_KERNEL_MATERN32) GRAD_LAUNCH(DD, GPBO_KERNEL_MATERN32);     \
+    else if (kernel == GPBO_KERNEL_MATERN52) GRAD_LAUNCH(DD, GPBO_KERNEL_MATERN52); \
+    else hipLaunchKernelGGL(nlml_grad_kernel<DD>, dim3((unsigned)tiles), dim3(256), 0, st, U, alpha, Xsc, (int)N, (int)Np, slab)
     GPBO_FOR_D(d, CALL)
 #undef CALL
+#undef GRAD_LAUNCH
     hipLaunchKernelGGL(nlml_grad_finish_kernel, dim3(1), dim3(256), 0, st, slab, tiles, (int)d, U, alpha, y, N, Np, info,
                        out);
     GPBO_CHECK_LAUNCH();

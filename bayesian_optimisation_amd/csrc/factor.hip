@@ -300,7 +300,16 @@ extern "C" int64_t gpbo_factorise_workspace_bytes(int64_t Np) {
 extern "C" int gpbo_factorise_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls_host,
                                   double jitter1, double jitter2, int64_t Np, double *Kp, double *U, double *alpha,
                                   int32_t *info, void *work, int64_t work_bytes, void *stream) {
+    return gpbo_factorise_kern_f64(X, y, N, d, ls_host, GPBO_KERNEL_SE, jitter1, jitter2, Np, Kp, U, alpha, info, work, work_bytes,
+                                   stream);
+}
+
+// (the covariance family reaches the K(X,X) build only: everything after it works on the matrix)
+extern "C" int gpbo_factorise_kern_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls_host,
+                                       int32_t kernel, double jitter1, double jitter2, int64_t Np, double *Kp, double *U,
+                                       double *alpha, int32_t *info, void *work, int64_t work_bytes, void *stream) {
     if (!X || !y || !Kp || !U || !alpha || !info || !work) return GPBO_ERR_ARG;
+    if (!kernel_ok(kernel, d)) return GPBO_ERR_ARG;
     if (Np != gpbo_padded_n(N)) return GPBO_ERR_ARG;
     if (work_bytes < gpbo_factorise_workspace_bytes(Np)) return GPBO_ERR_WORKSPACE;
     double *L = reinterpret_cast<double *>(work);
@@ -314,7 +323,7 @@ extern "C" int gpbo_factorise_f64(const double *X, const double *y, int64_t N, i
     // (the fused sweep's plan stops at Np = 32768 - 32-bit tile offsets; beyond, the two-pass chain, which has no such cap)
     if (!old_chain && Np <= GPBO_CHOLINV_MAX_NP) {
         double *S = L;  // [Np x 2 Np]: the same 2 Np^2 doubles
-        int rc = gpbo_kxx_launch(X, N, d, ls_host, jitter1, jitter2, Kp, Np, S, 2 * Np, info, stream);
+        int rc = gpbo_kxx_launch(X, N, d, ls_host, kernel, jitter1, jitter2, Kp, Np, S, 2 * Np, info, stream);
         if (rc != GPBO_OK) return rc;
         // GPBO_CI_OPTS="win,far_k,far_kind,defer+1,group_from+1,small_w": schedule choices of the plan for A/B runs (cholinv_plan.h)
         static int env_opt[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -329,7 +338,7 @@ extern "C" int gpbo_factorise_f64(const double *X, const double *y, int64_t N, i
         return gpbo_alpha_f64(U, y, N, Np, tmp, alpha, stream);
     }
     // one launch builds K twice (Kp stays as the reference's cov_meas, L is factorised in place) and clears info
-    int rc = gpbo_kxx_launch(X, N, d, ls_host, jitter1, jitter2, Kp, Np, L, Np, info, stream);
+    int rc = gpbo_kxx_launch(X, N, d, ls_host, kernel, jitter1, jitter2, Kp, Np, L, Np, info, stream);
     if (rc != GPBO_OK) return rc;
     rc = potrf_run(L, Np, dinv, info, true, stream);
     if (rc != GPBO_OK) return rc;

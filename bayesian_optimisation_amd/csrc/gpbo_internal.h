@@ -158,16 +158,16 @@ int gpbo_kstar_mu_mfma(const double *Xs, int64_t Mc, int64_t N, int64_t Np, int3
                        const double *alpha, const void *prep_buf, double *KsT, int64_t ldk, double *mu_part,
                        int64_t store_rows, void *stream);
 int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
-                       const double *ls_host, const double *alpha, double diag_add, int64_t cand_base, double *KsT,
-                       int64_t ldk, double *mu_part, int64_t store_rows, void *stream);
+                       const double *ls_host, int32_t kernel, const double *alpha, double diag_add, int64_t cand_base,
+                       double *KsT, int64_t ldk, double *mu_part, int64_t store_rows, void *stream);
 int gpbo_kstar_mu_anyd(const double *Xs, int64_t Mc, const double *X, int64_t N, int64_t Np, int32_t d, const double *ls_host,
                        const double *alpha, double diag_add, int64_t cand_base, double *KsT, int64_t ldk, double *mu_part,
                        void *stream);
 int gpbo_kstar_mu_mixed(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
                         const double *ls_host, const double *alpha, double diag_add, int64_t cand_base, float *KsT,
                         int64_t ldk, double *mu_part, void *stream);
-int gpbo_kxx_launch(const double *X, int64_t N, int32_t d, const double *ls_host, double jitter1, double jitter2,
-                    double *Kp, int64_t Np, double *K2, int64_t ld2, int32_t *info0, void *stream);
+int gpbo_kxx_launch(const double *X, int64_t N, int32_t d, const double *ls_host, int32_t kernel, double jitter1,
+                    double jitter2, double *Kp, int64_t Np, double *K2, int64_t ld2, int32_t *info0, void *stream);
 // fused Cholesky + inverse factor on the stacked matrix [A | W] (cholinv.hip)
 int gpbo_cholinv_run(double *S, int64_t ld, int64_t Np, int32_t *info, const int *opt, hipStream_t st);
 int gpbo_launch_transpose_w(const double *W, int64_t ldw, int64_t Np, double *U, hipStream_t st);

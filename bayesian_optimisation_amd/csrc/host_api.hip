@@ -14,6 +14,8 @@
 //   gpbo_nlml_grid_logdet_host_f64 = the same grid in fp64 with log det from the factor
 //   gpbo_nlml_grad_host_f64        = the likelihood and its gradient in the log length scales (ard="gradient")
 //   gpbo_nlml_hyper_host_f64       = the likelihood over length scales, noise, signal variance and mean (ard="hyper"; hyper.hip)
+//   gpbo_select_next_host_kern_f64 / gpbo_nlml_grad_host_kern_f64 / gpbo_nlml_hyper_host_kern_f64 = the same three with a
+//                                    covariance family (GPBO_KERNEL_*): it rides in the Surrogate, which hands it to the factorisation
 // Every factorising entry reads: own checks, own buffers, Surrogate (below), own calls, own read-backs.
 #include "gpbo_internal.h"
 
@@ -61,10 +63,12 @@ struct DeviceArena {
 struct Surrogate {
     const int64_t N, Np, wfact;   // observations, padded, the bytes the factorisation needs of `work`
     const int32_t d;
+    const int32_t kernel;   // GPBO_KERNEL_*: the family of the factorised matrix
     double *X = nullptr, *y = nullptr, *K = nullptr, *U = nullptr, *alpha = nullptr;
     int32_t *info = nullptr;
     char *work = nullptr;   // the factorisation's workspace is dead once U and alpha exist: the entry's own calls reuse it
-    Surrogate(int64_t N_, int32_t d_) : N(N_), Np(gpbo_padded_n(N_)), wfact(gpbo_factorise_workspace_bytes(Np)), d(d_) {}
+    Surrogate(int64_t N_, int32_t d_, int32_t kernel_ = GPBO_KERNEL_SE)
+        : N(N_), Np(gpbo_padded_n(N_)), wfact(gpbo_factorise_workspace_bytes(Np)), d(d_), kernel(kernel_) {}
     int64_t work_bytes(int64_t own) const { return wfact > own ? wfact : own; }   // (the entry adds its own slack)
     // Step 1, after the entry's own allocations: the buffers, GPBO_ERR_WORKSPACE if ANY allocation of the call failed, and
     // only then the first copies of the call: X and y.
@@ -78,7 +82,7 @@ struct Surrogate {
     }
     // The factorisation, enqueued (gpbo_nlml_grad_host_f64 stops here: its kernel reads `info` on the device).
     int factorise(DeviceArena &A, const double *ls, double jitter1, double jitter2) {
-        return gpbo_factorise_f64(X, y, N, d, ls, jitter1, jitter2, Np, K, U, alpha, info, work, wfact, A.st());
+        return gpbo_factorise_kern_f64(X, y, N, d, ls, kernel, jitter1, jitter2, Np, K, U, alpha, info, work, wfact, A.st());
     }
     // Step 2: the factorisation, its info word on the host, the stream idle.  *info_out != 0: not positive definite - the
     // entry fills its own outputs for that exit.
@@ -99,13 +103,23 @@ extern "C" int gpbo_select_next_host_f64(const double *X, const double *y, int64
                                          double p0, double p1, double diag_add, int64_t chunk, double *mu_out,
                                          double *sigma_out, double *acq_out, double *cov_meas_out, gpbo_result *result,
                                          int32_t *info) {
+    return gpbo_select_next_host_kern_f64(X, y, N, d, ls, GPBO_KERNEL_SE, jitter1, jitter2, Xs, M, acq_kind, p0, p1, diag_add, chunk,
+                                          mu_out, sigma_out, acq_out, cov_meas_out, result, info);
+}
+
+extern "C" int gpbo_select_next_host_kern_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls,
+                                              int32_t kernel, double jitter1, double jitter2, const double *Xs, int64_t M,
+                                              int32_t acq_kind, double p0, double p1, double diag_add, int64_t chunk,
+                                              double *mu_out, double *sigma_out, double *acq_out, double *cov_meas_out,
+                                              gpbo_result *result, int32_t *info) {
     if (!X || !y || !ls || !Xs || !result || !info) return GPBO_ERR_ARG;
+    if (!kernel_ok(kernel, d, diag_add)) return GPBO_ERR_ARG;
     if (N < 1 || M < 1 || d < 1 || d > GPBO_MAX_D_ANY) return GPBO_ERR_ARG;
     if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
     if (chunk == 0) chunk = (int64_t)1 << 17;
     if (!chunk_ok(chunk) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
     chunk = clamp_chunk(chunk, M);
-    Surrogate G(N, d);
+    Surrogate G(N, d, kernel);
     const int64_t Np = G.Np;
     const int64_t wpost = gpbo_posterior_workspace_bytes(Np, chunk, M);
     if (wpost < 0) return GPBO_ERR_ARG;
@@ -123,7 +137,8 @@ extern "C" int gpbo_select_next_host_f64(const double *X, const double *y, int64
     // rule and the same prefix lengths as DeviceGP.score_bound.
     // (jitter: with K = k(X,X) + tau I the true variance is >= tau, so the plain pass's sqrt(|var|) never reflects a
     //  negative value unless its rounding error exceeds tau - the one case a prefix cannot bound; DeviceGP.BOUND_MIN_JITTER)
-    const bool bound_route = !dense && diag_add == 0.0 && M >= 32768 && Np >= 1024 && d <= GPBO_MAX_D &&
+    // (squared exponential only: the bound builds its mean with the entries of kstar_mfma.hip; a Matern family takes the plain pass)
+    const bool bound_route = kernel == GPBO_KERNEL_SE && !dense && diag_add == 0.0 && M >= 32768 && Np >= 1024 && d <= GPBO_MAX_D &&
                              (acq_kind == GPBO_ACQ_EI || p0 >= 0.0) && jitter1 + jitter2 >= 1e-6;
     const int64_t J1 = (Np / 16) / 128 * 128 < 128 ? 128 : (Np / 16) / 128 * 128, J2 = (8 * J1 <= Np) ? 4 * J1 : 0;
     // every first-level survivor may go on to the second-level bound (1/16 of a plain pass per candidate); the plain pass
@@ -185,8 +200,8 @@ extern "C" int gpbo_select_next_host_f64(const double *X, const double *y, int64
         decided = !stats.fallback;
     }
     if (!decided) {
-        rc = gpbo_posterior_acq_f64(dXs, M, G.X, N, Np, d, ls, G.U, G.alpha, prior_var, acq_kind, p0, p1, diag_add, 0, chunk,
-                                    dmu, dsig, dacq, dres, G.work, wpost, nullptr, A.st());
+        rc = gpbo_posterior_acq_kern_f64(dXs, M, G.X, N, Np, d, ls, kernel, G.U, G.alpha, prior_var, acq_kind, p0, p1, diag_add, 0,
+                                         chunk, dmu, dsig, dacq, dres, G.work, wpost, nullptr, A.st());
         if (rc != GPBO_OK) return rc;
     }
     bool okc = A.d2h(result, dres, sizeof(gpbo_result));
@@ -424,8 +439,14 @@ extern "C" int gpbo_nlml_grid_logdet_host_f64(const double *X, const double *y, 
 
 extern "C" int gpbo_nlml_grad_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls,
                                        double jitter, double *out) {
-    if (!X || !y || !ls || !out || N < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
-    Surrogate G(N, d);
+    return gpbo_nlml_grad_host_kern_f64(X, y, N, d, ls, GPBO_KERNEL_SE, jitter, out);
+}
+
+extern "C" int gpbo_nlml_grad_host_kern_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls,
+                                            int32_t kernel, double jitter, double *out) {
+    if (!X || !y || !ls || !out || !kernel_ok(kernel, d)) return GPBO_ERR_ARG;
+    if (N < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    Surrogate G(N, d, kernel);
     const int64_t wgrad = gpbo_nlml_grad_workspace_bytes(G.Np, d);
     if (wgrad < 0) return GPBO_ERR_ARG;
 
@@ -437,16 +458,22 @@ extern "C" int gpbo_nlml_grad_host_f64(const double *X, const double *y, int64_t
     if (rc != GPBO_OK) return rc;
     rc = G.factorise(A, ls, jitter, 0.0);   // info stays on the device: the gradient kernel answers NaN for it
     if (rc != GPBO_OK) return rc;
-    rc = gpbo_nlml_grad_f64(G.U, G.alpha, G.y, G.X, N, G.Np, d, ls, G.info, dout, dwg, wgrad, A.st());
+    rc = gpbo_nlml_grad_kern_f64(G.U, G.alpha, G.y, G.X, N, G.Np, d, ls, kernel, G.info, dout, dwg, wgrad, A.st());
     if (rc != GPBO_OK) return rc;
     return A.d2h(out, dout, sizeof(double) * (1 + d)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
 extern "C" int gpbo_nlml_hyper_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls, double noise,
                                         int32_t flags, double *out) {
-    if (!X || !y || !ls || !out || N < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    return gpbo_nlml_hyper_host_kern_f64(X, y, N, d, ls, GPBO_KERNEL_SE, noise, flags, out);
+}
+
+extern "C" int gpbo_nlml_hyper_host_kern_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls,
+                                             int32_t kernel, double noise, int32_t flags, double *out) {
+    if (!X || !y || !ls || !out || !kernel_ok(kernel, d)) return GPBO_ERR_ARG;
+    if (N < 1 || d < 1 || d > GPBO_MAX_D || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
     if (!(noise > 0.0 && noise < __builtin_huge_val()) || (flags & ~(GPBO_HYPER_MEAN | GPBO_HYPER_SCALE))) return GPBO_ERR_ARG;
-    Surrogate G(N, d);
+    Surrogate G(N, d, kernel);
     const int64_t whyp = gpbo_nlml_hyper_workspace_bytes(G.Np, d);
     if (whyp < 0) return GPBO_ERR_ARG;
 
@@ -458,7 +485,8 @@ extern "C" int gpbo_nlml_hyper_host_f64(const double *X, const double *y, int64_
     if (rc != GPBO_OK) return rc;
     rc = G.factorise(A, ls, noise, 0.0);   // info stays on the device: the finish kernel answers NaN for it
     if (rc != GPBO_OK) return rc;
-    rc = gpbo_nlml_hyper_f64(G.U, G.alpha, G.y, G.X, N, G.Np, d, ls, noise, flags, G.info, dout, nullptr, dwh, whyp, A.st());
+    rc = gpbo_nlml_hyper_kern_f64(G.U, G.alpha, G.y, G.X, N, G.Np, d, ls, kernel, noise, flags, G.info, dout, nullptr, dwh, whyp,
+                                  A.st());
     if (rc != GPBO_OK) return rc;
     return A.d2h(out, dout, sizeof(double) * (4 + d)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }

@@ -25,6 +25,13 @@ inline bool chunk_ok(int64_t chunk) {
     return chunk >= GPBO_CHUNK_GRANULE && chunk % GPBO_CHUNK_GRANULE == 0 && chunk <= GPBO_CHUNK_MAX;
 }
 inline bool acq_kind_ok(int32_t kind) { return kind == GPBO_ACQ_LCB || kind == GPBO_ACQ_EI; }
+// a covariance family (GPBO_KERNEL_*) and what goes with it: the Matern kernels exist for the unrolled feature counts only and
+// never carry the N == M diagonal quirk (a shape coincidence of the reference's kernel_rbf)
+inline bool kernel_ok(int32_t kernel, int32_t d, double diag_add = 0.0) {
+    if (kernel == GPBO_KERNEL_SE) return true;
+    if (kernel != GPBO_KERNEL_MATERN32 && kernel != GPBO_KERNEL_MATERN52) return false;
+    return d <= GPBO_MAX_D && diag_add == 0.0;
+}
 inline bool np_ok(int64_t Np) { return Np >= GPBO_NPAD && Np % GPBO_NPAD == 0; }   // a padded size of the fp64 / int8 routes
 inline bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 inline bool length_scales_ok(const double *ls, int d) {
@@ -95,6 +102,7 @@ struct GpModel {
     const double *U;   // (L^-1)^T in fp64; null on the routes that bring their own copy of it (int8 slices)
     const double *alpha;
     double prior_var;
+    int32_t kernel;    // GPBO_KERNEL_*; a driver that does not set it gets 0 = the squared exponential
 };
 struct Acquisition {
     int32_t kind;   // GPBO_ACQ_*

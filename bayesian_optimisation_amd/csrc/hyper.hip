@@ -186,7 +186,18 @@ extern "C" int gpbo_nlml_hyper_f64(const double *U, const double *alpha, const d
                                    int64_t Np, int32_t d, const double *ls_host, double noise, int32_t flags,
                                    const int32_t *info, double *out, double *alpha_std_out, void *work, int64_t work_bytes,
                                    void *stream) {
+    return gpbo_nlml_hyper_kern_f64(U, alpha, y, X, N, Np, d, ls_host, GPBO_KERNEL_SE, noise, flags, info, out, alpha_std_out, work,
+                                    work_bytes, stream);
+}
+
+// The profiled mean and scale, the noise gradient and the finish never see the covariance function: the family only travels
+// to the length-scale gradients (gpbo_nlml_grad_kern_f64).
+extern "C" int gpbo_nlml_hyper_kern_f64(const double *U, const double *alpha, const double *y, const double *X, int64_t N,
+                                        int64_t Np, int32_t d, const double *ls_host, int32_t kernel, double noise,
+                                        int32_t flags, const int32_t *info, double *out, double *alpha_std_out, void *work,
+                                        int64_t work_bytes, void *stream) {
     if (!U || !alpha || !y || !X || !ls_host || !info || !out || !work) return GPBO_ERR_ARG;
+    if (!kernel_ok(kernel, d)) return GPBO_ERR_ARG;
     if (N < 1 || Np != gpbo_padded_n(N) || Np > (1 << 20) || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
     if (!positive_finite(noise) || (flags & ~(GPBO_HYPER_MEAN | GPBO_HYPER_SCALE))) return GPBO_ERR_ARG;
     if (!length_scales_ok(ls_host, d)) return GPBO_ERR_ARG;
@@ -206,7 +217,7 @@ extern "C" int gpbo_nlml_hyper_f64(const double *U, const double *alpha, const d
     hipLaunchKernelGGL(hyper_profile_kernel, dim3(1), dim3(PROFILE_THREADS), 0, st, alpha, b, y, kappa, N, Np, (int)flags,
                        alpha_std, r_std, alpha_std_out, scal);
     GPBO_CHECK_LAUNCH();
-    rc = gpbo_nlml_grad_f64(U, alpha_std, r_std, X, N, Np, d, ls_host, info, gout, work, L.wgrad, stream);
+    rc = gpbo_nlml_grad_kern_f64(U, alpha_std, r_std, X, N, Np, d, ls_host, kernel, info, gout, work, L.wgrad, stream);
     if (rc != GPBO_OK) return rc;
     hipLaunchKernelGGL(hyper_finish_kernel, dim3(1), dim3(64), 0, st, gout, scal, (int)d, N, noise, info, out);
     GPBO_CHECK_LAUNCH();

@@ -9,6 +9,9 @@
 // features in index order, times -0.5, exp.  K(X*,X) - M x N entries, the fp64-issue-bound kernel - uses
 // coordinates pre-scaled by 1/(ls_k sqrt 2) and its own exp(-t); both agree with the reference's values
 // to a few ulp (tests: 5e-15 absolute on entries <= 1).
+// Both kernels take the covariance family as a template parameter (GPBO_KERNEL_*, include/gpbo.h): the squared-exponential
+// instances are the code above unchanged, the Matern instances replace the exponential of the accumulated distance by
+// (1 + a) exp(-a) or (1 + a + a^2 / 3) exp(-a), a = sqrt(3) r or sqrt(5) r.
 #include "gpbo_internal.h"
 
 #include <cstdlib>
@@ -35,7 +38,7 @@ __device__ __forceinline__ double sqdist(const double (&xc)[D], const double *__
 // grid (ceil(Np/256), Np/8), block 256: thread = column j, block row-slice of 8 rows (the chains of one
 // entry are ~45 dependent fp64 instructions, so parallelism over rows matters more than reuse of xj).
 // ---------------------------------------------------------------------------------------------
-template <int D>
+template <int D, int KERN>
 __global__ __launch_bounds__(256) void kxx_kernel(const double *__restrict__ X, int N, LsArgs ls, double j1,
                                                   double j2, double *__restrict__ K, int Np,
                                                   double *__restrict__ K2 /* optional second copy (the one the
@@ -53,8 +56,16 @@ __global__ __launch_bounds__(256) void kxx_kernel(const double *__restrict__ X, 
     for (int i = i0; i < i0 + 8; ++i) {
         double v;
         if (i < N) {  // wave-uniform
-            const double acc = sqdist<D>(xj, X + (int64_t)i * D, ls);
-            v = exp(-0.5 * acc);
+            const double acc = sqdist<D>(xj, X + (int64_t)i * D, ls);   // r^2: the same bits for (i, j) and (j, i)
+            if constexpr (KERN == GPBO_KERNEL_SE) {
+                v = exp(-0.5 * acc);
+            } else if constexpr (KERN == GPBO_KERNEL_MATERN32) {
+                const double a = sqrt(3.0 * acc);
+                v = (1.0 + a) * exp(-a);
+            } else {
+                const double a = sqrt(5.0 * acc);
+                v = ((1.0 + a) + a * a / 3.0) * exp(-a);
+            }
             if (i == j) v = (v + j1) + j2;  // reference: kernel_rbf adds 1e-4 (:193), assembly adds 1e-6 (:79)
             if (j >= N) v = 0.0;
         } else {
@@ -99,7 +110,21 @@ __device__ __forceinline__ void store_pair(float *p, double a, double b) {
 // TK = double: the fp64 path.  TK = float (gpbo_kstar_mu_mixed): entries and means are computed exactly as in the
 // fp64 path - the mean partials are the same doubles bit for bit - and only the stored K*^T is rounded to fp32
 // (relative error <= 2^-24 per entry) for the fp32 variance screen.
-template <int D, int VARIANT, bool HAS_DIAG, typename TK, bool NT>
+// KERN: with the coordinates scaled as above the accumulated s is r^2 / 2, so a = sqrt(6 s) (Matern 3/2) or sqrt(10 s) (5/2, where
+// a^2 / 3 = 10/3 s needs no square).  The HAS_DIAG quirk belongs to the reference's kernel_rbf: squared exponential only.
+template <int KERN>
+__device__ __forceinline__ double matern_entry(double s, const double *tab) {
+    static_assert(KERN == GPBO_KERNEL_MATERN32 || KERN == GPBO_KERNEL_MATERN52, "a Matern family");
+    if constexpr (KERN == GPBO_KERNEL_MATERN32) {
+        const double a = sqrt_nonneg(6.0 * s);
+        return (1.0 + a) * exp_neg(a, tab);
+    } else {
+        const double a = sqrt_nonneg(10.0 * s);
+        return ((1.0 + a) + (10.0 / 3.0) * s) * exp_neg(a, tab);
+    }
+}
+
+template <int D, int VARIANT, bool HAS_DIAG, typename TK, bool NT, int KERN = GPBO_KERNEL_SE>
 __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict__ Xs, int64_t Mc,
                                                        const double *__restrict__ Xsc, int N, LsArgs ls,
                                                        const double *__restrict__ alpha, double diag_add,
@@ -108,6 +133,7 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
                                                        int store_rows /* rows n >= store_rows are not stored (multiple of 64):
                                                                          the prefix-bound screen needs the mean of all N
                                                                          observations but K*^T of the first few only */) {
+    static_assert(KERN == GPBO_KERNEL_SE || (!HAS_DIAG && VARIANT == 0), "the quirk and the timing variants are SE-only");
     __shared__ double tab[GPBO_EXP_E];
     if (threadIdx.x < GPBO_EXP_E) tab[threadIdx.x] = kExp2Tab256[threadIdx.x * (256 / GPBO_EXP_E)];
     const int64_t c0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
@@ -147,6 +173,10 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
             s11 = fma(d11, d11, s11);
         }
         double k00, k01, k10, k11;
+        if constexpr (KERN != GPBO_KERNEL_SE) {
+            k00 = matern_entry<KERN>(s00, tab); k01 = matern_entry<KERN>(s01, tab);
+            k10 = matern_entry<KERN>(s10, tab); k11 = matern_entry<KERN>(s11, tab);
+        } else
         if (VARIANT == 3) { k00 = s00; k01 = s01; k10 = s10; k11 = s11; }
         else { k00 = exp_neg(s00, tab); k01 = exp_neg(s01, tab); k10 = exp_neg(s10, tab); k11 = exp_neg(s11, tab); }
         if (HAS_DIAG) {  // N == M shape-coincidence quirk (point_selector.py:173,191-193)
@@ -180,7 +210,9 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
             sa = fma(da, da, sa);
             sb = fma(db, db, sb);
         }
-        double ka = exp_neg(sa, tab), kb = exp_neg(sb, tab);
+        double ka, kb;
+        if constexpr (KERN != GPBO_KERNEL_SE) { ka = matern_entry<KERN>(sa, tab); kb = matern_entry<KERN>(sb, tab); }
+        else { ka = exp_neg(sa, tab); kb = exp_neg(sb, tab); }
         if (HAS_DIAG) {
             if ((int64_t)n == cand_base + c0) ka += diag_add;
             if ((int64_t)n == cand_base + c0 + 1) kb += diag_add;
@@ -351,9 +383,10 @@ static int make_ls(const double *ls_host, int d, LsArgs *out) {
         default: return GPBO_ERR_ARG; \
     }
 
-int gpbo_kxx_launch(const double *X, int64_t N, int32_t d, const double *ls_host, double jitter1, double jitter2,
-                    double *Kp, int64_t Np, double *K2, int64_t ld2, int32_t *info0, void *stream) {
+int gpbo_kxx_launch(const double *X, int64_t N, int32_t d, const double *ls_host, int32_t kernel, double jitter1,
+                    double jitter2, double *Kp, int64_t Np, double *K2, int64_t ld2, int32_t *info0, void *stream) {
     if (!X || !Kp || N < 1 || Np < N || Np % 64 != 0 || Np > (1 << 20)) return GPBO_ERR_ARG;
+    if (!kernel_ok(kernel, d)) return GPBO_ERR_ARG;
     if (K2 && (ld2 < Np || ld2 > (1 << 21))) return GPBO_ERR_ARG;
     if (d > GPBO_MAX_D) {  // any feature count: the slow path
         hipStream_t st = gpbo_stream(stream);
@@ -371,19 +404,28 @@ int gpbo_kxx_launch(const double *X, int64_t N, int32_t d, const double *ls_host
     int rc = make_ls(ls_host, d, &ls);
     if (rc != GPBO_OK) return rc;
     dim3 grid((unsigned)((Np + 255) / 256), (unsigned)(Np / 8));
-#define CALL(DD) \
-    hipLaunchKernelGGL(kxx_kernel<DD>, grid, dim3(256), 0, gpbo_stream(stream), X, (int)N, ls, jitter1, jitter2, Kp, (int)Np, \
+#define KXX_LAUNCH(DD, KK)                                                                                                   \
+    hipLaunchKernelGGL((kxx_kernel<DD, KK>), grid, dim3(256), 0, gpbo_stream(stream), X, (int)N, ls, jitter1, jitter2, Kp, (int)Np, \
                        K2, (int)ld2, info0)
+#define CALL(DD)                                                                  \
+    if (kernel == GPBO_KERNEL_MATERN32) KXX_LAUNCH(DD, GPBO_KERNEL_MATERN32);     \
+    else if (kernel == GPBO_KERNEL_MATERN52) KXX_LAUNCH(DD, GPBO_KERNEL_MATERN52); \
+    else KXX_LAUNCH(DD, GPBO_KERNEL_SE)
     GPBO_DISPATCH_D(d, CALL)
 #undef CALL
-#undef KSTAR_LAUNCH
+#undef KXX_LAUNCH
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
 }
 
 extern "C" int gpbo_kxx_f64(const double *X, int64_t N, int32_t d, const double *ls_host, double jitter1,
                             double jitter2, double *Kp, int64_t Np, void *stream) {
-    return gpbo_kxx_launch(X, N, d, ls_host, jitter1, jitter2, Kp, Np, nullptr, 0, nullptr, stream);
+    return gpbo_kxx_kern_f64(X, N, d, ls_host, GPBO_KERNEL_SE, jitter1, jitter2, Kp, Np, stream);
+}
+
+extern "C" int gpbo_kxx_kern_f64(const double *X, int64_t N, int32_t d, const double *ls_host, int32_t kernel, double jitter1,
+                                 double jitter2, double *Kp, int64_t Np, void *stream) {
+    return gpbo_kxx_launch(X, N, d, ls_host, kernel, jitter1, jitter2, Kp, Np, nullptr, 0, nullptr, stream);
 }
 
 int gpbo_scale_points_launch(const double *X, int64_t N, int64_t Np, int32_t d, const double *ls_host, double *Xsc,
@@ -407,15 +449,23 @@ extern "C" int gpbo_scale_points_f64(const double *X, int64_t N, int64_t Np, int
 extern "C" int gpbo_kstar_mu_f64(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
                                  const double *ls_host, const double *alpha, double diag_add, int64_t cand_base,
                                  double *KsT, int64_t ldk, double *mu_part, void *stream) {
-    return gpbo_kstar_mu_rows(Xs, Mc, Xsc, N, Np, d, ls_host, alpha, diag_add, cand_base, KsT, ldk, mu_part, Np, stream);
+    return gpbo_kstar_mu_kern_f64(Xs, Mc, Xsc, N, Np, d, ls_host, GPBO_KERNEL_SE, alpha, diag_add, cand_base, KsT, ldk, mu_part,
+                                  stream);
+}
+
+extern "C" int gpbo_kstar_mu_kern_f64(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
+                                      const double *ls_host, int32_t kernel, const double *alpha, double diag_add,
+                                      int64_t cand_base, double *KsT, int64_t ldk, double *mu_part, void *stream) {
+    return gpbo_kstar_mu_rows(Xs, Mc, Xsc, N, Np, d, ls_host, kernel, alpha, diag_add, cand_base, KsT, ldk, mu_part, Np, stream);
 }
 
 // store_rows: only rows n < store_rows of K*^T are written (a multiple of 64; Np = everything); the mean partials always
 // cover all N observations.
 int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
-                       const double *ls_host, const double *alpha, double diag_add, int64_t cand_base, double *KsT,
-                       int64_t ldk, double *mu_part, int64_t store_rows, void *stream) {
+                       const double *ls_host, int32_t kernel, const double *alpha, double diag_add, int64_t cand_base,
+                       double *KsT, int64_t ldk, double *mu_part, int64_t store_rows, void *stream) {
     if (!Xs || !Xsc || !alpha || !KsT || !mu_part) return GPBO_ERR_ARG;
+    if (!kernel_ok(kernel, d, diag_add)) return GPBO_ERR_ARG;
     if (store_rows < 0 || store_rows > Np || store_rows % KS_SLICE) return GPBO_ERR_ARG;
     if (Mc < 1 || N < 1 || Np < N || Np % 128 != 0 || ldk % GPBO_CHUNK_GRANULE != 0 || Mc > ldk)
         return GPBO_ERR_ARG;
@@ -437,15 +487,24 @@ int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t 
                        ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)store_rows)
 #define KSTAR_LAUNCH(DD, V, H) \
     do { if (nt) KSTAR_LAUNCH1(DD, V, H, true); else KSTAR_LAUNCH1(DD, V, H, false); } while (0)
+#define KSTAR_MATERN1(DD, NTF, KK)                                                                                                \
+    hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, double, NTF, KK>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, Xsc, (int)N, \
+                       ls, alpha, 0.0, cand_base, KsT, ldk, mu_part, (int)store_rows)
+#define KSTAR_MATERN(DD, KK) \
+    do { if (nt) KSTAR_MATERN1(DD, true, KK); else KSTAR_MATERN1(DD, false, KK); } while (0)
 #ifdef GPBO_DIAGNOSTICS
-#define CALL(DD)                                        \
-    if (diag_add != 0.0) KSTAR_LAUNCH(DD, 0, true);     \
-    else if (variant == 1) KSTAR_LAUNCH(DD, 1, false);  \
-    else if (variant == 3) KSTAR_LAUNCH(DD, 3, false);  \
+#define CALL(DD)                                                                    \
+    if (kernel == GPBO_KERNEL_MATERN32) KSTAR_MATERN(DD, GPBO_KERNEL_MATERN32);     \
+    else if (kernel == GPBO_KERNEL_MATERN52) KSTAR_MATERN(DD, GPBO_KERNEL_MATERN52); \
+    else if (diag_add != 0.0) KSTAR_LAUNCH(DD, 0, true);                            \
+    else if (variant == 1) KSTAR_LAUNCH(DD, 1, false);                              \
+    else if (variant == 3) KSTAR_LAUNCH(DD, 3, false);                              \
     else KSTAR_LAUNCH(DD, 0, false)
 #else
-#define CALL(DD)                                        \
-    if (diag_add != 0.0) KSTAR_LAUNCH(DD, 0, true);     \
+#define CALL(DD)                                                                    \
+    if (kernel == GPBO_KERNEL_MATERN32) KSTAR_MATERN(DD, GPBO_KERNEL_MATERN32);     \
+    else if (kernel == GPBO_KERNEL_MATERN52) KSTAR_MATERN(DD, GPBO_KERNEL_MATERN52); \
+    else if (diag_add != 0.0) KSTAR_LAUNCH(DD, 0, true);                            \
     else KSTAR_LAUNCH(DD, 0, false)
 #endif
     (void)variant;

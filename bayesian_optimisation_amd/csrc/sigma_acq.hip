@@ -797,7 +797,18 @@ extern "C" int gpbo_posterior_acq_f64(const double *Xs, int64_t M, const double 
                                       int64_t chunk, double *mu_out, double *sigma_out, double *acq_out,
                                       gpbo_result *result, void *work, int64_t work_bytes, gpbo_profile *prof,
                                       void *stream) {
-    return gpbo_posterior_acq_f64_split(Xs, M, {X, N, Np, d, ls_host, U, alpha, prior_var}, {acq_kind, p0, p1}, diag_add,
+    return gpbo_posterior_acq_kern_f64(Xs, M, X, N, Np, d, ls_host, GPBO_KERNEL_SE, U, alpha, prior_var, acq_kind, p0, p1, diag_add,
+                                       idx_offset, chunk, mu_out, sigma_out, acq_out, result, work, work_bytes, prof, stream);
+}
+
+// (the covariance family reaches the K(X*,X) launches only: the variance kernel, the epilogues and the arg-max work on K*^T)
+extern "C" int gpbo_posterior_acq_kern_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
+                                           const double *ls_host, int32_t kernel, const double *U, const double *alpha,
+                                           double prior_var, int32_t acq_kind, double p0, double p1, double diag_add,
+                                           int64_t idx_offset, int64_t chunk, double *mu_out, double *sigma_out,
+                                           double *acq_out, gpbo_result *result, void *work, int64_t work_bytes,
+                                           gpbo_profile *prof, void *stream) {
+    return gpbo_posterior_acq_f64_split(Xs, M, {X, N, Np, d, ls_host, U, alpha, prior_var, kernel}, {acq_kind, p0, p1}, diag_add,
                                         idx_offset, chunk, {mu_out, sigma_out, acq_out, nullptr}, result, work, work_bytes,
                                         prof, 1, 0, stream);
 }
@@ -836,6 +847,8 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
     const int64_t N = gp.N, Np = gp.Np;
     const int32_t d = gp.d;
     if (!Xs || !X || !U || !alpha || !result || !work) return GPBO_ERR_ARG;
+    // (a Matern family: never with the prefix bound, whose mean comes from the squared-exponential kstar_mfma.hip)
+    if (!kernel_ok(gp.kernel, d, diag_add) || (gp.kernel != GPBO_KERNEL_SE && n_prefix != 0)) return GPBO_ERR_ARG;
     if (n_prefix < 0 || n_prefix > Np || n_prefix % BN || (n_prefix && diag_add != 0.0)) return GPBO_ERR_ARG;
     if (M < 1 || N < 1 || Np != gpbo_padded_n(N) || Np > (1 << 20)) return GPBO_ERR_ARG;
     if (!chunk_ok(chunk)) return GPBO_ERR_ARG;
@@ -910,14 +923,14 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
             const int64_t nrow = (N < n_prefix) ? N : n_prefix;
             // (its mean partials - of the first n_prefix observations only - are not wanted: they go to rows of the K*^T
             //  slab that the prefix mode neither writes nor reads, [n_prefix, n_prefix + n_prefix / 64))
-            rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, Xsc, nrow, n_prefix, d, ls_host, alpha, 0.0, idx_offset + s, KsT[b], chunk,
-                                    KsT[b] + n_prefix * chunk, n_prefix, ks);
+            rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, Xsc, nrow, n_prefix, d, ls_host, GPBO_KERNEL_SE, alpha, 0.0, idx_offset + s,
+                                    KsT[b], chunk, KsT[b] + n_prefix * chunk, n_prefix, ks);
         } else if (anyd) {
             rc = gpbo_kstar_mu_anyd(Xs + s * d, Mc, X, N, Np, d, ls_host, alpha, diag_add, idx_offset + s, KsT[b], chunk,
                                     mu_part[b], ks);
         } else {
-            rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, Xsc, N, Np, d, ls_host, alpha, diag_add, idx_offset + s, KsT[b], chunk,
-                                    mu_part[b], n_prefix ? n_prefix : Np, ks);
+            rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, Xsc, N, Np, d, ls_host, gp.kernel, alpha, diag_add, idx_offset + s, KsT[b],
+                                    chunk, mu_part[b], n_prefix ? n_prefix : Np, ks);
         }
         if (rc != GPBO_OK) return rc;
         if (hp && hipEventRecord(hp->kdone[b], ks) != hipSuccess) return GPBO_ERR_LAUNCH;

@@ -178,6 +178,7 @@ class DeviceGP:
         self.N = self.Np = self.d = 0
         self.X = self.y = self.ls_h = None   # the observations and length scales of the last factorise() / load_state_dict()
         self.jitter1 = self.jitter2 = 0.0
+        self.kernel = "se"           # covariance family of the held factorisation (_lib.KERNEL_IDS)
         self.n_appended = 0
         self._owns_xy = False
         self.K = self.U = self.alpha = None
@@ -269,6 +270,15 @@ class DeviceGP:
             setattr(self, slot_name, w)
         return w
 
+    def _need_se(self, what: str):
+        """The calls that build covariance entries with squared-exponential kernels of their own refuse a surrogate of another
+        family (each is a follow-up of its own: DESIGN.md 4g)."""
+        if self.kernel != "se":
+            raise ValueError(f"{what} is not available with kernel={self.kernel!r}: it supports kernel='se' only")
+
+    def _kid(self) -> int:
+        return _lib.KERNEL_IDS[self.kernel]
+
     def _read(self, res_tuple) -> ScoreResult:
         """The synchronous form of what a score_async* call returned (reads the result record: synchronises)."""
         res, mu, sigma, acq = res_tuple
@@ -277,8 +287,11 @@ class DeviceGP:
 
     # -- factorisation (once per BO step) ---------------------------------------------------------
     def factorise(self, X, y, ls, jitter1: float = JITTER_KERNEL, jitter2: float = JITTER_ASSEMBLY,
-                  check: bool = True, order: str = "arrival"):
+                  check: bool = True, order: str = "arrival", kernel: str = "se"):
         """K = k(X,X) + jitter; K = L L^T; U = L^-T; alpha = K^-1 y   (point_selector.py:79, 89-90).
+        kernel: "se" (the reference's squared exponential), "matern32" or "matern52" (include/gpbo.h: GPBO_KERNEL_*; d <= 16,
+        order="arrival").  score() / score_async(), kxx_host(), cov_meas_host(), cov_meas_pred_host(), loo() and
+        acquisition_on_posterior() follow it; everything else of this class raises ValueError for a Matern surrogate.
         order="fps": the observations are factorised in their farthest-point order (gpbo_fps_order_f64: `bound_prefix()`
         members spread over the region the observations occupy, then the others in arrival order) instead of the order in
         which they arrived.  A GP's posterior does not depend on the order of its observations - every scoring call returns
@@ -289,12 +302,17 @@ class DeviceGP:
         torch = self.torch
         if order not in ("arrival", "fps"):
             raise ValueError("order must be 'arrival' or 'fps'")
+        kid = _lib.kernel_id(kernel)
+        if kernel != "se" and order != "arrival":
+            raise ValueError(f"order='fps' serves score_bound(), which is not available with kernel={kernel!r}")
         Xd = self._dev(X)
         if Xd.dim() != 2:
             raise ValueError("X must be (N, d)")
         N, d = int(Xd.shape[0]), int(Xd.shape[1])
         if d > _lib.MAX_D_ANY:
             raise ValueError(f"d = {d} > {_lib.MAX_D_ANY} is not supported")
+        if kernel != "se" and d > _lib.MAX_D:
+            raise ValueError(f"kernel={kernel!r} needs d <= {_lib.MAX_D} (d = {d}): the any-d slow path is kernel='se' only")
         yd = self._dev(y).reshape(-1)
         if yd.numel() != N:
             raise ValueError("y must have one value per row of X")
@@ -325,6 +343,7 @@ class DeviceGP:
             self.X, self.y, self.ls_h = Xd, yd, ls_h
             self.N, self.Np, self.d = N, Np, d
             self.jitter1, self.jitter2 = float(jitter1), float(jitter2)
+            self.kernel = kernel
             self._owns_xy = False
             self.n_appended = 0  # columns of U built by append() since the last full factorisation
             self._epoch += 1
@@ -339,11 +358,11 @@ class DeviceGP:
             self._u8_valid = False
             wbytes = int(self.lib.gpbo_factorise_workspace_bytes(Np))
             work = self._workspace("_work_fact", wbytes)
-            st = self.lib.gpbo_factorise_f64(self._ptr(Xd), self._ptr(yd), N, d, ls_h.ctypes.data_as(C.c_void_p),
-                                             jitter1, jitter2, Np, self._ptr(self.K), self._ptr(self.U),
-                                             self._ptr(self.alpha), self._ptr(self.info), self._ptr(work), wbytes,
-                                             self._stream())
-            _lib.check(st, "gpbo_factorise_f64")
+            st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(yd), N, d, ls_h.ctypes.data_as(C.c_void_p), kid,
+                                                  jitter1, jitter2, Np, self._ptr(self.K), self._ptr(self.U),
+                                                  self._ptr(self.alpha), self._ptr(self.info), self._ptr(work), wbytes,
+                                                  self._stream())
+            _lib.check(st, "gpbo_factorise_kern_f64")
             if check:
                 info = int(self.info.item())  # synchronises
                 if info != 0:
@@ -420,6 +439,7 @@ class DeviceGP:
         An appended column goes through the explicit inverse factor (l = U^T k), so it carries cond(L) eps of
         relative error where the blocked Cholesky is backward stable: `n_appended` counts the columns built this way
         since the last full factorisation, for callers that want to refresh after a while (PointSelector does)."""
+        self._need_se("append()")
         self._need_unrolled_d("append()")
         torch = self.torch
         if self.N < 1:
@@ -468,6 +488,7 @@ class DeviceGP:
     # -- persistence across jobs: the DAG's select_parameters jobs are separate processes --------------------
     def state_dict(self) -> dict:
         """Host copy of everything append()/score() need (the N x N part of the factors, not the padding)."""
+        self._need_se("state_dict()")
         N = self.N
         st = dict(version=1, N=N, d=self.d, ls=np.array(self.ls_h), jitter1=self.jitter1, jitter2=self.jitter2,
                   n_appended=self.n_appended,
@@ -478,6 +499,7 @@ class DeviceGP:
         return st
 
     def load_state_dict(self, st: dict):
+        self._need_se("load_state_dict()")
         torch = self.torch
         if int(st.get("version", 0)) != 1:
             raise ValueError("unknown surrogate state version")
@@ -519,6 +541,7 @@ class DeviceGP:
         import os
         import tempfile
 
+        self._need_se("save_state()")
         path = str(path)
         if not path.endswith(".npz"):
             path += ".npz"  # what np.savez would have appended
@@ -538,6 +561,7 @@ class DeviceGP:
             raise
 
     def load_state(self, path: str):
+        self._need_se("load_state()")
         with np.load(path) as z:
             return self.load_state_dict({k: z[k] for k in z.files})
 
@@ -560,6 +584,9 @@ class DeviceGP:
             # the N == M quirk (point_selector.py:173) adds to entry (i, i) of k(X, X*): candidate i against the caller's
             # observation i, which is not row i of a permuted factorisation
             raise ValueError("diag_add (the N == M shape quirk) needs factorise(order='arrival')")
+        if diag_add != 0.0 and self.kernel != "se":
+            raise ValueError(f"diag_add (the N == M shape quirk of the reference's kernel_rbf) is not available with "
+                             f"kernel={self.kernel!r}")
         with torch.cuda.device(self.device):
             chunk, wbytes = self._ensure_post_workspace(M)
             mu = sigma = acq = None
@@ -567,14 +594,14 @@ class DeviceGP:
                 mu = torch.empty(M, dtype=torch.float64, device=self.device)
                 sigma = torch.empty(M, dtype=torch.float64, device=self.device)
                 acq = torch.empty(M, dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_posterior_acq_f64(
+            st = self.lib.gpbo_posterior_acq_kern_f64(
                 self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d,
-                self.ls_h.ctypes.data_as(C.c_void_p), self._ptr(self.U), self._ptr(self.alpha), prior_var,
+                self.ls_h.ctypes.data_as(C.c_void_p), self._kid(), self._ptr(self.U), self._ptr(self.alpha), prior_var,
                 kind, p0, p1, float(diag_add), int(idx_offset), chunk, self._ptr(mu), self._ptr(sigma),
                 self._ptr(acq), self._ptr(self._result), self._ptr(self._work_post), wbytes,
                 self._profile if self.profile_active else None,
                 self._stream())
-            _lib.check(st, "gpbo_posterior_acq_f64")
+            _lib.check(st, "gpbo_posterior_acq_kern_f64")
         self._keep = Xsd  # keep the candidate tensor alive until the stream has consumed it
         return self._result, mu, sigma, acq
 
@@ -622,6 +649,7 @@ class DeviceGP:
         its lowest index.  Dense outputs (mu exactly the fp64 path's; sigma / acq with the screen's variance) are
         float64 tensors.  Unlike score_async this call synchronises (the survivor count is read back).
         `last_screen` keeps the statistics of the call."""
+        self._need_se(f"the {mode} screen (score_{mode}())")
         self._need_unrolled_d(f"the {mode} screen")
         torch = self.torch
         Xsd, M = self._candidates(Xs)
@@ -736,6 +764,7 @@ class DeviceGP:
         clustered).  Bounds and exact values come from the same U, the same K(X*,X) kernel and the same variance
         kernel: |v[:J]|^2 is a partial sum of the squares score() adds up.
         Synchronises; `last_screen` keeps the statistics."""
+        self._need_se("score_bound()")
         torch = self.torch
         if self.d > _lib.MAX_D:   # the slow any-d kernels serve the plain pass only
             self.last_screen = dict(mode="bound", fallback=True, reason="d > 16")
@@ -807,6 +836,7 @@ class DeviceGP:
         Returns (result_tensor, qei or None); the result's best_idx is a BATCH index.
         Z must be finite: a host array is checked here, a device tensor is the caller's (the kernel skips the improvements
         a NaN sample makes NaN instead of reporting them: DESIGN.md 1, "qEI and NaN")."""
+        self._need_se("score_qei()")
         self._need_unrolled_d("qEI")
         torch = self.torch
         if isinstance(Z, np.ndarray) and not np.isfinite(Z).all():
@@ -849,6 +879,7 @@ class DeviceGP:
         EI keeps the f_best it is given for the whole batch: with fantasy="liar" and lie < f_best the later members are still
         scored against f_best, not against the lie (the NumPy reference of the tests, tests/batch_ref.py, does the same).
         A caller who wants the lie to count as the incumbent passes f_best = min(f_best, lie)."""
+        self._need_se("select_batch_on_posterior()")
         self._need_unrolled_d("select_batch()")
         torch = self.torch
         Xsd, M = self._candidates(Xs)
@@ -886,6 +917,7 @@ class DeviceGP:
         chosen so far excluded.  Runs the dense plain pass, then gpbo_select_batch_f64: per member N kernel entries per
         candidate instead of the N^2 of a pass after append().  The factorisation (U, alpha, N) is not touched.
         d <= 16; not with the N == M shape quirk (diag_add)."""
+        self._need_se("select_batch()")
         if diag_add != 0.0:
             raise ValueError("select_batch() does not support diag_add (the N == M shape quirk)")
         self._need_unrolled_d("select_batch()")
@@ -907,6 +939,7 @@ class DeviceGP:
         only.  The paths stay valid until the next factorise() / append() / load_state_dict()."""
         from .thompson import path_params, thompson_draws
 
+        self._need_se("thompson_paths()")
         n_paths, n_features, seed = path_params(n_paths, n_features, seed)
         self._need_unrolled_d("thompson_paths()")
         if self.N < 1:
@@ -934,6 +967,7 @@ class DeviceGP:
         acquisition -f_s there and, with dense=True, the paths themselves [n_paths x M] on the device.  One read-back
         (synchronises).  IndexError when a value is NaN (a candidate with a non-finite coordinate), as the other
         acquisitions raise."""
+        self._need_se("thompson_score()")
         self._need_unrolled_d("thompson_score()")
         if not isinstance(paths, ThompsonPaths) or paths.epoch != (id(self), self._epoch):
             raise ValueError("these sample paths do not belong to the surrogate as it is now: call thompson_paths() again "
@@ -968,6 +1002,7 @@ class DeviceGP:
         ValueError on bad q / n_paths / n_features / seed before any GPU work; IndexError when a value is NaN."""
         from .thompson import first_distinct, select_params
 
+        self._need_se("select_thompson()")
         self._need_unrolled_d("select_thompson()")
         Xsd, M = self._candidates(Xs)
         q, n_paths, n_features, seed = select_params(q, n_paths, n_features, seed, M=M, d=self.d)
@@ -990,6 +1025,7 @@ class DeviceGP:
         """Posterior mean, standard deviation and acquisition at the rows of Xq [P x d] (P <= 4096) with their gradients in
         x (gpbo_posterior_grad_f64).  Query points, not candidates: the N == M quirk (diag_add) does not apply.  Works on
         the factorisation as it is (any order=, appended rows included).  Enqueues only; device tensors come back."""
+        self._need_se("posterior_grad()")
         self._need_unrolled_d("posterior_grad()")
         torch = self.torch
         Xd, P = self._points(Xq, "Xq")
@@ -1015,6 +1051,7 @@ class DeviceGP:
         [lower, upper] (gpbo_refine_f64; the rule is stated in include/gpbo.h): each start on its own, step doubled after an
         accepted trial and halved after a rejected one, iters trials.  All iters + 1 evaluations are enqueued at once;
         one read-back of the result record (synchronises).  Two calls give the same bits."""
+        self._need_se("refine()")
         self._need_unrolled_d("refine()")
         torch = self.torch
         Xd, P = self._points(starts, "starts")
@@ -1043,6 +1080,7 @@ class DeviceGP:
         """The dense score() of the candidates Xs, then refine() from the n_starts candidates with the largest acquisition
         (stable descending sort: ties keep the lower index first).  lower / upper omitted: the per-feature minimum / maximum
         of Xs.  Returns refine()'s result with grid_idx / grid_val = score()'s arg-max and its value."""
+        self._need_se("select_refined()")
         self._need_unrolled_d("select_refined()")
         torch = self.torch
         Xsd, M = self._candidates(Xs)
@@ -1124,6 +1162,7 @@ class DeviceGP:
 
     def nlml_grid_device(self, X, y, ls_cells, jitter: float = JITTER_KERNEL, likelihood: str = "reference"):
         """The same grid left on the device (float32 / float64 tensor [G]); enqueues on the current stream, no read-back."""
+        self._need_se("nlml_grid()")   # (the grid kernels generate squared-exponential entries)
         if likelihood not in ("reference", "logdet"):
             raise ValueError(f"likelihood must be 'reference' or 'logdet', got {likelihood!r}")
         torch = self.torch
@@ -1182,11 +1221,12 @@ class DeviceGP:
         fb = self._fit_bufs or {}
         return sum(t.numel() * t.element_size() for t in fb.values() if isinstance(t, self.torch.Tensor))
 
-    def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL):
+    def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL, kernel: str = "se"):
         """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I - the "logdet" likelihood and its gradient - from a
         factorisation into the fit's own buffers (the surrogate held by this object is not touched).  NaN in every
-        output when K is not positive definite.  d <= 16."""
+        output when K is not positive definite.  d <= 16.  kernel: the covariance family k (factorise())."""
         torch = self.torch
+        kid = _lib.kernel_id(kernel)
         Xd, yd = self._dev(X), self._dev(y).reshape(-1)
         if Xd.dim() != 2:
             raise ValueError("X must be (N, d)")
@@ -1204,18 +1244,18 @@ class DeviceGP:
         with torch.cuda.device(self.device):
             fb = self._fit_buffers(Np, d)
             lsp = ls_h.ctypes.data_as(C.c_void_p)
-            st = self.lib.gpbo_factorise_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, float(jitter), 0.0, Np,
-                                             self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
-                                             self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
-            _lib.check(st, "gpbo_factorise_f64")
-            st = self.lib.gpbo_nlml_grad_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N, Np,
-                                             d, lsp, self._ptr(fb["info"]), self._ptr(fb["out"]), self._ptr(fb["work_grad"]),
-                                             fb["wg"], self._stream())
-            _lib.check(st, "gpbo_nlml_grad_f64")
+            st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, kid, float(jitter), 0.0, Np,
+                                                  self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
+                                                  self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
+            _lib.check(st, "gpbo_factorise_kern_f64")
+            st = self.lib.gpbo_nlml_grad_kern_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N,
+                                                  Np, d, lsp, kid, self._ptr(fb["info"]), self._ptr(fb["out"]),
+                                                  self._ptr(fb["work_grad"]), fb["wg"], self._stream())
+            _lib.check(st, "gpbo_nlml_grad_kern_f64")
             out = fb["out"][: 1 + d].cpu().numpy()   # synchronises
         return float(out[0]), out[1:].copy()
 
-    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, **opts):
+    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, kernel: str = "se", **opts):
         """ML-II fit of the ARD length scales inside [lower, upper] from ls0 (ard_fit.fit_length_scales: projected L-BFGS
         in log ls, every evaluation one factorisation + one gradient launch).  Returns the FitResult.  The fit's buffers
         are released afterwards when larger than ARD_KEEP_WORKSPACE_BYTES."""
@@ -1223,19 +1263,20 @@ class DeviceGP:
 
         Xd, yd = self._dev(X), self._dev(y).reshape(-1)   # uploaded once for all evaluations
         try:
-            return fit_length_scales(lambda ls: self.nlml_and_grad(Xd, yd, ls, jitter), ls0, lower, upper, **opts)
+            return fit_length_scales(lambda ls: self.nlml_and_grad(Xd, yd, ls, jitter, kernel), ls0, lower, upper, **opts)
         finally:
             if self._fit_bytes() > self.ARD_KEEP_WORKSPACE_BYTES:
                 self._fit_bufs = None
 
     # -- ML-II over all hyperparameters (ard="hyper"; csrc/hyper.hip) and leave-one-out prediction ---------------------
-    def nlml_hyper(self, X, y, ls, noise: float, fit_mean: bool = True, fit_scale: bool = True):
+    def nlml_hyper(self, X, y, ls, noise: float, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se"):
         """(L, dL / d(log ls, log noise) [d + 1], mean, scale^2) of the model y ~ N(mean 1, scale^2 (k(X,X) + noise I)) with
         mean and scale^2 at their closed-form optima (fit_mean / fit_scale False: held at 0 / 1): gpbo_nlml_hyper_f64 on a
         factorisation of the raw y with (jitter1, jitter2) = (noise, 0) in the fit's own buffers (the surrogate held by this
         object is not touched).  NaN in every output when the matrix is not positive definite or scale^2 is not positive
-        (one observation, a constant y).  d <= 16."""
+        (one observation, a constant y).  d <= 16.  kernel: the covariance family k (factorise())."""
         torch = self.torch
+        kid = _lib.kernel_id(kernel)
         Xd, yd = self._dev(X), self._dev(y).reshape(-1)
         if Xd.dim() != 2:
             raise ValueError("X must be (N, d)")
@@ -1264,19 +1305,21 @@ class DeviceGP:
                 fb["wh"] = wh
                 fb["out_hyper"] = torch.empty(4 + fb["d"], dtype=torch.float64, device=self.device)
             lsp = ls_h.ctypes.data_as(C.c_void_p)
-            st = self.lib.gpbo_factorise_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, noise, 0.0, Np,
-                                             self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
-                                             self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
-            _lib.check(st, "gpbo_factorise_f64")
-            st = self.lib.gpbo_nlml_hyper_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N, Np,
-                                              d, lsp, noise, flags, self._ptr(fb["info"]), self._ptr(fb["out_hyper"]), None,
-                                              self._ptr(fb["work_hyper"]), fb["wh"], self._stream())
-            _lib.check(st, "gpbo_nlml_hyper_f64")
+            st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, kid, noise, 0.0, Np,
+                                                  self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
+                                                  self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
+            _lib.check(st, "gpbo_factorise_kern_f64")
+            st = self.lib.gpbo_nlml_hyper_kern_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N,
+                                                   Np, d, lsp, kid, noise, flags, self._ptr(fb["info"]),
+                                                   self._ptr(fb["out_hyper"]), None, self._ptr(fb["work_hyper"]), fb["wh"],
+                                                   self._stream())
+            _lib.check(st, "gpbo_nlml_hyper_kern_f64")
             out = fb["out_hyper"][: 4 + d].cpu().numpy()   # synchronises
         return float(out[0]), out[1: 2 + d].copy(), float(out[2 + d]), float(out[3 + d])
 
     def fit_hyperparameters(self, X, y, ls0, ls_lower, ls_upper, noise0: float = 1e-2, noise_lower: float = 1e-6,
-                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, **opts):
+                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se",
+                            **opts):
         """ML-II fit of the length scales and the noise-to-signal ratio inside their boxes, mean and signal variance profiled
         out (ard_fit.fit_hyperparameters: projected L-BFGS in the d + 1 log variables, every evaluation one factorisation and
         one nlml_hyper).  Returns the HyperFitResult.  The fit's buffers are released afterwards when larger than
@@ -1285,7 +1328,7 @@ class DeviceGP:
 
         Xd, yd = self._dev(X), self._dev(y).reshape(-1)   # uploaded once for all evaluations
         try:
-            return fit_hyperparameters(lambda ls, noise: self.nlml_hyper(Xd, yd, ls, noise, fit_mean, fit_scale), ls0,
+            return fit_hyperparameters(lambda ls, noise: self.nlml_hyper(Xd, yd, ls, noise, fit_mean, fit_scale, kernel), ls0,
                                        ls_lower, ls_upper, noise0, noise_lower, noise_upper, **opts)
         finally:
             if self._fit_bytes() > self.ARD_KEEP_WORKSPACE_BYTES:
@@ -1328,7 +1371,8 @@ class DeviceGP:
         return Ka
 
     def kxx_host(self, P, ls, jitter1, jitter2) -> np.ndarray:
-        """k(P,P) with the reference's jitter, as a host array (used for `cov_pred` on small grids)."""
+        """k(P,P) of the surrogate's covariance family with the reference's jitter, as a host array (used for `cov_pred` on small
+        grids)."""
         torch = self.torch
         Pd = self._dev(P)
         n, d = int(Pd.shape[0]), int(Pd.shape[1])
@@ -1336,9 +1380,9 @@ class DeviceGP:
         ls_h = np.ascontiguousarray(np.asarray(ls, dtype=np.float64).reshape(-1))
         with torch.cuda.device(self.device):
             Kp = torch.empty((npad, npad), dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_kxx_f64(self._ptr(Pd), n, d, ls_h.ctypes.data_as(C.c_void_p), jitter1, jitter2,
-                                       self._ptr(Kp), npad, self._stream())
-            _lib.check(st, "gpbo_kxx_f64")
+            st = self.lib.gpbo_kxx_kern_f64(self._ptr(Pd), n, d, ls_h.ctypes.data_as(C.c_void_p), self._kid(), jitter1, jitter2,
+                                            self._ptr(Kp), npad, self._stream())
+            _lib.check(st, "gpbo_kxx_kern_f64")
             return Kp[:n, :n].cpu().numpy()
 
     def cov_meas_pred_host(self, Xs, diag_add: float = 0.0) -> np.ndarray:
@@ -1354,10 +1398,10 @@ class DeviceGP:
             lsp = self.ls_h.ctypes.data_as(C.c_void_p)
             _lib.check(self.lib.gpbo_scale_points_f64(self._ptr(self.X), self.N, self.Np, self.d, lsp, self._ptr(xsc),
                                                       self._stream()), "gpbo_scale_points_f64")
-            st = self.lib.gpbo_kstar_mu_f64(self._ptr(Xsd), M, self._ptr(xsc), self.N, self.Np, self.d, lsp,
-                                            self._ptr(self.alpha), float(diag_add), 0, self._ptr(kst), ldk,
-                                            self._ptr(mup), self._stream())
-            _lib.check(st, "gpbo_kstar_mu_f64")
+            st = self.lib.gpbo_kstar_mu_kern_f64(self._ptr(Xsd), M, self._ptr(xsc), self.N, self.Np, self.d, lsp, self._kid(),
+                                                 self._ptr(self.alpha), float(diag_add), 0, self._ptr(kst), ldk,
+                                                 self._ptr(mup), self._stream())
+            _lib.check(st, "gpbo_kstar_mu_kern_f64")
             Kf = kst[: self.N, :M].t().contiguous().cpu().numpy()
         p = self._perm_host()
         if p is None:

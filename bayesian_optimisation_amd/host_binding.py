@@ -74,22 +74,25 @@ def nlml_grid(X, y, ls_cells, jitter: float = JITTER_KERNEL, lib=None, likelihoo
     return out
 
 
-def nlml_and_grad(X, y, ls, jitter: float = JITTER_KERNEL, lib=None):
-    """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I on host arrays: gpbo_nlml_grad_host_f64 (factorisation and
-    gradient kernel in one call).  NaN in every output when K is not positive definite.  d <= 16."""
+def nlml_and_grad(X, y, ls, jitter: float = JITTER_KERNEL, lib=None, kernel: str = "se"):
+    """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I on host arrays: gpbo_nlml_grad_host_kern_f64 (factorisation and
+    gradient kernel in one call).  NaN in every output when K is not positive definite.  d <= 16.  kernel: "se", "matern32" or
+    "matern52"."""
+    kid = _lib.kernel_id(kernel)
     lib = lib or _lib.load()
     X, y, ls, N, d = _problem(X, y, ls)
     out = np.empty(1 + d)
     _lib.note_hip_use()
-    _lib.check(lib.gpbo_nlml_grad_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), float(jitter), _ptr(out)),
-               "gpbo_nlml_grad_host_f64")
+    _lib.check(lib.gpbo_nlml_grad_host_kern_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(jitter), _ptr(out)),
+               "gpbo_nlml_grad_host_kern_f64")
     return float(out[0]), out[1:].copy()
 
 
-def nlml_hyper(X, y, ls, noise: float, fit_mean: bool = True, fit_scale: bool = True, lib=None):
+def nlml_hyper(X, y, ls, noise: float, fit_mean: bool = True, fit_scale: bool = True, lib=None, kernel: str = "se"):
     """(L, dL / d(log ls, log noise) [d + 1], mean, scale^2) of y ~ N(mean 1, scale^2 (k(X,X) + noise I)) on host arrays:
     gpbo_nlml_hyper_host_f64 (factorisation and the kernels of csrc/hyper.hip in one call).  NaN in every output when the
-    matrix is not positive definite or scale^2 is not positive.  d <= 16."""
+    matrix is not positive definite or scale^2 is not positive.  d <= 16.  kernel: "se", "matern32" or "matern52"."""
+    kid = _lib.kernel_id(kernel)
     lib = lib or _lib.load()
     X, y, ls, N, d = _problem(X, y, ls)
     noise = float(noise)
@@ -98,17 +101,19 @@ def nlml_hyper(X, y, ls, noise: float, fit_mean: bool = True, fit_scale: bool = 
     flags = (_lib.HYPER_MEAN if fit_mean else 0) | (_lib.HYPER_SCALE if fit_scale else 0)
     out = np.empty(4 + d)
     _lib.note_hip_use()
-    _lib.check(lib.gpbo_nlml_hyper_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), float(noise), flags, _ptr(out)),
-               "gpbo_nlml_hyper_host_f64")
+    _lib.check(lib.gpbo_nlml_hyper_host_kern_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(noise), flags, _ptr(out)),
+               "gpbo_nlml_hyper_host_kern_f64")
     return float(out[0]), out[1: 2 + d].copy(), float(out[2 + d]), float(out[3 + d])
 
 
 def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
                 dense: bool = True, want_cov_meas: bool = False, chunk: int = 0, lib=None,
-                jitter1: float = JITTER_KERNEL, jitter2: float = JITTER_ASSEMBLY, diag_add=None) -> dict:
+                jitter1: float = JITTER_KERNEL, jitter2: float = JITTER_ASSEMBLY, diag_add=None, kernel: str = "se") -> dict:
     """One surrogate step on host arrays.  Returns dict(best_val, best_idx, nan_count, info, mu, sigma, acq, cov_meas).
     jitter1 / jitter2: the two diagonal terms of the factorised matrix (prior variance (1 + jitter1) + jitter2); diag_add:
-    None for the reference's N == M rule, or the value itself."""
+    None for the reference's N == M rule (squared exponential only: a Matern kernel has no such quirk), or the value itself.
+    kernel: "se", "matern32" or "matern52"; a Matern step always takes the plain pass."""
+    kid = _lib.kernel_id(kernel)
     lib = lib or _lib.load()
     X, y, ls, Xs, N, d, M = _problem(X, y, ls, Xs)
     kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
@@ -118,12 +123,12 @@ def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_
     cov = np.empty((N, N)) if want_cov_meas else None
     out = _Result()
     if diag_add is None:
-        diag_add = JITTER_KERNEL if Xs.shape == X.shape else 0.0      # point_selector.py:173 shape-coincidence quirk
+        diag_add = JITTER_KERNEL if Xs.shape == X.shape and kernel == "se" else 0.0   # point_selector.py:173 shape quirk
     _lib.note_hip_use()
-    st = lib.gpbo_select_next_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), float(jitter1), float(jitter2), _ptr(Xs), M,
-                                       kind, p0, p1, float(diag_add), int(chunk), _ptr(mu), _ptr(sigma), _ptr(acq), _ptr(cov),
-                                       out.res_ptr, out.info_ptr)
-    _lib.check(st, "gpbo_select_next_host_f64")
+    st = lib.gpbo_select_next_host_kern_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(jitter1), float(jitter2), _ptr(Xs), M,
+                                            kind, p0, p1, float(diag_add), int(chunk), _ptr(mu), _ptr(sigma), _ptr(acq),
+                                            _ptr(cov), out.res_ptr, out.info_ptr)
+    _lib.check(st, "gpbo_select_next_host_kern_f64")
     return dict(out.decode(), mu=mu, sigma=sigma, acq=acq, cov_meas=cov)
 
 
@@ -226,25 +231,26 @@ class _GridOnly:
     def nlml_grid(self, X, y, ls_cells, jitter: float = JITTER_KERNEL, likelihood: str = "reference"):
         return nlml_grid(X, y, ls_cells, jitter, self.lib, likelihood)
 
-    def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL):
-        return nlml_and_grad(X, y, ls, jitter, self.lib)
+    def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL, kernel: str = "se"):
+        return nlml_and_grad(X, y, ls, jitter, self.lib, kernel)
 
-    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, **opts):
+    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, kernel: str = "se", **opts):
         from .ard_fit import fit_length_scales
 
         X, y = _f64(X), _f64(y).reshape(-1)
-        return fit_length_scales(lambda ls: self.nlml_and_grad(X, y, ls, jitter), ls0, lower, upper, **opts)
+        return fit_length_scales(lambda ls: self.nlml_and_grad(X, y, ls, jitter, kernel), ls0, lower, upper, **opts)
 
-    def nlml_hyper(self, X, y, ls, noise, fit_mean: bool = True, fit_scale: bool = True):
-        return nlml_hyper(X, y, ls, noise, fit_mean, fit_scale, self.lib)
+    def nlml_hyper(self, X, y, ls, noise, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se"):
+        return nlml_hyper(X, y, ls, noise, fit_mean, fit_scale, self.lib, kernel)
 
     def fit_hyperparameters(self, X, y, ls0, ls_lower, ls_upper, noise0: float = 1e-2, noise_lower: float = 1e-6,
-                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, **opts):
+                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se",
+                            **opts):
         from .ard_fit import fit_hyperparameters
 
         X, y = _f64(X), _f64(y).reshape(-1)
-        return fit_hyperparameters(lambda ls, noise: self.nlml_hyper(X, y, ls, noise, fit_mean, fit_scale), ls0, ls_lower,
-                                   ls_upper, noise0, noise_lower, noise_upper, **opts)
+        return fit_hyperparameters(lambda ls, noise: self.nlml_hyper(X, y, ls, noise, fit_mean, fit_scale, kernel), ls0,
+                                   ls_lower, ls_upper, noise0, noise_lower, noise_upper, **opts)
 
 
 _HostFit = _GridOnly   # (the likelihood side of the host route: grid, gradient fit, hyperparameter fit)
@@ -254,9 +260,9 @@ class PointSelectorHost(PointSelector):
     """`PointSelector` with the same attribute protocol (point_selector.py:13-207), on the host-pointer entry points."""
 
     def __init__(self, verbose: bool = False, chunk: int = 0, likelihood: str = "reference", ard: str = "grid",
-                 noise0: float = 1e-2, noise_bounds=(1e-6, 1.0)):
+                 noise0: float = 1e-2, noise_bounds=(1e-6, 1.0), kernel: str = "se"):
         super().__init__(device=None, verbose=verbose, shard_candidates=False, likelihood=likelihood, ard=ard, noise0=noise0,
-                         noise_bounds=noise_bounds)
+                         noise_bounds=noise_bounds, kernel=kernel)
         self.lib = _lib.load()
         self._gp = _GridOnly(self.lib)
         self._chunk = int(chunk)
@@ -278,11 +284,12 @@ class PointSelectorHost(PointSelector):
         X, y, ls, Xs = self._inputs
         if self._ard != "hyper":
             return self._factorised(select_next(X, y, ls, Xs, acquisition=acquisition, dense=True,
-                                                want_cov_meas=want_cov_meas, chunk=self._chunk, lib=self.lib, **kw))
+                                                want_cov_meas=want_cov_meas, chunk=self._chunk, lib=self.lib,
+                                                kernel=self._kernel, **kw))
         # the fitted model: (y - m) / s under K = k(X,X) + rho I, no N == M quirk; in and out in the units of y
         r = self._factorised(select_next(X, self._to_model(y), ls, Xs, acquisition=acquisition, dense=True,
                                          want_cov_meas=want_cov_meas, chunk=self._chunk, lib=self.lib, jitter1=self.noise,
-                                         jitter2=0.0, diag_add=0.0, **self._acq_kw(kw)))
+                                         jitter2=0.0, diag_add=0.0, kernel=self._kernel, **self._acq_kw(kw)))
         r["mu"] = self.y_mean + self.y_scale * r["mu"]
         r["sigma"] = self.y_scale * r["sigma"]
         r["acq"] = self._acq_to_y(acquisition, r["acq"])
@@ -290,6 +297,7 @@ class PointSelectorHost(PointSelector):
         return r
 
     def _not_in_hyper_mode(self, what: str):
+        self._need_se_kernel(what)
         if self._ard == "hyper":
             raise ValueError(f"PointSelectorHost(ard='hyper') supports update_surrogate(), lower_confidence_bound() and "
                              f"expected_improvement(); {what} needs PointSelector")

@@ -65,7 +65,7 @@ def _plot_hooks():
 class PointSelector:
     def __init__(self, device=None, verbose: bool = False, shard_candidates: bool = True, precision: str = "fp64",
                  incremental: bool = False, state_path=None, dense_outputs: bool = True, likelihood: str = "reference",
-                 ard: str = "grid", noise0: float = 1e-2, noise_bounds=(1e-6, 1.0)):
+                 ard: str = "grid", noise0: float = 1e-2, noise_bounds=(1e-6, 1.0), kernel: str = "se"):
         # attribute protocol of point_selector.py:15-40
         self.feature_domain = None
         self.predicted_pts = None
@@ -121,6 +121,26 @@ class PointSelector:
                 raise ValueError("ard='hyper' refits the model at every update: incremental / state_path are not available")
             if not dense_outputs:
                 raise ValueError("ard='hyper' needs dense_outputs=True (the prefix bound assumes the reference's jitters)")
+        # kernel="se" (default): the reference's squared exponential, every code path as it was.  "matern32" / "matern52" (not in
+        # the reference, whose docs name them as its first planned improvement): the Matern families on the fp64 path -
+        # factorisation, scoring, LCB / EI, loo() and the ML-II fits (ard="gradient" / "hyper", or preset kernel_params);
+        # everything built on squared-exponential kernels of its own is refused here or at the call.
+        from ._lib import kernel_id
+        kernel_id(kernel)
+        self._kernel = kernel
+        if kernel != "se":
+            if ard == "grid":
+                raise ValueError(f"kernel={kernel!r} with ard='grid': the grid kernels generate squared-exponential entries; use "
+                                 "ard='gradient' or ard='hyper' (preset kernel_params still skip the search)")
+            if precision != "fp64":
+                raise ValueError(f"kernel={kernel!r} needs precision='fp64', got precision={precision!r} (the screens build "
+                                 "squared-exponential entries)")
+            if incremental or state_path is not None:
+                raise ValueError(f"kernel={kernel!r}: incremental / state_path are not available (append() and the state file "
+                                 "are squared-exponential only)")
+            if not dense_outputs:
+                raise ValueError(f"kernel={kernel!r} needs dense_outputs=True (dense_outputs=False goes through the prefix "
+                                 "bound, which is squared-exponential only)")
         self.noise = None              # ard="hyper": fitted noise-to-signal ratio rho (noise variance = rho y_scale^2)
         self.y_mean = None             # ard="hyper": fitted constant mean m, in the units of measured_vals
         self.y_scale = None            # ard="hyper": fitted signal standard deviation s, in the units of measured_vals
@@ -162,6 +182,10 @@ class PointSelector:
     cov_meas_pred = property(lambda self: self._cov_get("cov_meas_pred"),
                              lambda self, v: self._cov_set("cov_meas_pred", v),
                              doc="k(X,X*).T (point_selector.py:81); None above COV_MEAS_PRED_MAX entries")
+
+    def _need_se_kernel(self, what: str):
+        if self._kernel != "se":
+            raise ValueError(f"{what} is not available with kernel={self._kernel!r}: it supports kernel='se' only")
 
     def _log(self, *a):
         if self._verbose:
@@ -209,13 +233,14 @@ class PointSelector:
         hyper = self._ard == "hyper"
         if hyper:
             # the fitted model: the GP of (y - m) / s with K = k(X,X) + rho I; the N == M quirk is a reference artefact
-            gp.factorise(X, self._to_model(y), ls, self.noise, 0.0, check=True, order="arrival")
+            gp.factorise(X, self._to_model(y), ls, self.noise, 0.0, check=True, order="arrival", kernel=self._kernel)
             self.last_update = "factorise"
         else:
             self._factorise_or_append(gp, X, y, ls)                       # :79, :89 (raises LinAlgError)
 
         M, N = len(Xs), len(X)
-        diag_add = JITTER_KERNEL if Xs.shape == X.shape and not hyper else 0.0   # :173 shape-coincidence quirk
+        # :173 shape-coincidence quirk (of the reference's kernel_rbf: not with a fitted model, not with a Matern kernel)
+        diag_add = JITTER_KERNEL if Xs.shape == X.shape and not hyper and self._kernel == "se" else 0.0
         world, rank = self._world()
         lo, hi = D.shard_bounds(M, world, rank)
         if not self._dense:
@@ -360,7 +385,8 @@ class PointSelector:
             # factorisation (DeviceGP.score_bound), so those are chosen to cover the region whatever the order of the
             # history; not with the N == M quirk, which is keyed on the arrival index (:173)
             fps = not self._dense and np.shape(self.predicted_pts) != np.shape(X)
-            gp.factorise(X, y, ls, JITTER_KERNEL, JITTER_ASSEMBLY, check=True, order="fps" if fps else "arrival")
+            gp.factorise(X, y, ls, JITTER_KERNEL, JITTER_ASSEMBLY, check=True, order="fps" if fps else "arrival",
+                         kernel=self._kernel)
             if fps and self._shard and self._world()[0] > 1:
                 # the order is part of the factorisation: if the selection fell back to the arrival order on ANY rank, every
                 # rank refactorises in arrival order (identical factors on all shards: the cross-shard tie rule needs them)
@@ -480,10 +506,10 @@ class PointSelector:
             # the same box and start for the length scales; the noise-to-signal ratio joins them, mean and scale are profiled
             if np.ptp(y) == 0.0:
                 raise np.linalg.LinAlgError("the likelihood is not finite: constant measured_vals leave no signal variance to fit")
-            res = self._gp.fit_hyperparameters(X, y, ls0, lower, upper, self._noise0, *self._noise_bounds)
+            res = self._gp.fit_hyperparameters(X, y, ls0, lower, upper, self._noise0, *self._noise_bounds, kernel=self._kernel)
             self.noise, self.y_mean, self.y_scale = float(res.noise), float(res.mean), float(res.scale)
         else:
-            res = self._gp.fit_length_scales(X, y, ls0, lower, upper)
+            res = self._gp.fit_length_scales(X, y, ls0, lower, upper, kernel=self._kernel)
         self.kernel_params = np.asarray(res.ls, dtype=np.float64).reshape(shape)
         self.hyperparam_obj = [float(v) for v in res.trace]
         self.nlogml = np.asarray(res.trace, dtype=np.float64)
@@ -534,6 +560,7 @@ class PointSelector:
         of the first batch with the largest qEI, and leaves the per-batch values in `acq_func_eval` (1-D).
         Fixed base samples: default_rng(seed).standard_normal((n_samples, 8)).  Batches are sharded over the
         ranks like single candidates are."""
+        self._need_se_kernel("q_expected_improvement()")
         if self._cached is None:
             raise RuntimeError("call update_surrogate() first")
         fd = [int(v) for v in self.feature_domain]
@@ -582,6 +609,7 @@ class PointSelector:
         acq_func_eval stay as update_surrogate() set them (the selection works on copies of the device posterior).
         Needs precision="fp64", dense_outputs=True and candidates of another shape than the observations (the N == M
         quirk); candidates sharded over more than one rank are OUT OF SCOPE: NotImplementedError."""
+        self._need_se_kernel("select_batch()")
         if self._cached is None:
             raise RuntimeError("call update_surrogate() first")
         if self._precision != "fp64":
@@ -611,6 +639,7 @@ class PointSelector:
         non-finite coordinate; candidates sharded over more than one rank are OUT OF SCOPE: NotImplementedError."""
         from .thompson import select_params
 
+        self._need_se_kernel("select_thompson()")
         if self._cached is None:
             raise RuntimeError("call update_surrogate() first")
         Xs = np.asarray(self.predicted_pts, dtype=np.float64)
@@ -659,6 +688,7 @@ class PointSelector:
         xi).  mean_func / cov_func / acq_func_eval and every other attribute stay as they are; IndexError when the
         acquisition contains NaN.  With sharded candidates every rank refines the same global starts on the replicated
         factorisation (same bits on every rank, no collective)."""
+        self._need_se_kernel("refine_next()")
         kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
         r = self._gp.refine(starts, lo, hi, iters=int(iters), prior_var=self._prior_var(), **self._acq_kw(kw))
         if r.nan_count > 0 or r.best < 0:

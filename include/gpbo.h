@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_kxx_kern_f64 / gpbo_kstar_mu_kern_f64 / gpbo_factorise_kern_f64 / gpbo_posterior_acq_kern_f64 / gpbo_nlml_grad_kern_f64 / gpbo_nlml_hyper_kern_f64 / gpbo_select_next_host_kern_f64 / gpbo_nlml_grad_host_kern_f64 / gpbo_nlml_hyper_host_kern_f64, the Matern 3/2 and 5/2 covariance families on the fp64 path; gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -51,6 +51,12 @@ extern "C" {
 #define GPBO_NPAD 128          /* observation padding granule (column-block width of the variance kernel) */
 #define GPBO_CHUNK_GRANULE 512 /* candidate-chunk granule */
 #define GPBO_CHUNK_MAX (1 << 24) /* largest chunk (16-row tile offsets inside K*^T are 32-bit element offsets) */
+
+/* Covariance families (the `kernel` argument of the gpbo_*_kern_f64 entry points; every other entry is the squared exponential).
+ * r^2 = sum_k (x_k - x'_k)^2 / ls_k^2 with the ARD length scales; all three have unit prior variance, k(x, x) = 1 exactly. */
+#define GPBO_KERNEL_SE 0       /* k = exp(-r^2 / 2): the reference's kernel_rbf (point_selector.py:166-195) */
+#define GPBO_KERNEL_MATERN32 1 /* a = sqrt(3) r, k = (1 + a) exp(-a)             (not in the reference) */
+#define GPBO_KERNEL_MATERN52 2 /* a = sqrt(5) r, k = (1 + a + a^2 / 3) exp(-a)   (not in the reference) */
 
 #define GPBO_ACQ_LCB 0 /* acq = p0*sigma - mu            (point_selector.py:204, p0 = explore) */
 #define GPBO_ACQ_EI 1  /* acq = EI for minimisation, p0 = f_best, p1 = xi (not in the reference) */
@@ -578,6 +584,52 @@ int gpbo_nlml_hyper_host_f64(const double *X_host, const double *y_host, int64_t
 int64_t gpbo_loo_workspace_bytes(int64_t Np);
 int gpbo_loo_f64(const double *U, const double *alpha, const double *y, int64_t N, int64_t Np, double scale2, double *mu_out,
                  double *var_out, double *kinv_diag_out, void *work, int64_t work_bytes, void *stream);
+
+/* ---- The Matern covariance families (not in the reference, whose docs/README.md names them as its first planned improvement).
+ * Each entry below is its squared-exponential twin with `int32_t kernel` (GPBO_KERNEL_*) inserted after ls_host; the twin is a
+ * one-line forward with GPBO_KERNEL_SE, so kernel = 0 gives the twin's results bit for bit.  Workspaces are those of the twins
+ * (the same *_workspace_bytes queries).  With r^2 = sum_k (x_k - x'_k)^2 / ls_k^2:
+ *   GPBO_KERNEL_MATERN32   a = sqrt(3) r,  k = (1 + a) exp(-a),             dk / dlog ls_k = 3 exp(-a) (x_k - x'_k)^2 / ls_k^2
+ *   GPBO_KERNEL_MATERN52   a = sqrt(5) r,  k = (1 + a + a^2 / 3) exp(-a),   dk / dlog ls_k = 5/3 (1 + a) exp(-a) (x_k - x'_k)^2 / ls_k^2
+ * (nothing is divided by r: coincident points need no special case).  Only three kernels evaluate covariance entries - K(X,X),
+ * K(X*,X) and the epilogue of the likelihood gradient - so the factorisation, alpha, the variance product, the acquisitions, the
+ * arg-max, the profiled mean and scale of gpbo_nlml_hyper_f64 and gpbo_loo_f64 serve every family unchanged.  The diagonal of
+ * K(X,X) is (1 + jitter1) + jitter2 as for the squared exponential.
+ * Refused with GPBO_ERR_ARG before any HIP call: a kernel id outside {0, 1, 2}; a Matern id with d > GPBO_MAX_D (the any-d slow
+ * path is squared-exponential only); a Matern id with diag_add != 0 (the N == M quirk reproduces a shape coincidence of the
+ * reference's kernel_rbf and belongs to that kernel alone).  gpbo_select_next_host_kern_f64 with a Matern id always takes the
+ * plain pass (the prefix bound builds its mean with squared-exponential entries).  Everything else of the ABI - append, the
+ * fp32 / int8 screens, the prefix bound, qEI, batches, Thompson sampling, refinement, the likelihood grids - is
+ * squared-exponential only. */
+int gpbo_kxx_kern_f64(const double *X, int64_t N, int32_t d, const double *ls_host, int32_t kernel, double jitter1, double jitter2,
+                      double *Kp, int64_t Np, void *stream);
+int gpbo_kstar_mu_kern_f64(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
+                           const double *ls_host, int32_t kernel, const double *alpha, double diag_add, int64_t cand_base,
+                           double *KsT, int64_t ldk, double *mu_part, void *stream);
+int gpbo_factorise_kern_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls_host, int32_t kernel,
+                            double jitter1, double jitter2, int64_t Np, double *Kp, double *U, double *alpha, int32_t *info,
+                            void *work, int64_t work_bytes, void *stream);
+int gpbo_posterior_acq_kern_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
+                                const double *ls_host, int32_t kernel, const double *U, const double *alpha, double prior_var,
+                                int32_t acq_kind, double p0, double p1, double diag_add, int64_t idx_offset, int64_t chunk,
+                                double *mu_out, double *sigma_out, double *acq_out, gpbo_result *result, void *work,
+                                int64_t work_bytes, gpbo_profile *prof /* or NULL */, void *stream);
+int gpbo_nlml_grad_kern_f64(const double *U, const double *alpha, const double *y, const double *X, int64_t N, int64_t Np,
+                            int32_t d, const double *ls_host, int32_t kernel, const int32_t *info, double *out, void *work,
+                            int64_t work_bytes, void *stream);
+int gpbo_nlml_hyper_kern_f64(const double *U, const double *alpha, const double *y, const double *X, int64_t N, int64_t Np,
+                             int32_t d, const double *ls_host, int32_t kernel, double noise, int32_t flags, const int32_t *info,
+                             double *out /* [d + 4] */, double *alpha_std_out /* optional [Np] */, void *work,
+                             int64_t work_bytes, void *stream);
+int gpbo_select_next_host_kern_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
+                                   int32_t kernel, double jitter1, double jitter2, const double *Xs_host, int64_t M,
+                                   int32_t acq_kind, double p0, double p1, double diag_add, int64_t chunk, double *mu_out_host,
+                                   double *sigma_out_host, double *acq_out_host, double *cov_meas_out_host,
+                                   gpbo_result *result_host, int32_t *info_host);
+int gpbo_nlml_grad_host_kern_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
+                                 int32_t kernel, double jitter, double *out_host);
+int gpbo_nlml_hyper_host_kern_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
+                                  int32_t kernel, double noise, int32_t flags, double *out_host /* [d + 4] */);
 
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;
