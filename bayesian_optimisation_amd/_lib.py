@@ -254,10 +254,3 @@ def check(status: int, what: str):
         msg = load().gpbo_strerror(status).decode()
         raise GpboError(f"{what}: {msg} (status {status})")
 
-
-def host_f64(arr):
-    """ctypes pointer to a contiguous fp64 host array (kept alive by the caller)."""
-    import numpy as np
-
-    a = np.ascontiguousarray(arr, dtype=np.float64)
-    return a, a.ctypes.data_as(C.c_void_p)

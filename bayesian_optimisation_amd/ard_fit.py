@@ -2,8 +2,8 @@
 
 Not in the reference, which planned it (point_selector.py:30 `hyperparam_obj`, :33 `gradient_steps`) and searches a
 grid instead (:104-163).  The objective is any function ls -> (value, gradient with respect to log ls); the package
-drives it with the negative log marginal likelihood and its gradient from the GPU (DeviceGP.nlml_and_grad,
-csrc/ard_grad.hip).  Working in log ls keeps the length scales positive and makes the box [lower, upper] a box in the
+drives it with the negative log marginal likelihood and its gradient from the GPU (gp_device.LikelihoodFits over
+DeviceGP.nlml_and_grad or the host-pointer binding's, csrc/ard_grad.hip).  Working in log ls keeps the length scales positive and makes the box [lower, upper] a box in the
 optimisation variable.
 
 The method (deterministic for a deterministic objective):

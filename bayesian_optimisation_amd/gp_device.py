@@ -6,19 +6,21 @@ plumbing only; every number is produced by the HIP kernels behind the C ABI (inc
 Mirrors the arithmetic of PointSelector.update_surrogate / lower_confidence_bound
 (/root/reference/point_selector.py:76-98, 197-207) with the factorisation done once per BO step and
 the candidates streamed in chunks.  There is no CPU path: without libgpbo.so or a GPU this raises.
+The ML-II fits are written once, in `LikelihoodFits`, over a provider's nlml_and_grad() / nlml_hyper(): DeviceGP here (device
+tensors, one input check and one factorise-into-fit-buffers step for both) and host_binding's host-pointer provider.
 """
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, ard_fit
+from .model import JITTER_ASSEMBLY, JITTER_KERNEL, need_se  # noqa: F401  (the two jitters are part of this module's API)
 
-JITTER_KERNEL = 1e-4    # point_selector.py:193
-JITTER_ASSEMBLY = 1e-6  # point_selector.py:78-79
 # the IndexError of an acquisition with NaN in it: the reference's own failure, in NumPy's words (point_selector.py:207)
 NAN_ACQUISITION = "index 0 is out of bounds for axis 0 with size 0 (acquisition contains NaN)"
 PRIOR_VAR = (1.0 + JITTER_KERNEL) + JITTER_ASSEMBLY  # diagonal of cov_pred as the reference rounds it
@@ -164,7 +166,28 @@ def fantasy_params(fantasy: str, lie: Optional[float]) -> tuple:
     raise ValueError(f"fantasy must be 'believer' or 'liar', got {fantasy!r}")
 
 
-class DeviceGP:
+class LikelihoodFits:
+    """The ML-II fits (ard_fit.py) over a provider's nlml_and_grad() / nlml_hyper().  The provider's _fit_session(X, y) is a
+    context manager around one fit: it yields the (X, y) every evaluation receives and cleans up behind the fit."""
+
+    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, kernel: str = "se", **opts):
+        """ML-II fit of the ARD length scales inside [lower, upper] from ls0 (ard_fit.fit_length_scales: projected L-BFGS
+        in log ls, every evaluation one nlml_and_grad).  Returns the FitResult."""
+        with self._fit_session(X, y) as (X, y):
+            return ard_fit.fit_length_scales(lambda ls: self.nlml_and_grad(X, y, ls, jitter, kernel), ls0, lower, upper, **opts)
+
+    def fit_hyperparameters(self, X, y, ls0, ls_lower, ls_upper, noise0: float = 1e-2, noise_lower: float = 1e-6,
+                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se",
+                            **opts):
+        """ML-II fit of the length scales and the noise-to-signal ratio inside their boxes, mean and signal variance profiled
+        out (ard_fit.fit_hyperparameters: projected L-BFGS in the d + 1 log variables, every evaluation one nlml_hyper).
+        Returns the HyperFitResult."""
+        with self._fit_session(X, y) as (X, y):
+            return ard_fit.fit_hyperparameters(lambda ls, noise: self.nlml_hyper(X, y, ls, noise, fit_mean, fit_scale, kernel),
+                                               ls0, ls_lower, ls_upper, noise0, noise_lower, noise_upper, **opts)
+
+
+class DeviceGP(LikelihoodFits):
     """One BO step's surrogate on one GPU: factorise once, then score any number of candidates."""
 
     def __init__(self, device=None, chunk: int = DEFAULT_CHUNK):
@@ -269,12 +292,6 @@ class DeviceGP:
             w = self.torch.empty((nbytes + 7) // 8, dtype=self.torch.float64, device=self.device)
             setattr(self, slot_name, w)
         return w
-
-    def _need_se(self, what: str):
-        """The calls that build covariance entries with squared-exponential kernels of their own refuse a surrogate of another
-        family (each is a follow-up of its own: DESIGN.md 4g)."""
-        if self.kernel != "se":
-            raise ValueError(f"{what} is not available with kernel={self.kernel!r}: it supports kernel='se' only")
 
     def _kid(self) -> int:
         return _lib.KERNEL_IDS[self.kernel]
@@ -439,7 +456,7 @@ class DeviceGP:
         An appended column goes through the explicit inverse factor (l = U^T k), so it carries cond(L) eps of
         relative error where the blocked Cholesky is backward stable: `n_appended` counts the columns built this way
         since the last full factorisation, for callers that want to refresh after a while (PointSelector does)."""
-        self._need_se("append()")
+        need_se(self.kernel, "append()")
         self._need_unrolled_d("append()")
         torch = self.torch
         if self.N < 1:
@@ -488,7 +505,7 @@ class DeviceGP:
     # -- persistence across jobs: the DAG's select_parameters jobs are separate processes --------------------
     def state_dict(self) -> dict:
         """Host copy of everything append()/score() need (the N x N part of the factors, not the padding)."""
-        self._need_se("state_dict()")
+        need_se(self.kernel, "state_dict()")
         N = self.N
         st = dict(version=1, N=N, d=self.d, ls=np.array(self.ls_h), jitter1=self.jitter1, jitter2=self.jitter2,
                   n_appended=self.n_appended,
@@ -499,7 +516,7 @@ class DeviceGP:
         return st
 
     def load_state_dict(self, st: dict):
-        self._need_se("load_state_dict()")
+        need_se(self.kernel, "load_state_dict()")
         torch = self.torch
         if int(st.get("version", 0)) != 1:
             raise ValueError("unknown surrogate state version")
@@ -541,7 +558,7 @@ class DeviceGP:
         import os
         import tempfile
 
-        self._need_se("save_state()")
+        need_se(self.kernel, "save_state()")
         path = str(path)
         if not path.endswith(".npz"):
             path += ".npz"  # what np.savez would have appended
@@ -561,7 +578,7 @@ class DeviceGP:
             raise
 
     def load_state(self, path: str):
-        self._need_se("load_state()")
+        need_se(self.kernel, "load_state()")
         with np.load(path) as z:
             return self.load_state_dict({k: z[k] for k in z.files})
 
@@ -649,7 +666,7 @@ class DeviceGP:
         its lowest index.  Dense outputs (mu exactly the fp64 path's; sigma / acq with the screen's variance) are
         float64 tensors.  Unlike score_async this call synchronises (the survivor count is read back).
         `last_screen` keeps the statistics of the call."""
-        self._need_se(f"the {mode} screen (score_{mode}())")
+        need_se(self.kernel, f"the {mode} screen (score_{mode}())")
         self._need_unrolled_d(f"the {mode} screen")
         torch = self.torch
         Xsd, M = self._candidates(Xs)
@@ -764,7 +781,7 @@ class DeviceGP:
         clustered).  Bounds and exact values come from the same U, the same K(X*,X) kernel and the same variance
         kernel: |v[:J]|^2 is a partial sum of the squares score() adds up.
         Synchronises; `last_screen` keeps the statistics."""
-        self._need_se("score_bound()")
+        need_se(self.kernel, "score_bound()")
         torch = self.torch
         if self.d > _lib.MAX_D:   # the slow any-d kernels serve the plain pass only
             self.last_screen = dict(mode="bound", fallback=True, reason="d > 16")
@@ -836,7 +853,7 @@ class DeviceGP:
         Returns (result_tensor, qei or None); the result's best_idx is a BATCH index.
         Z must be finite: a host array is checked here, a device tensor is the caller's (the kernel skips the improvements
         a NaN sample makes NaN instead of reporting them: DESIGN.md 1, "qEI and NaN")."""
-        self._need_se("score_qei()")
+        need_se(self.kernel, "score_qei()")
         self._need_unrolled_d("qEI")
         torch = self.torch
         if isinstance(Z, np.ndarray) and not np.isfinite(Z).all():
@@ -879,7 +896,7 @@ class DeviceGP:
         EI keeps the f_best it is given for the whole batch: with fantasy="liar" and lie < f_best the later members are still
         scored against f_best, not against the lie (the NumPy reference of the tests, tests/batch_ref.py, does the same).
         A caller who wants the lie to count as the incumbent passes f_best = min(f_best, lie)."""
-        self._need_se("select_batch_on_posterior()")
+        need_se(self.kernel, "select_batch_on_posterior()")
         self._need_unrolled_d("select_batch()")
         torch = self.torch
         Xsd, M = self._candidates(Xs)
@@ -917,7 +934,7 @@ class DeviceGP:
         chosen so far excluded.  Runs the dense plain pass, then gpbo_select_batch_f64: per member N kernel entries per
         candidate instead of the N^2 of a pass after append().  The factorisation (U, alpha, N) is not touched.
         d <= 16; not with the N == M shape quirk (diag_add)."""
-        self._need_se("select_batch()")
+        need_se(self.kernel, "select_batch()")
         if diag_add != 0.0:
             raise ValueError("select_batch() does not support diag_add (the N == M shape quirk)")
         self._need_unrolled_d("select_batch()")
@@ -939,7 +956,7 @@ class DeviceGP:
         only.  The paths stay valid until the next factorise() / append() / load_state_dict()."""
         from .thompson import path_params, thompson_draws
 
-        self._need_se("thompson_paths()")
+        need_se(self.kernel, "thompson_paths()")
         n_paths, n_features, seed = path_params(n_paths, n_features, seed)
         self._need_unrolled_d("thompson_paths()")
         if self.N < 1:
@@ -967,7 +984,7 @@ class DeviceGP:
         acquisition -f_s there and, with dense=True, the paths themselves [n_paths x M] on the device.  One read-back
         (synchronises).  IndexError when a value is NaN (a candidate with a non-finite coordinate), as the other
         acquisitions raise."""
-        self._need_se("thompson_score()")
+        need_se(self.kernel, "thompson_score()")
         self._need_unrolled_d("thompson_score()")
         if not isinstance(paths, ThompsonPaths) or paths.epoch != (id(self), self._epoch):
             raise ValueError("these sample paths do not belong to the surrogate as it is now: call thompson_paths() again "
@@ -1002,7 +1019,7 @@ class DeviceGP:
         ValueError on bad q / n_paths / n_features / seed before any GPU work; IndexError when a value is NaN."""
         from .thompson import first_distinct, select_params
 
-        self._need_se("select_thompson()")
+        need_se(self.kernel, "select_thompson()")
         self._need_unrolled_d("select_thompson()")
         Xsd, M = self._candidates(Xs)
         q, n_paths, n_features, seed = select_params(q, n_paths, n_features, seed, M=M, d=self.d)
@@ -1025,7 +1042,7 @@ class DeviceGP:
         """Posterior mean, standard deviation and acquisition at the rows of Xq [P x d] (P <= 4096) with their gradients in
         x (gpbo_posterior_grad_f64).  Query points, not candidates: the N == M quirk (diag_add) does not apply.  Works on
         the factorisation as it is (any order=, appended rows included).  Enqueues only; device tensors come back."""
-        self._need_se("posterior_grad()")
+        need_se(self.kernel, "posterior_grad()")
         self._need_unrolled_d("posterior_grad()")
         torch = self.torch
         Xd, P = self._points(Xq, "Xq")
@@ -1051,7 +1068,7 @@ class DeviceGP:
         [lower, upper] (gpbo_refine_f64; the rule is stated in include/gpbo.h): each start on its own, step doubled after an
         accepted trial and halved after a rejected one, iters trials.  All iters + 1 evaluations are enqueued at once;
         one read-back of the result record (synchronises).  Two calls give the same bits."""
-        self._need_se("refine()")
+        need_se(self.kernel, "refine()")
         self._need_unrolled_d("refine()")
         torch = self.torch
         Xd, P = self._points(starts, "starts")
@@ -1080,7 +1097,7 @@ class DeviceGP:
         """The dense score() of the candidates Xs, then refine() from the n_starts candidates with the largest acquisition
         (stable descending sort: ties keep the lower index first).  lower / upper omitted: the per-feature minimum / maximum
         of Xs.  Returns refine()'s result with grid_idx / grid_val = score()'s arg-max and its value."""
-        self._need_se("select_refined()")
+        need_se(self.kernel, "select_refined()")
         self._need_unrolled_d("select_refined()")
         torch = self.torch
         Xsd, M = self._candidates(Xs)
@@ -1162,7 +1179,7 @@ class DeviceGP:
 
     def nlml_grid_device(self, X, y, ls_cells, jitter: float = JITTER_KERNEL, likelihood: str = "reference"):
         """The same grid left on the device (float32 / float64 tensor [G]); enqueues on the current stream, no read-back."""
-        self._need_se("nlml_grid()")   # (the grid kernels generate squared-exponential entries)
+        need_se(self.kernel, "nlml_grid()")   # (the grid kernels generate squared-exponential entries)
         if likelihood not in ("reference", "logdet"):
             raise ValueError(f"likelihood must be 'reference' or 'logdet', got {likelihood!r}")
         torch = self.torch
@@ -1221,11 +1238,8 @@ class DeviceGP:
         fb = self._fit_bufs or {}
         return sum(t.numel() * t.element_size() for t in fb.values() if isinstance(t, self.torch.Tensor))
 
-    def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL, kernel: str = "se"):
-        """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I - the "logdet" likelihood and its gradient - from a
-        factorisation into the fit's own buffers (the surrogate held by this object is not touched).  NaN in every
-        output when K is not positive definite.  d <= 16.  kernel: the covariance family k (factorise())."""
-        torch = self.torch
+    def _fit_problem(self, X, y, ls, kernel):
+        """The input check of the two likelihood calls: (kernel id, X and y on the device, N, d, length scales on the host)."""
         kid = _lib.kernel_id(kernel)
         Xd, yd = self._dev(X), self._dev(y).reshape(-1)
         if Xd.dim() != 2:
@@ -1240,14 +1254,27 @@ class DeviceGP:
             raise ValueError(f"length scales: expected {d} values, got {ls_h.size}")
         if not np.all(ls_h > 0):
             raise ValueError("length scales must be positive")
+        return kid, Xd, yd, N, d, ls_h
+
+    def _fit_factorise(self, kid, Xd, yd, N, d, ls_h, jitter):
+        """K = k(X,X) + jitter I factorised into the fit's own buffers (enqueued; inside torch.cuda.device(self.device)).
+        Returns (buffers, padded N, pointer to the length scales)."""
         Np = int(self.lib.gpbo_padded_n(N))
-        with torch.cuda.device(self.device):
-            fb = self._fit_buffers(Np, d)
-            lsp = ls_h.ctypes.data_as(C.c_void_p)
-            st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, kid, float(jitter), 0.0, Np,
-                                                  self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
-                                                  self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
-            _lib.check(st, "gpbo_factorise_kern_f64")
+        fb = self._fit_buffers(Np, d)
+        lsp = ls_h.ctypes.data_as(C.c_void_p)
+        st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, kid, float(jitter), 0.0, Np,
+                                              self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
+                                              self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
+        _lib.check(st, "gpbo_factorise_kern_f64")
+        return fb, Np, lsp
+
+    def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL, kernel: str = "se"):
+        """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I - the "logdet" likelihood and its gradient - from a
+        factorisation into the fit's own buffers (the surrogate held by this object is not touched).  NaN in every
+        output when K is not positive definite.  d <= 16.  kernel: the covariance family k (factorise())."""
+        kid, Xd, yd, N, d, ls_h = self._fit_problem(X, y, ls, kernel)
+        with self.torch.cuda.device(self.device):
+            fb, Np, lsp = self._fit_factorise(kid, Xd, yd, N, d, ls_h, jitter)
             st = self.lib.gpbo_nlml_grad_kern_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N,
                                                   Np, d, lsp, kid, self._ptr(fb["info"]), self._ptr(fb["out"]),
                                                   self._ptr(fb["work_grad"]), fb["wg"], self._stream())
@@ -1255,15 +1282,13 @@ class DeviceGP:
             out = fb["out"][: 1 + d].cpu().numpy()   # synchronises
         return float(out[0]), out[1:].copy()
 
-    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, kernel: str = "se", **opts):
-        """ML-II fit of the ARD length scales inside [lower, upper] from ls0 (ard_fit.fit_length_scales: projected L-BFGS
-        in log ls, every evaluation one factorisation + one gradient launch).  Returns the FitResult.  The fit's buffers
-        are released afterwards when larger than ARD_KEEP_WORKSPACE_BYTES."""
-        from .ard_fit import fit_length_scales
-
-        Xd, yd = self._dev(X), self._dev(y).reshape(-1)   # uploaded once for all evaluations
+    @contextmanager
+    def _fit_session(self, X, y):
+        """X and y uploaded once for all evaluations of a fit; the fit's buffers are released afterwards when larger than
+        ARD_KEEP_WORKSPACE_BYTES."""
+        Xd, yd = self._dev(X), self._dev(y).reshape(-1)
         try:
-            return fit_length_scales(lambda ls: self.nlml_and_grad(Xd, yd, ls, jitter, kernel), ls0, lower, upper, **opts)
+            yield Xd, yd
         finally:
             if self._fit_bytes() > self.ARD_KEEP_WORKSPACE_BYTES:
                 self._fit_bufs = None
@@ -1276,27 +1301,13 @@ class DeviceGP:
         object is not touched).  NaN in every output when the matrix is not positive definite or scale^2 is not positive
         (one observation, a constant y).  d <= 16.  kernel: the covariance family k (factorise())."""
         torch = self.torch
-        kid = _lib.kernel_id(kernel)
-        Xd, yd = self._dev(X), self._dev(y).reshape(-1)
-        if Xd.dim() != 2:
-            raise ValueError("X must be (N, d)")
-        N, d = int(Xd.shape[0]), int(Xd.shape[1])
-        if d > _lib.MAX_D:
-            raise ValueError(f"the likelihood gradient supports d <= {_lib.MAX_D}, got {d}")
-        if yd.numel() != N:
-            raise ValueError("y must have one value per row of X")
-        ls_h = np.ascontiguousarray(np.asarray(ls, dtype=np.float64).reshape(-1))
-        if ls_h.size != d:
-            raise ValueError(f"length scales: expected {d} values, got {ls_h.size}")
-        if not np.all(ls_h > 0):
-            raise ValueError("length scales must be positive")
+        kid, Xd, yd, N, d, ls_h = self._fit_problem(X, y, ls, kernel)
         noise = float(noise)
         if not (np.isfinite(noise) and noise > 0.0):
             raise ValueError(f"noise must be positive and finite, got {noise!r}")
         flags = (_lib.HYPER_MEAN if fit_mean else 0) | (_lib.HYPER_SCALE if fit_scale else 0)
-        Np = int(self.lib.gpbo_padded_n(N))
         with torch.cuda.device(self.device):
-            fb = self._fit_buffers(Np, d)
+            fb, Np, lsp = self._fit_factorise(kid, Xd, yd, N, d, ls_h, noise)
             if "work_hyper" not in fb:
                 wh = int(self.lib.gpbo_nlml_hyper_workspace_bytes(Np, fb["d"]))
                 if wh < 0:
@@ -1304,11 +1315,6 @@ class DeviceGP:
                 fb["work_hyper"] = torch.empty((wh + 7) // 8, dtype=torch.float64, device=self.device)
                 fb["wh"] = wh
                 fb["out_hyper"] = torch.empty(4 + fb["d"], dtype=torch.float64, device=self.device)
-            lsp = ls_h.ctypes.data_as(C.c_void_p)
-            st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, kid, noise, 0.0, Np,
-                                                  self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
-                                                  self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
-            _lib.check(st, "gpbo_factorise_kern_f64")
             st = self.lib.gpbo_nlml_hyper_kern_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N,
                                                    Np, d, lsp, kid, noise, flags, self._ptr(fb["info"]),
                                                    self._ptr(fb["out_hyper"]), None, self._ptr(fb["work_hyper"]), fb["wh"],
@@ -1316,23 +1322,6 @@ class DeviceGP:
             _lib.check(st, "gpbo_nlml_hyper_kern_f64")
             out = fb["out_hyper"][: 4 + d].cpu().numpy()   # synchronises
         return float(out[0]), out[1: 2 + d].copy(), float(out[2 + d]), float(out[3 + d])
-
-    def fit_hyperparameters(self, X, y, ls0, ls_lower, ls_upper, noise0: float = 1e-2, noise_lower: float = 1e-6,
-                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se",
-                            **opts):
-        """ML-II fit of the length scales and the noise-to-signal ratio inside their boxes, mean and signal variance profiled
-        out (ard_fit.fit_hyperparameters: projected L-BFGS in the d + 1 log variables, every evaluation one factorisation and
-        one nlml_hyper).  Returns the HyperFitResult.  The fit's buffers are released afterwards when larger than
-        ARD_KEEP_WORKSPACE_BYTES."""
-        from .ard_fit import fit_hyperparameters
-
-        Xd, yd = self._dev(X), self._dev(y).reshape(-1)   # uploaded once for all evaluations
-        try:
-            return fit_hyperparameters(lambda ls, noise: self.nlml_hyper(Xd, yd, ls, noise, fit_mean, fit_scale, kernel), ls0,
-                                       ls_lower, ls_upper, noise0, noise_lower, noise_upper, **opts)
-        finally:
-            if self._fit_bytes() > self.ARD_KEEP_WORKSPACE_BYTES:
-                self._fit_bufs = None
 
     def loo(self, scale2: float = 1.0):
         """Leave-one-out prediction of every observation from the factorisation held by this object (gpbo_loo_f64: the diagonal

@@ -7,6 +7,9 @@ This is the ctypes stub a maintainer of the reference would write against includ
 library, which costs a few milliseconds per step against the tensor-resident `PointSelector`; the numbers are the
 same (same kernels).  Not available here: candidate sharding over several GPUs, the incremental factorisation,
 fp32 / int8 screening - those need the device-pointer API behind `PointSelector`.
+`PointSelectorHost` is `PointSelector` with two methods of its own - update_surrogate() and _score_acq(), one
+gpbo_select_next_host_kern_f64 call with the update's model.SurrogateModel - between the shared prologue, epilogue and
+_finish; `_GridOnly` supplies the likelihoods to the shared search and fits (gp_device.LikelihoodFits).
 A process that uses both this binding and the PyTorch-based classes must `import torch` before its first call here
 (bringing PyTorch's GPU context up after this library has initialised HIP was seen to dead-lock now and then; the
 PyTorch-based classes refuse that order with a clear error).
@@ -14,11 +17,13 @@ PyTorch-based classes refuse that order with a clear error).
 from __future__ import annotations
 
 import ctypes as C
+from contextlib import contextmanager
 
 import numpy as np
 
 from . import _lib
-from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, NAN_ACQUISITION, acq_params, fantasy_params, refine_box, refine_params
+from .gp_device import NAN_ACQUISITION, LikelihoodFits, acq_params, fantasy_params, refine_box, refine_params
+from .model import JITTER_ASSEMBLY, JITTER_KERNEL, SurrogateModel, need_se
 from .point_selector import PointSelector
 
 
@@ -117,13 +122,11 @@ def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_
     lib = lib or _lib.load()
     X, y, ls, Xs, N, d, M = _problem(X, y, ls, Xs)
     kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
-    mu = np.empty(M) if dense else None
-    sigma = np.empty(M) if dense else None
-    acq = np.empty(M) if dense else None
+    mu, sigma, acq = (np.empty(M) if dense else None for _ in range(3))
     cov = np.empty((N, N)) if want_cov_meas else None
     out = _Result()
     if diag_add is None:
-        diag_add = JITTER_KERNEL if Xs.shape == X.shape and kernel == "se" else 0.0   # point_selector.py:173 shape quirk
+        diag_add = SurrogateModel(kernel, jitter1, jitter2).diag_add(Xs.shape, X.shape)   # point_selector.py:173 shape quirk
     _lib.note_hip_use()
     st = lib.gpbo_select_next_host_kern_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(jitter1), float(jitter2), _ptr(Xs), M,
                                             kind, p0, p1, float(diag_add), int(chunk), _ptr(mu), _ptr(sigma), _ptr(acq),
@@ -161,8 +164,7 @@ def select_batch(X, y, ls, Xs, q: int, acquisition: str = "lcb", explore: float 
     kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
     fkind, fl = fantasy_params(fantasy, lie)
     idx, val = np.full(q, -1, dtype=np.int64), np.full(q, np.nan)
-    mu = np.empty(M) if dense else None
-    sigma = np.empty(M) if dense else None
+    mu, sigma = (np.empty(M) if dense else None for _ in range(2))
     out = _Result()
     _lib.note_hip_use()
     st = lib.gpbo_select_batch_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M, kind,
@@ -221,9 +223,9 @@ def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: fl
                 nan_count=r["nan_count"], info=r["info"])
 
 
-class _GridOnly:
+class _GridOnly(LikelihoodFits):
     """What PointSelector.tune_kernel needs from its surrogate object: the likelihood grid (ard="grid"), the likelihood
-    and its gradient (ard="gradient") or the likelihood over all hyperparameters (ard="hyper")."""
+    and its gradient (ard="gradient") or the likelihood over all hyperparameters (ard="hyper"), and the fits over them."""
 
     def __init__(self, lib):
         self.lib = lib
@@ -234,26 +236,12 @@ class _GridOnly:
     def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL, kernel: str = "se"):
         return nlml_and_grad(X, y, ls, jitter, self.lib, kernel)
 
-    def fit_length_scales(self, X, y, ls0, lower, upper, jitter: float = JITTER_KERNEL, kernel: str = "se", **opts):
-        from .ard_fit import fit_length_scales
-
-        X, y = _f64(X), _f64(y).reshape(-1)
-        return fit_length_scales(lambda ls: self.nlml_and_grad(X, y, ls, jitter, kernel), ls0, lower, upper, **opts)
-
     def nlml_hyper(self, X, y, ls, noise, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se"):
         return nlml_hyper(X, y, ls, noise, fit_mean, fit_scale, self.lib, kernel)
 
-    def fit_hyperparameters(self, X, y, ls0, ls_lower, ls_upper, noise0: float = 1e-2, noise_lower: float = 1e-6,
-                            noise_upper: float = 1.0, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se",
-                            **opts):
-        from .ard_fit import fit_hyperparameters
-
-        X, y = _f64(X), _f64(y).reshape(-1)
-        return fit_hyperparameters(lambda ls, noise: self.nlml_hyper(X, y, ls, noise, fit_mean, fit_scale, kernel), ls0,
-                                   ls_lower, ls_upper, noise0, noise_lower, noise_upper, **opts)
-
-
-_HostFit = _GridOnly   # (the likelihood side of the host route: grid, gradient fit, hyperparameter fit)
+    @contextmanager
+    def _fit_session(self, X, y):
+        yield _f64(X), _f64(y).reshape(-1)   # made contiguous once for all evaluations
 
 
 class PointSelectorHost(PointSelector):
@@ -269,8 +257,7 @@ class PointSelectorHost(PointSelector):
         self._inputs = None
 
     def _surrogate_inputs(self):
-        if self._inputs is None:
-            raise RuntimeError("call update_surrogate() first")
+        self._need_update()
         return self._inputs
 
     def _factorised(self, r):
@@ -281,23 +268,25 @@ class PointSelectorHost(PointSelector):
         return r
 
     def _score(self, acquisition, want_cov_meas=False, **kw):
+        """One host call with this update's model; the result dict with mu / sigma / acq / best_val in the units of y."""
         X, y, ls, Xs = self._inputs
-        if self._ard != "hyper":
-            return self._factorised(select_next(X, y, ls, Xs, acquisition=acquisition, dense=True,
-                                                want_cov_meas=want_cov_meas, chunk=self._chunk, lib=self.lib,
-                                                kernel=self._kernel, **kw))
-        # the fitted model: (y - m) / s under K = k(X,X) + rho I, no N == M quirk; in and out in the units of y
-        r = self._factorised(select_next(X, self._to_model(y), ls, Xs, acquisition=acquisition, dense=True,
-                                         want_cov_meas=want_cov_meas, chunk=self._chunk, lib=self.lib, jitter1=self.noise,
-                                         jitter2=0.0, diag_add=0.0, kernel=self._kernel, **self._acq_kw(kw)))
-        r["mu"] = self.y_mean + self.y_scale * r["mu"]
-        r["sigma"] = self.y_scale * r["sigma"]
-        r["acq"] = self._acq_to_y(acquisition, r["acq"])
-        r["best_val"] = float(self._acq_to_y(acquisition, r["best_val"]))
+        m = self._model
+        r = self._factorised(select_next(X, m.to_model(y), ls, Xs, acquisition=acquisition, dense=True,
+                                         want_cov_meas=want_cov_meas, chunk=self._chunk, lib=self.lib, jitter1=m.jitter1,
+                                         jitter2=m.jitter2, diag_add=m.diag_add(Xs.shape, X.shape), kernel=m.kernel,
+                                         **m.acq_kw(kw)))
+        r.update(mu=m.mean_to_y(r["mu"]), sigma=m.sd_to_y(r["sigma"]), acq=m.acq_to_y(acquisition, r["acq"]),
+                 best_val=float(m.acq_to_y(acquisition, r["best_val"])))
         return r
 
+    def _score_acq(self, kind, **kw):
+        r = self._score(kind, **kw)
+        return r["acq"], (r["best_val"], r["best_idx"], r["nan_count"])
+
+    _NEGATIVE_INDEX_IS_NAN = True
+
     def _not_in_hyper_mode(self, what: str):
-        self._need_se_kernel(what)
+        need_se(self._kernel, what)
         if self._ard == "hyper":
             raise ValueError(f"PointSelectorHost(ard='hyper') supports update_surrogate(), lower_confidence_bound() and "
                              f"expected_improvement(); {what} needs PointSelector")
@@ -307,34 +296,13 @@ class PointSelectorHost(PointSelector):
 
     def update_surrogate(self):
         """point_selector.py:42-102."""
-        self.measured_pts = np.array(self.measured_pts)
-        self.measured_vals = np.array(self.measured_vals)
-        X = np.asarray(self.measured_pts, dtype=np.float64)
-        y = np.asarray(self.measured_vals, dtype=np.float64)
-        Xs = np.asarray(self.predicted_pts, dtype=np.float64)
-        ls = self._select_kernel_params(X)
+        X, y, Xs, ls = self._begin_update()
         self._inputs = (X, y, ls, Xs)
         r = self._score("lcb", want_cov_meas=True, explore=4.0)
-        fd = [int(v) for v in self.feature_domain]
         self.cov_meas = r["cov_meas"]
-        self.mean_func = r["mu"].reshape(fd)                              # :97
-        self.cov_func = r["sigma"].reshape(fd)                            # :98 (a standard deviation)
-        self._cached = {("lcb", 4.0, 0.0): (r["acq"].reshape(fd), (r["best_val"], r["best_idx"], r["nan_count"]))}
         self.cov_pred = self.cov_meas_pred = None                         # not materialised on this route
         self.last_update = "factorise"
-        self.measured_pts = self.measured_pts.tolist()                    # :101-102
-        self.measured_vals = self.measured_vals.tolist()
-
-    def _finish(self, key, kind, **kw):
-        fd = [int(v) for v in self.feature_domain]
-        if key not in self._cached:   # another acquisition on the same data: one more pass through the kernels
-            r = self._score(kind, **kw)
-            self._cached[key] = (r["acq"].reshape(fd), (r["best_val"], r["best_idx"], r["nan_count"]))
-        acq, (best_val, best_idx, nan_count) = self._cached[key]
-        self.acq_func_eval = acq
-        if nan_count > 0 or best_idx >= int(np.prod(fd)) or best_idx < 0:
-            raise IndexError(NAN_ACQUISITION)
-        return np.array(np.unravel_index(best_idx, fd), dtype=np.int64)
+        self._publish(r["mu"], r["sigma"], r["acq"], (r["best_val"], r["best_idx"], r["nan_count"]))
 
     def q_expected_improvement(self, n_samples=512, seed=7, xi=0.0):
         """q = 8 Monte-Carlo Expected Improvement on the host-pointer route (same definition and return value as

@@ -34,6 +34,11 @@ Differences from the reference, all deliberate:
     search; INTEGRATION.md "ARD fit modes"), and `ard="hyper"` (fit noise, signal variance and a constant mean together with
     the length scales; every attribute and acquisition value is then in the units of `measured_vals`: INTEGRATION.md
     "Fitting the whole model").
+Layout: what the surrogate IS besides its length scales (covariance family, diagonal terms, the units of y) is one record,
+model.SurrogateModel, built once per update_surrogate() and read by every later call; what `length_scales` spans is one
+model.LengthScaleSpace, which _select_kernel_params / tune_kernel / _fit_kernel ask for the middle, the box, the grid and the
+shape of kernel_params.  update_surrogate()'s prologue and epilogue (_begin_update, _publish) and the tail of every
+acquisition call (_finish) are shared with PointSelectorHost, which supplies its own "score this acquisition" (_score_acq).
 There is no CPU implementation behind this class.
 """
 from __future__ import annotations
@@ -41,7 +46,8 @@ from __future__ import annotations
 import numpy as np
 
 from . import distributed as D
-from .gp_device import JITTER_ASSEMBLY, JITTER_KERNEL, NAN_ACQUISITION, PRIOR_VAR, DeviceGP
+from .gp_device import NAN_ACQUISITION, DeviceGP
+from .model import LengthScaleSpace, SurrogateModel, need_se
 
 COV_PRED_MAX_M = 4096          # cov_pred is M x M: 128 MiB at this size
 COV_MEAS_PRED_MAX = 1 << 24    # entries of the (M, N) cross covariance kept for inspection
@@ -128,6 +134,7 @@ class PointSelector:
         from ._lib import kernel_id
         kernel_id(kernel)
         self._kernel = kernel
+        self._model = SurrogateModel(kernel)   # rebuilt by every update_surrogate(): what the surrogate is, besides its length scales
         if kernel != "se":
             if ard == "grid":
                 raise ValueError(f"kernel={kernel!r} with ard='grid': the grid kernels generate squared-exponential entries; use "
@@ -151,7 +158,7 @@ class PointSelector:
         self._dense = bool(dense_outputs)
         self._gp = None
         self._mu_dev = self._sigma_dev = None
-        self._xs_dev = None            # fp64 dense route: this rank's candidates on the device (select_batch reuses them)
+        self._cand = None              # (this rank's candidates on the device, diag_add) of the last update_surrogate()
         self._cached = None  # (kind, p0, p1) -> (acq ndarray, flat index)
         self._preset_kernel_params = False
         self._ls_cells = None          # explicit [G x d] cell list for d > 2 (set_length_scale_cells)
@@ -162,7 +169,6 @@ class PointSelector:
         self._inc = None               # (X, y, ls) of the factorisation held by self._gp
         self.last_update = None        # "factorise" | "append": what the last update_surrogate() did
         self.last_screen = None        # screened precisions: DeviceGP.last_screen of the last acquisition + sigma_abs_tol
-        self._screen_ctx = None        # screened precisions: (candidate shard on the device, diag_add)
 
     # ------------------------------------------------------------------------------------------
     def _cov_get(self, name):
@@ -183,9 +189,9 @@ class PointSelector:
                              lambda self, v: self._cov_set("cov_meas_pred", v),
                              doc="k(X,X*).T (point_selector.py:81); None above COV_MEAS_PRED_MAX entries")
 
-    def _need_se_kernel(self, what: str):
-        if self._kernel != "se":
-            raise ValueError(f"{what} is not available with kernel={self._kernel!r}: it supports kernel='se' only")
+    def _need_update(self):
+        if self._cached is None:
+            raise RuntimeError("call update_surrogate() first")
 
     def _log(self, *a):
         if self._verbose:
@@ -217,107 +223,75 @@ class PointSelector:
         self._preset_kernel_params = True
 
     # ------------------------------------------------------------------------------------------
-    def update_surrogate(self):
-        """point_selector.py:42-102."""
+    def _begin_update(self):
+        """The prologue of update_surrogate() (point_selector.py:42-73): (X, y, X*, length scales) as fp64 arrays, with the
+        length scales chosen and the model record of this update built."""
         self.measured_pts = np.array(self.measured_pts)
         self.measured_vals = np.array(self.measured_vals)
         X = np.asarray(self.measured_pts, dtype=np.float64)
         y = np.asarray(self.measured_vals, dtype=np.float64)
         Xs = np.asarray(self.predicted_pts, dtype=np.float64)
-        if self._gp is None:
-            self._gp = DeviceGP(self._device)
-        gp = self._gp
-
         ls = self._select_kernel_params(X)
+        # ard="hyper": the fitted model, the GP of (y - m) / s with K = k(X,X) + rho I; otherwise the reference's frozen one
+        fit = (self.noise, 0.0, self.y_mean, self.y_scale, True) if self._ard == "hyper" else ()
+        self._model = SurrogateModel(self._kernel, *fit)
+        return X, y, Xs, ls
 
-        hyper = self._ard == "hyper"
-        if hyper:
-            # the fitted model: the GP of (y - m) / s with K = k(X,X) + rho I; the N == M quirk is a reference artefact
-            gp.factorise(X, self._to_model(y), ls, self.noise, 0.0, check=True, order="arrival", kernel=self._kernel)
-            self.last_update = "factorise"
-        else:
-            self._factorise_or_append(gp, X, y, ls)                       # :79, :89 (raises LinAlgError)
-
-        M, N = len(Xs), len(X)
-        # :173 shape-coincidence quirk (of the reference's kernel_rbf: not with a fitted model, not with a Matern kernel)
-        diag_add = JITTER_KERNEL if Xs.shape == X.shape and not hyper and self._kernel == "se" else 0.0
-        world, rank = self._world()
-        lo, hi = D.shard_bounds(M, world, rank)
-        if not self._dense:
-            self.mean_func = self.cov_func = self.acq_func_eval = None
-            self._mu_dev = self._sigma_dev = self._xs_dev = None
-            self._cached = {}
-            self._lo_hi = (lo, hi)
-            self._select_only = (gp._dev(Xs[lo:hi]), diag_add)
-            self._cov = {"cov_pred": None, "cov_meas": None, "cov_meas_pred": None}
-            self._lazy = {"cov_meas": gp.cov_meas_host}
-            self.measured_pts = self.measured_pts.tolist()
-            self.measured_vals = self.measured_vals.tolist()
-            return
-        if self._precision in ("fp32", "i8", "i8c"):   # screened variance product (fp32: BASELINE config 4's mode), fp64 decision
-            score = {"fp32": gp.score_f32, "i8": gp.score_i8, "i8c": gp.score_i8c}[self._precision]
-            self._xs_dev = None
-            self._screen_ctx = (gp._dev(Xs[lo:hi]), diag_add)
-            res = score(self._screen_ctx[0], acquisition="lcb", explore=4.0, dense=True, idx_offset=lo, diag_add=diag_add)
-            self.last_screen = dict(gp.last_screen, sigma_abs_tol=SCREEN_SIGMA_TOL[self._precision])
-        else:
-            self._screen_ctx = None
-            self._xs_dev = gp._dev(Xs[lo:hi])
-            res = gp.score(self._xs_dev, acquisition="lcb", explore=4.0, dense=True, idx_offset=lo, diag_add=diag_add,
-                           prior_var=self._prior_var())
-        self._mu_dev, self._sigma_dev = res.mu, res.sigma                 # (ard="hyper": in model units)
-        best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
-        # sharded: the three dense arrays are gathered on the device (one collective), then copied to the host once
-        mu, sigma, acq = (t.cpu().numpy() for t in D.gather_concat_tensors([res.mu, res.sigma, res.acq], M))
-        if hyper:
-            mu, sigma, acq = self.y_mean + self.y_scale * mu, self.y_scale * sigma, self._acq_to_y("lcb", acq)
-            best = (float(self._acq_to_y("lcb", best[0])),) + tuple(best[1:])
+    def _publish(self, mu, sigma, acq, best):
+        """The epilogue of update_surrogate() (:97-102), everything in the units of y: mean_func, cov_func, the LCB(4) entry
+        of the acquisition cache, and measured_* back as lists."""
         fd = [int(v) for v in self.feature_domain]
         self.mean_func = mu.reshape(fd)                                   # :97
         self.cov_func = sigma.reshape(fd)                                 # :98 (a standard deviation)
         self._cached = {("lcb", 4.0, 0.0): (acq.reshape(fd), best)}
+        self.measured_pts = self.measured_pts.tolist()                    # :101-102
+        self.measured_vals = self.measured_vals.tolist()
+
+    def update_surrogate(self):
+        """point_selector.py:42-102."""
+        X, y, Xs, ls = self._begin_update()
+        model = self._model
+        if self._gp is None:
+            self._gp = DeviceGP(self._device)
+        gp = self._gp
+        self._factorise_or_append(gp, X, model.to_model(y), ls)           # :79, :89 (raises LinAlgError)
+
+        M, N = len(Xs), len(X)
+        diag_add = model.diag_add(Xs.shape, X.shape)                      # :173 shape-coincidence quirk
+        world, rank = self._world()
+        lo, hi = D.shard_bounds(M, world, rank)
         self._lo_hi = (lo, hi)
+        self._cand = (gp._dev(Xs[lo:hi]), diag_add)   # this rank's candidates on the device: every later call scores these
+        self._cov = {"cov_pred": None, "cov_meas": None, "cov_meas_pred": None}
+        self._lazy = {"cov_meas": gp.cov_meas_host}
+        self._mu_dev = self._sigma_dev = None
+        if not self._dense:
+            self.mean_func = self.cov_func = self.acq_func_eval = None
+            self._cached = {}
+            self.measured_pts = self.measured_pts.tolist()
+            self.measured_vals = self.measured_vals.tolist()
+            return
+        if self._precision != "fp64":   # screened variance product (fp32: BASELINE config 4's mode), fp64 decision
+            res = self._score_screened("lcb", explore=4.0)
+        else:
+            res = gp.score(self._cand[0], acquisition="lcb", explore=4.0, dense=True, idx_offset=lo, diag_add=diag_add,
+                           prior_var=model.prior_var)
+        self._mu_dev, self._sigma_dev = res.mu, res.sigma                 # (in the units of the model)
+        best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
+        # sharded: the three dense arrays are gathered on the device (one collective), then copied to the host once
+        mu, sigma, acq = (t.cpu().numpy() for t in D.gather_concat_tensors([res.mu, res.sigma, res.acq], M))
+        self._publish(model.mean_to_y(mu), model.sd_to_y(sigma), model.acq_to_y("lcb", acq), model.best_to_y("lcb", best))
 
         # The three covariance attributes of point_selector.py:38-40 are read by nobody on the reference's call path
         # (select_parameters.py reads mean_func / cov_func / acq_func_eval only): they are copied out of the device
         # on first access instead of on every call (the 2,500 x 2,500 cov_pred copy was 6.4 of 7.9 ms of a C1 step).
-        self._cov = {"cov_pred": None, "cov_meas": None, "cov_meas_pred": None}
-        self._lazy = {"cov_meas": gp.cov_meas_host}
         if M * N <= COV_MEAS_PRED_MAX:
             self._lazy["cov_meas_pred"] = lambda: gp.cov_meas_pred_host(Xs, diag_add)
         if M <= COV_PRED_MAX_M:
-            j1, j2 = (self.noise, 0.0) if hyper else (JITTER_KERNEL, JITTER_ASSEMBLY)
-            self._lazy["cov_pred"] = lambda: gp.kxx_host(Xs, ls, j1, j2)
+            self._lazy["cov_pred"] = lambda: gp.kxx_host(Xs, ls, model.jitter1, model.jitter2)
 
-        self.measured_pts = self.measured_pts.tolist()                    # :101-102
-        self.measured_vals = self.measured_vals.tolist()
-
-    # -- ard="hyper": the units of y <-> the units of the model (the GP of (y - y_mean) / y_scale) -----------------------
-    def _to_model(self, v):
-        return (np.asarray(v, dtype=np.float64) - self.y_mean) / self.y_scale
-
-    def _prior_var(self) -> float:
-        """Diagonal of cov_pred: the reference's (1 + 1e-4) + 1e-6, or 1 + rho of the fitted model (the same meaning: the
-        variance of an OBSERVATION at a point nothing is known about)."""
-        return 1.0 + self.noise if self._ard == "hyper" else PRIOR_VAR
-
-    def _acq_kw(self, kw: dict) -> dict:
-        """Acquisition keywords given in the units of y, as the kernels take them: EI's f_best and xi are standardised."""
-        if self._ard != "hyper":
-            return kw
-        kw = dict(kw)
-        if kw.get("f_best") is not None:
-            kw["f_best"] = float(self._to_model(kw["f_best"]))
-        if "xi" in kw:
-            kw["xi"] = float(kw["xi"]) / self.y_scale
-        return kw
-
-    def _acq_to_y(self, kind, acq):
-        """Acquisition values of the model in the units of y: LCB = s acq - m (explore s sigma - (m + s mu)), EI / qEI = s acq.
-        Both maps increase, so the arg-max and its tie rule are those of the kernels."""
-        if self._ard != "hyper":
-            return acq
-        return self.y_scale * acq - self.y_mean if kind == "lcb" else self.y_scale * acq
+    def _space(self, d: int) -> LengthScaleSpace:
+        return LengthScaleSpace(self.length_scales, self._ls_cells, d)
 
     def _select_kernel_params(self, X) -> np.ndarray:
         """point_selector.py:60-73: preset, ARD grid search (n > 1) or the middle of each length-scale axis."""
@@ -331,16 +305,8 @@ class PointSelector:
             pass
         elif len(X[:, 0]) > 1:                                           # :60
             self.tune_kernel()
-        elif self._ls_cells is not None:                                 # one observation: the middle cell of the list
-            self.kernel_params = np.array(self._ls_cells[len(self._ls_cells) // 2])
-        elif X.shape[1] > 2:                                             # the middle of every axis, as :63-73 does
-            self.kernel_params = np.array([np.asarray(a, dtype=np.float64)[len(a) // 2] for a in self.length_scales])
         else:                                                            # :63-73
-            if len(self.length_scales) == 2:
-                a1, a2 = self.length_scales[0], self.length_scales[1]
-                self.kernel_params = np.array([a1[len(a1) // 2], a2[len(a2) // 2]])
-            else:
-                self.kernel_params = np.array([self.length_scales[len(self.length_scales) // 2]])
+            self.kernel_params = self._space(X.shape[1]).middle()
         return np.asarray(self.kernel_params, dtype=np.float64).reshape(-1)
 
     def _factorise_or_append(self, gp, X, y, ls):
@@ -348,6 +314,7 @@ class PointSelector:
         the old data plus a few rows and the length scales are bit-identical to those of the held factors."""
         import os
 
+        model = self._model
         appended = False
         world, rank = self._world()
         if self._incremental:
@@ -365,7 +332,7 @@ class PointSelector:
                 can_append = (n0 < len(X) <= n0 + MAX_APPEND_ROWS and gp.N == n0 and X0.shape[1:] == X.shape[1:]
                               and gp.n_appended + (len(X) - n0) <= MAX_APPENDED_COLUMNS
                               and ls0.shape == ls.shape and np.array_equal(ls0, ls)
-                              and gp.jitter1 == JITTER_KERNEL and gp.jitter2 == JITTER_ASSEMBLY
+                              and gp.jitter1 == model.jitter1 and gp.jitter2 == model.jitter2
                               and np.array_equal(X[:n0], X0) and np.array_equal(y[:n0], y0)
                               # (a permuted factorisation cannot carry the N == M quirk, which is keyed on the arrival index)
                               and (gp.perm is None or np.shape(self.predicted_pts) != np.shape(X)))
@@ -385,22 +352,18 @@ class PointSelector:
             # factorisation (DeviceGP.score_bound), so those are chosen to cover the region whatever the order of the
             # history; not with the N == M quirk, which is keyed on the arrival index (:173)
             fps = not self._dense and np.shape(self.predicted_pts) != np.shape(X)
-            gp.factorise(X, y, ls, JITTER_KERNEL, JITTER_ASSEMBLY, check=True, order="fps" if fps else "arrival",
-                         kernel=self._kernel)
+            gp.factorise(X, y, ls, model.jitter1, model.jitter2, check=True, order="fps" if fps else "arrival",
+                         kernel=model.kernel)
             if fps and self._shard and self._world()[0] > 1:
                 # the order is part of the factorisation: if the selection fell back to the arrival order on ANY rank, every
                 # rank refactorises in arrival order (identical factors on all shards: the cross-shard tie rule needs them)
                 if not D.all_agree(not gp.order_fell_back()):
-                    gp.factorise(X, y, ls, JITTER_KERNEL, JITTER_ASSEMBLY, check=True, order="arrival")
+                    gp.factorise(X, y, ls, model.jitter1, model.jitter2, check=True, order="arrival", kernel=model.kernel)
         self.last_update = "append" if appended else "factorise"
         if self._incremental:
             self._inc = (X.copy(), y.copy(), ls.copy())
             if self._state_path is not None and rank == 0:   # one writer; DeviceGP.save_state renames atomically
                 gp.save_state(self._state_path)
-
-    @staticmethod
-    def _gather(local: np.ndarray, M: int, world: int) -> np.ndarray:
-        return D.gather_concat(local, M)
 
     def _nlml_cells(self, X, y, cells) -> np.ndarray:
         """The likelihood of every grid cell; with several ranks each evaluates a contiguous block of cells
@@ -424,84 +387,22 @@ class PointSelector:
         if self._ard in ("gradient", "hyper"):
             self._fit_kernel(X, y)
             return
-        if self._ls_cells is not None:
-            # explicit cell list (any d): the reference's likelihood in every cell, first minimum wins
-            if self._ls_cells.shape[1] != X.shape[1]:
-                raise ValueError(f"length-scale cells have {self._ls_cells.shape[1]} columns, the observations {X.shape[1]}")
-            nlogml = self._nlml_cells(X, y, self._ls_cells)
-            self.kernel_params = np.array(self._ls_cells[np.argwhere(nlogml == np.amin(nlogml))[0][0]])
-            self.nlogml = nlogml
-            return
-        if X.shape[1] > 2:
-            # d > 2: `length_scales` holds one search axis per feature.  The full Cartesian grid has prod(G_k) cells, so
-            # the axes are searched one at a time from the middle of every axis (the reference's choice when it cannot
-            # tune, :63-73), first minimum per axis, `ard_sweeps` passes.
-            axes = [np.asarray(a, dtype=np.float64).reshape(-1) for a in self.length_scales]
-            if len(axes) != X.shape[1]:
-                raise ValueError(f"length_scales must hold one axis per feature ({X.shape[1]}), got {len(axes)}")
-            ls = np.array([a[len(a) // 2] for a in axes])
-            grids = [None] * len(axes)
-            for _ in range(int(self.ard_sweeps)):
-                for k, a in enumerate(axes):
-                    cells = np.tile(ls, (len(a), 1))
-                    cells[:, k] = a
-                    g = self._nlml_cells(X, y, cells)
-                    grids[k] = g
-                    ls[k] = a[np.argwhere(g == np.amin(g))[0][0]]
-            self.kernel_params = ls
-            self.nlogml = grids
-            return
-        if len(self.length_scales) == 2:                                  # :122
-            axis1 = np.asarray(self.length_scales[0], dtype=np.float64)
-            axis2 = np.asarray(self.length_scales[1], dtype=np.float64)
-            cells = np.stack(np.meshgrid(axis1, axis2, indexing="ij"), -1).reshape(-1, 2)
-            nlogml = self._nlml_cells(X, y, cells).reshape(len(axis1), len(axis2))
-            min_idx = np.argwhere(nlogml == np.amin(nlogml))[0]           # :141
-            self.kernel_params = np.array([axis1[min_idx[0]], axis2[min_idx[1]]])
-            self.nlogml = nlogml
-            if plot2 is not None:
-                try:
-                    plot2(nlogml, self.kernel_params, self.length_scales, self.name, self.iteration)
-                except Exception:  # noqa: BLE001
-                    pass
-        else:
-            axis = np.asarray(self.length_scales, dtype=np.float64)
-            nlogml = self._nlml_cells(X, y, axis.reshape(-1, 1))
-            min_idx = np.argwhere(nlogml == np.amin(nlogml))[0]           # :159
-            self.kernel_params = np.array([axis[min_idx]])                # shape (1, 1), as at :161
-            self.nlogml = nlogml
-            if plot1 is not None:
-                try:
-                    plot1(nlogml, self.kernel_params, self.length_scales, self.name, self.iteration)
-                except Exception:  # noqa: BLE001
-                    pass
+        space = self._space(X.shape[1])
+        self.kernel_params, self.nlogml = space.search(lambda cells: self._nlml_cells(X, y, cells), int(self.ard_sweeps))
+        plot = {"grid2": plot2, "grid1": plot1}.get(space.kind)          # :146, :163
+        if plot is not None:
+            try:
+                plot(self.nlogml, self.kernel_params, self.length_scales, self.name, self.iteration)
+            except Exception:  # noqa: BLE001
+                pass
 
     def _fit_kernel(self, X, y):
-        """tune_kernel with ard="gradient": the box is each feature's [min, max] of its search axis (of the cell list's
-        column with set_length_scale_cells), the start the middle of every axis - the reference's choice when it does not
-        tune (point_selector.py:63-73) - and the objective always the fp64 log-det likelihood: the reference's
-        log(det K) is -inf beyond N ~ 100 and has no gradient.  kernel_params keeps the shape the grid route gives for
-        that d; hyperparam_obj (point_selector.py:30) receives the accepted likelihood values.  With several ranks every
-        rank fits the same problem with the same deterministic kernels: no collective."""
-        d = X.shape[1]
-        if self._ls_cells is not None:
-            if self._ls_cells.shape[1] != d:
-                raise ValueError(f"length-scale cells have {self._ls_cells.shape[1]} columns, the observations {d}")
-            lower, upper = self._ls_cells.min(axis=0), self._ls_cells.max(axis=0)
-            ls0 = np.array(self._ls_cells[len(self._ls_cells) // 2])
-            shape = (d,)
-        else:
-            if d > 2 or len(self.length_scales) == 2:
-                axes = [np.asarray(a, dtype=np.float64).reshape(-1) for a in self.length_scales]
-                shape = (len(axes),)
-            else:
-                axes = [np.asarray(self.length_scales, dtype=np.float64).reshape(-1)]
-                shape = (1, 1)                                            # np.array([axis[min_idx]]), as at :161
-            if len(axes) != d:
-                raise ValueError(f"length_scales must hold one axis per feature ({d}), got {len(axes)}")
-            lower = np.array([a.min() for a in axes])
-            upper = np.array([a.max() for a in axes])
-            ls0 = np.array([a[len(a) // 2] for a in axes])
+        """tune_kernel with ard="gradient" / "hyper": box, start and the shape of kernel_params from the search space
+        (LengthScaleSpace.box_and_start), the objective always the fp64 log-det likelihood: the reference's log(det K) is
+        -inf beyond N ~ 100 and has no gradient.  hyperparam_obj (point_selector.py:30) receives the accepted likelihood
+        values.  With several ranks every rank fits the same problem with the same deterministic kernels: no collective."""
+        space = self._space(X.shape[1])
+        lower, upper, ls0 = space.box_and_start()
         if self._ard == "hyper":
             # the same box and start for the length scales; the noise-to-signal ratio joins them, mean and scale are profiled
             if np.ptp(y) == 0.0:
@@ -510,7 +411,7 @@ class PointSelector:
             self.noise, self.y_mean, self.y_scale = float(res.noise), float(res.mean), float(res.scale)
         else:
             res = self._gp.fit_length_scales(X, y, ls0, lower, upper, kernel=self._kernel)
-        self.kernel_params = np.asarray(res.ls, dtype=np.float64).reshape(shape)
+        self.kernel_params = space.fitted(res.ls)
         self.hyperparam_obj = [float(v) for v in res.trace]
         self.nlogml = np.asarray(res.trace, dtype=np.float64)
         self.last_fit = res.as_dict()
@@ -519,39 +420,48 @@ class PointSelector:
         self._log(f"ARD fit: {res.reason} after {res.n_iter} steps / {res.n_eval} evaluations, nlml {res.nlml:.12g}")
 
     # ------------------------------------------------------------------------------------------
+    _NEGATIVE_INDEX_IS_NAN = False   # (PointSelectorHost: a negative arg-max index also raises the NaN IndexError)
+
+    def _score_screened(self, kind, **kw):
+        """A screen pass with this acquisition, then the fp64 kernels on every survivor; last_screen says how it went."""
+        score = {"fp32": self._gp.score_f32, "i8": self._gp.score_i8, "i8c": self._gp.score_i8c}[self._precision]
+        res = score(self._cand[0], acquisition=kind, dense=True, idx_offset=self._lo_hi[0], diag_add=self._cand[1], **kw)
+        self.last_screen = dict(self._gp.last_screen, sigma_abs_tol=SCREEN_SIGMA_TOL[self._precision])
+        return res
+
+    def _score_acq(self, kind, **kw):
+        """(acquisition values over all candidates [M] or None, (best value, flat index, NaN count)) of an acquisition that
+        is not in the cache, in the units of y: what each class provides to _finish."""
+        model, lo = self._model, self._lo_hi[0]
+        if not self._dense:
+            res = self._gp.score_bound(self._cand[0], acquisition=kind, idx_offset=lo, diag_add=self._cand[1], **kw)
+            return None, D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
+        if self._precision != "fp64":
+            # screened precision: the stored sigma is the screen's, so the decision for THIS acquisition is made the
+            # way the cached LCB(4) one was
+            res = self._score_screened(kind, **kw)
+        else:
+            res = self._gp.acquisition_on_posterior(self._mu_dev, self._sigma_dev, acquisition=kind, idx_offset=lo,
+                                                    **model.acq_kw(kw))
+        best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
+        M = int(np.prod([int(v) for v in self.feature_domain]))
+        return model.acq_to_y(kind, D.gather_concat_tensors([res.acq], M)[0].cpu().numpy()), model.best_to_y(kind, best)
+
     def _finish(self, key, kind, **kw):
         fd = [int(v) for v in self.feature_domain]
-        if not self._dense:
-            if key not in self._cached:
-                Xd, diag_add = self._select_only
-                res = self._gp.score_bound(Xd, acquisition=kind, idx_offset=self._lo_hi[0], diag_add=diag_add, **kw)
-                self._cached[key] = (None, D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count))
-        elif key not in self._cached:
-            lo, hi = self._lo_hi
-            if self._screen_ctx is not None:
-                # screened precision: the stored sigma is the screen's, so the decision for THIS acquisition is made the
-                # way the cached LCB(4) one was - a screen pass with it, then the fp64 kernels on every survivor
-                score = {"fp32": self._gp.score_f32, "i8": self._gp.score_i8, "i8c": self._gp.score_i8c}[self._precision]
-                Xd, diag_add = self._screen_ctx
-                res = score(Xd, acquisition=kind, dense=True, idx_offset=lo, diag_add=diag_add, **kw)
-                self.last_screen = dict(self._gp.last_screen, sigma_abs_tol=SCREEN_SIGMA_TOL[self._precision])
-            else:
-                res = self._gp.acquisition_on_posterior(self._mu_dev, self._sigma_dev, acquisition=kind,
-                                                        idx_offset=lo, **self._acq_kw(kw))
-            best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
-            acq = self._acq_to_y(kind, D.gather_concat_tensors([res.acq], int(np.prod(fd)))[0].cpu().numpy())
-            self._cached[key] = (acq.reshape(fd), (float(self._acq_to_y(kind, best[0])),) + tuple(best[1:]))
+        if key not in self._cached:   # another acquisition on the same data: one more pass through the kernels
+            acq, best = self._score_acq(kind, **kw)
+            self._cached[key] = (None if acq is None else acq.reshape(fd), best)
         acq, (best_val, best_idx, nan_count) = self._cached[key]
         self.acq_func_eval = acq
-        if nan_count > 0 or best_idx >= int(np.prod(fd)):
+        if nan_count > 0 or best_idx >= int(np.prod(fd)) or (self._NEGATIVE_INDEX_IS_NAN and best_idx < 0):
             # the reference: amax is NaN, the comparison is empty, [0] raises (point_selector.py:207)
             raise IndexError(NAN_ACQUISITION)
         return np.array(np.unravel_index(best_idx, fd), dtype=np.int64)
 
     def lower_confidence_bound(self, explore=4):
         """point_selector.py:197-207: acq = explore*sigma - mu; first row-major arg-max as a multi-index."""
-        if self._cached is None:
-            raise RuntimeError("call update_surrogate() first")
+        self._need_update()
         return self._finish(("lcb", float(explore), 0.0), "lcb", explore=float(explore))
 
     def q_expected_improvement(self, n_samples=512, seed=7, xi=0.0):
@@ -560,9 +470,8 @@ class PointSelector:
         of the first batch with the largest qEI, and leaves the per-batch values in `acq_func_eval` (1-D).
         Fixed base samples: default_rng(seed).standard_normal((n_samples, 8)).  Batches are sharded over the
         ranks like single candidates are."""
-        self._need_se_kernel("q_expected_improvement()")
-        if self._cached is None:
-            raise RuntimeError("call update_surrogate() first")
+        need_se(self._kernel, "q_expected_improvement()")
+        self._need_update()
         fd = [int(v) for v in self.feature_domain]
         M = int(np.prod(fd))
         if M % 8:
@@ -572,11 +481,11 @@ class PointSelector:
         Xs = np.asarray(self.predicted_pts, dtype=np.float64)
         world, rank = self._world()
         blo, bhi = D.shard_bounds(M // 8, world, rank)          # whole batches per rank, contiguous
-        kw = self._acq_kw(dict(f_best=f_best, xi=float(xi)))
+        kw = self._model.acq_kw(dict(f_best=f_best, xi=float(xi)))
         res = self._gp.score_qei(Xs[blo * 8: bhi * 8], Z, kw["f_best"], xi=kw["xi"], dense=True, batch_offset=blo,
-                                 prior_var=self._prior_var())
+                                 prior_var=self._model.prior_var)
         best_val, best_idx, nan_count = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
-        qei = self._acq_to_y("qei", D.gather_concat_tensors([res.acq], M // 8)[0].cpu().numpy())
+        qei = self._model.acq_to_y("qei", D.gather_concat_tensors([res.acq], M // 8)[0].cpu().numpy())
         self.acq_func_eval = qei
         if nan_count > 0 or best_idx >= M // 8:
             raise IndexError(NAN_ACQUISITION)
@@ -609,9 +518,8 @@ class PointSelector:
         acq_func_eval stay as update_surrogate() set them (the selection works on copies of the device posterior).
         Needs precision="fp64", dense_outputs=True and candidates of another shape than the observations (the N == M
         quirk); candidates sharded over more than one rank are OUT OF SCOPE: NotImplementedError."""
-        self._need_se_kernel("select_batch()")
-        if self._cached is None:
-            raise RuntimeError("call update_surrogate() first")
+        need_se(self._kernel, "select_batch()")
+        self._need_update()
         if self._precision != "fp64":
             raise ValueError("select_batch() needs precision='fp64' (a screened sigma cannot seed the updates)")
         if not self._dense:
@@ -620,12 +528,11 @@ class PointSelector:
             raise ValueError("select_batch() does not support candidates of the observations' shape (the N == M quirk)")
         if self._world()[0] > 1:
             raise NotImplementedError("select_batch() with candidates sharded over several ranks is not implemented")
-        kw = self._acq_kw(self._batch_acq(acquisition, explore, xi))
-        if self._ard == "hyper" and lie is not None and np.isfinite(float(lie)):
-            lie = float(self._to_model(lie))   # a fantasy observation is a value of y
+        model = self._model
         # the candidates update_surrogate() left on the device: no second upload of M x d values
-        r = self._gp.select_batch_on_posterior(self._xs_dev, self._mu_dev.clone(), self._sigma_dev.clone(), int(q),
-                                               fantasy=fantasy, lie=lie, prior_var=self._prior_var(), **kw)
+        r = self._gp.select_batch_on_posterior(self._cand[0], self._mu_dev.clone(), self._sigma_dev.clone(), int(q),
+                                               fantasy=fantasy, lie=model.lie_to_model(lie), prior_var=model.prior_var,
+                                               **model.acq_kw(self._batch_acq(acquisition, explore, xi)))
         return self._batch_indices(r.indices, r.nan_count)
 
     def select_thompson(self, q, n_features=2048, seed=0):
@@ -639,16 +546,15 @@ class PointSelector:
         non-finite coordinate; candidates sharded over more than one rank are OUT OF SCOPE: NotImplementedError."""
         from .thompson import select_params
 
-        self._need_se_kernel("select_thompson()")
-        if self._cached is None:
-            raise RuntimeError("call update_surrogate() first")
+        need_se(self._kernel, "select_thompson()")
+        self._need_update()
         Xs = np.asarray(self.predicted_pts, dtype=np.float64)
         Xs = Xs.reshape(len(Xs), -1)
         select_params(q, None, n_features, seed, M=len(Xs), d=Xs.shape[1])   # (refused before any GPU work)
         if self._world()[0] > 1:
             raise NotImplementedError("select_thompson() with candidates sharded over several ranks is not implemented")
-        # the candidates update_surrogate() left on the device where it did: no second upload of M x d values
-        r = self._gp.select_thompson(self._xs_dev if self._xs_dev is not None else Xs, q, n_features=n_features, seed=seed)
+        # the candidates update_surrogate() left on the device: no second upload of M x d values
+        r = self._gp.select_thompson(self._cand[0], q, n_features=n_features, seed=seed)
         return self._batch_indices(r.indices, r.nan_count)
 
     def _refine_inputs(self, n_starts, iters, acquisition, explore, xi):
@@ -659,8 +565,7 @@ class PointSelector:
         top of the order), the screen's values below them; the refinement itself is always fp64."""
         from .gp_device import refine_params
 
-        if self._cached is None:
-            raise RuntimeError("call update_surrogate() first")
+        self._need_update()
         if not self._dense:
             raise ValueError("refine_next() needs dense_outputs=True (its starts come from the dense acquisition)")
         kw = self._batch_acq(acquisition, explore, xi)
@@ -688,9 +593,9 @@ class PointSelector:
         xi).  mean_func / cov_func / acq_func_eval and every other attribute stay as they are; IndexError when the
         acquisition contains NaN.  With sharded candidates every rank refines the same global starts on the replicated
         factorisation (same bits on every rank, no collective)."""
-        self._need_se_kernel("refine_next()")
+        need_se(self._kernel, "refine_next()")
         kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
-        r = self._gp.refine(starts, lo, hi, iters=int(iters), prior_var=self._prior_var(), **self._acq_kw(kw))
+        r = self._gp.refine(starts, lo, hi, iters=int(iters), prior_var=self._model.prior_var, **self._model.acq_kw(kw))
         if r.nan_count > 0 or r.best < 0:
             raise IndexError(NAN_ACQUISITION)
         return r.x[r.best].cpu().numpy().astype(np.float64)
@@ -702,18 +607,15 @@ class PointSelector:
         (DeviceGP.loo).  The standard deviation is that of a NOISY observation at the left-out point (the model's K holds the
         noise), which is what the left-out value is compared with.  With ard="hyper" the residuals of a well-specified model are
         unit normal; the frozen model of the other modes is only calibrated for data that are already standardised."""
-        if self._cached is None:
-            raise RuntimeError("call update_surrogate() first")
-        m, s = (self.y_mean, self.y_scale) if self._ard == "hyper" else (0.0, 1.0)
+        self._need_update()
         mu, var, _ = self._gp.loo(1.0)
-        mean = m + s * mu.cpu().numpy()
-        sd = s * np.sqrt(var.cpu().numpy())
+        mean = self._model.y_mean + self._model.y_scale * mu.cpu().numpy()   # (computed for every model, as it always was)
+        sd = self._model.y_scale * np.sqrt(var.cpu().numpy())
         return mean, sd, (np.asarray(self.measured_vals, dtype=np.float64).reshape(-1) - mean) / sd
 
     def expected_improvement(self, xi=0.0):
         """Not in the reference (docs/README.md:363-365 'future work'): EI for minimisation,
         f_best = min(measured_vals)."""
-        if self._cached is None:
-            raise RuntimeError("call update_surrogate() first")
+        self._need_update()
         f_best = float(np.min(np.asarray(self.measured_vals, dtype=np.float64)))
         return self._finish(("ei", f_best, float(xi)), "ei", f_best=f_best, xi=float(xi))

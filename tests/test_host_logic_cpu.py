@@ -72,6 +72,93 @@ def test_preset_kernel_params_skip_the_search():
     assert ps._gp.calls == 0 and np.array_equal(ls, [0.3, 0.4, 0.5])
 
 
+class _FitRecorder:
+    """Stands in for the surrogate object inside tune_kernel with ard="gradient": records the box and the start it is given
+    and answers with a fit that moved every length scale."""
+
+    def fit_length_scales(self, X, y, ls0, lower, upper, kernel="se"):
+        from bayesian_optimisation_amd.ard_fit import FitResult
+
+        self.ls0, self.lower, self.upper = (np.array(v) for v in (ls0, lower, upper))
+        return FitResult(ls=0.5 * (self.lower + self.upper), nlml=1.0, trace=[2.0, 1.0], n_eval=2, n_iter=1, converged=True,
+                         reason="ftol", pg_norm=0.0)
+
+
+_AXES4 = [np.linspace(0.1 * (k + 1), 2.0 + k, 5) for k in range(4)]
+_CELLS = np.exp(np.random.default_rng(3).uniform(np.log(0.1), np.log(2.0), size=(7, 3)))
+
+
+@pytest.mark.parametrize("d,length_scales,cells,shape", [
+    (1, np.linspace(0.05, 5.0, 9), None, (1, 1)),                          # np.array([axis[min_idx]]), as at :161
+    (2, [np.linspace(0.05, 5.0, 9), np.linspace(0.2, 3.0, 6)], None, (2,)),
+    (4, _AXES4, None, (4,)),
+    (3, None, _CELLS, (3,))], ids=["1d", "2d", "4_axes", "cell_list"])
+def test_fit_takes_box_start_and_shape_from_the_search_space(d, length_scales, cells, shape):
+    ps = PointSelector(ard="gradient")
+    ps._gp = gp = _FitRecorder()
+    ps.measured_pts, ps.measured_vals = np.zeros((5, d)), np.arange(5.0)
+    if cells is None:
+        ps.length_scales = length_scales
+        axes = [np.asarray(length_scales)] if d == 1 else [np.asarray(a) for a in length_scales]
+        lower, upper = [a.min() for a in axes], [a.max() for a in axes]
+        start = [a[len(a) // 2] for a in axes]                           # the middle of every axis (:63-73)
+    else:
+        ps.set_length_scale_cells(cells)
+        lower, upper, start = cells.min(axis=0), cells.max(axis=0), cells[len(cells) // 2]
+    ls = ps._select_kernel_params(np.zeros((5, d)))
+    assert np.array_equal(gp.lower, lower) and np.array_equal(gp.upper, upper) and np.array_equal(gp.ls0, start)
+    assert ps.kernel_params.shape == shape and ps.kernel_params.dtype == np.float64
+    assert ls.shape == (d,) and np.array_equal(ls, 0.5 * (gp.lower + gp.upper))
+    assert ps.hyperparam_obj == [2.0, 1.0] and ps.last_fit["reason"] == "ftol"
+    # one observation: nothing is fitted, the start itself is the answer (shape (d,), also in 1-D)
+    one = PointSelector(ard="gradient")
+    one._gp, one.length_scales, one._ls_cells = None, ps.length_scales, ps._ls_cells
+    assert np.array_equal(one._select_kernel_params(np.zeros((1, d))), start) and one.kernel_params.shape == (d,)
+
+
+class _OracleGrid:
+    """Stands in for the surrogate object inside tune_kernel: the oracle's likelihood of the cells it is asked for."""
+
+    def nlml_grid(self, X, y, cells, jitter=1e-4):
+        from oracle import gp_oracle as O
+
+        return O.nlml_cells(X, y, cells)
+
+
+def test_coordinate_sweep_is_the_oracles_bit_for_bit():
+    from bayesian_optimisation_amd.synthetic import make_problem
+    from oracle import gp_oracle as O
+
+    X, y, _, _ = make_problem(12, 8, 4)
+    want_ls, want_grids = O.coordinate_search(X, y, _AXES4, sweeps=2)
+    ps = PointSelector()
+    ps._gp = _OracleGrid()
+    ps.measured_pts, ps.measured_vals, ps.length_scales, ps.ard_sweeps = X, y, _AXES4, 2
+    ls = ps._select_kernel_params(X)
+    assert ps.kernel_params.shape == (4,) and ps.kernel_params.tobytes() == want_ls.tobytes() == ls.tobytes()
+    assert len(ps.nlogml) == 4
+    for got, want in zip(ps.nlogml, want_grids):
+        assert got.dtype == want.dtype == np.float32 and got.shape == (5,) and got.tobytes() == want.tobytes()
+    assert not np.array_equal(want_ls, [a[len(a) // 2] for a in _AXES4])   # (the search moved off its start)
+
+
+@pytest.mark.parametrize("ard", ["grid", "gradient"])
+def test_search_space_refuses_a_wrong_column_or_axis_count(ard):
+    ps = PointSelector(ard=ard)
+    ps._gp = _GridFromFixture(np.zeros(1))                               # must not be consulted
+    ps.measured_pts, ps.measured_vals = np.zeros((5, 4)), np.arange(5.0)
+    ps.set_length_scale_cells(_CELLS)                                    # 3 columns, 4 features
+    with pytest.raises(ValueError, match="length-scale cells have 3 columns, the observations 4"):
+        ps.tune_kernel()
+    ps = PointSelector(ard=ard)
+    ps._gp = _GridFromFixture(np.zeros(1))
+    ps.measured_pts, ps.measured_vals = np.zeros((5, 5)), np.arange(5.0)
+    ps.length_scales = _AXES4                                            # 4 axes, 5 features
+    with pytest.raises(ValueError, match=r"length_scales must hold one axis per feature \(5\), got 4"):
+        ps.tune_kernel()
+    assert ps._gp.calls == 0
+
+
 def test_host_binding_checks_shapes_before_touching_the_device():
     X, y, Xs = np.zeros((5, 2)), np.zeros(5), np.zeros((7, 2))
     with pytest.raises(ValueError):
