@@ -6,7 +6,8 @@ Importing the package does not load the HIP library; the first use of `PointSele
 from .point_selector import PointSelector  # noqa: F401
 from .gp_device import (BatchResult, DeviceGP, GradResult, RefineResult, ScoreResult, ThompsonPaths,  # noqa: F401
                         ThompsonResult)
+from .ensemble import DeviceEnsemble, EnsembleResult  # noqa: F401
 from .host_binding import PointSelectorHost  # noqa: F401  (NumPy + ctypes only: no PyTorch needed)
 
 __all__ = ["PointSelector", "PointSelectorHost", "DeviceGP", "ScoreResult", "BatchResult", "GradResult", "RefineResult",
-           "ThompsonPaths", "ThompsonResult"]
+           "ThompsonPaths", "ThompsonResult", "DeviceEnsemble", "EnsembleResult"]

@@ -29,6 +29,8 @@ TS_MAX_PATHS = 64
 TS_MAX_FEATURES = 16384
 HYPER_MEAN = 1      # gpbo_nlml_hyper_f64: fit the constant mean
 HYPER_SCALE = 2     # ... and the signal variance
+HYPER_CELLS_MAX_N = 64   # gpbo_nlml_hyper_cells_f64: a cell's rows are the lanes of one wave
+ENSEMBLE_MAX_S = 64      # gpbo_ensemble_acq_f64: models per call
 # covariance families of the gpbo_*_kern_f64 entry points (include/gpbo.h: GPBO_KERNEL_*)
 KERNEL_IDS = {"se": 0, "matern32": 1, "matern52": 2}
 
@@ -156,6 +158,10 @@ SIGNATURES = {
                                                  _i64, _p, _p, _p, _p, _p, _p]),
     "gpbo_nlml_grad_host_kern_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _f64, _p]),
     "gpbo_nlml_hyper_host_kern_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _f64, _i32, _p]),
+    "gpbo_nlml_hyper_cells_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p]),
+    "gpbo_ensemble_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "gpbo_ensemble_acq_f64": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _i32, _p, _i32, _p, _p, _p, _i32, _f64, _f64, _i64, _i64,
+                                        _p, _p, _p, _p, _p, _i64, _p]),
     "gpbo_gemm_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
                                 _i32, _i32, _p]),
 }

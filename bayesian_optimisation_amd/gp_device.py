@@ -1323,6 +1323,77 @@ class DeviceGP(LikelihoodFits):
             out = fb["out_hyper"][: 4 + d].cpu().numpy()   # synchronises
         return float(out[0]), out[1: 2 + d].copy(), float(out[2 + d]), float(out[3 + d])
 
+    # -- the same likelihood at many cells (ard="marginal"; csrc/hyper_wave.hip) ------------------------------------------
+    HYPER_CELLS_KERNELS = ("se", "matern32", "matern52")   # families with instances of the wave-per-cell kernel (all: none spills)
+
+    def hyper_cells_route(self, N: int, kernel: str = "se") -> str:
+        """"wave": one launch of gpbo_nlml_hyper_cells_f64 for all cells (N <= 64, a family with instances); "loop": one
+        nlml_hyper() per cell."""
+        return "wave" if N <= _lib.HYPER_CELLS_MAX_N and kernel in self.HYPER_CELLS_KERNELS else "loop"
+
+    def nlml_hyper_cells_fn(self, X, y, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se", route=None):
+        """cells [G x (d + 1)] -> [G x 3] for one (X, y), uploaded once: what a sampler calls once per step (nlml_hyper_cells
+        describes the values).  route: None (hyper_cells_route), "wave" or "loop"."""
+        torch = self.torch
+        kid = _lib.kernel_id(kernel)
+        Xd = self._dev(X)
+        if Xd.dim() != 2:
+            raise ValueError("X must be (N, d)")
+        N, d = int(Xd.shape[0]), int(Xd.shape[1])
+        if d > _lib.MAX_D:
+            raise ValueError(f"the likelihood of hyperparameter cells supports d <= {_lib.MAX_D}, got {d}")
+        y_h = (y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)).astype(np.float64).reshape(-1)
+        if y_h.size != N:
+            raise ValueError("y must have one value per row of X")
+        route = self.hyper_cells_route(N, kernel) if route is None else route
+        if route not in ("wave", "loop") or (route == "wave" and self.hyper_cells_route(N, kernel) != "wave"):
+            raise ValueError(f"route {route!r} is not available for N = {N}, kernel={kernel!r}")
+        flags = (_lib.HYPER_MEAN if fit_mean else 0) | (_lib.HYPER_SCALE if fit_scale else 0)
+        # the kernel forms the profile from y . Kt^-1 y, 1 . Kt^-1 y and 1 . Kt^-1 1, which cancels like (mean / sd)^2 of the y
+        # it is given: with a fitted mean it gets y - mean(y), and the shift goes back onto m (include/gpbo.h)
+        shift = float(np.mean(y_h)) if fit_mean else 0.0
+        yd = self._dev(y_h - shift) if route == "wave" else self._dev(y_h)
+
+        def cells_ok(cells):
+            c = np.ascontiguousarray(np.asarray(cells, dtype=np.float64))
+            if c.ndim != 2 or c.shape[1] != d + 1 or c.shape[0] < 1:
+                raise ValueError(f"cells must be [G x {d + 1}] rows (ls_1 ... ls_d, rho) with G >= 1")
+            if not (np.all(np.isfinite(c)) and np.all(c[:, :d] > 0.0)):
+                raise ValueError("cells must be finite with positive length scales")
+            return c
+
+        def wave(cells):
+            c = cells_ok(cells)
+            with torch.cuda.device(self.device):
+                cd = torch.from_numpy(c).to(self.device)
+                out = torch.empty((len(c), 3), dtype=torch.float64, device=self.device)
+                st = self.lib.gpbo_nlml_hyper_cells_f64(self._ptr(Xd), self._ptr(yd), N, d, self._ptr(cd), len(c), kid, flags,
+                                                        self._ptr(out), self._stream())
+                _lib.check(st, "gpbo_nlml_hyper_cells_f64")
+                res = out.cpu().numpy()   # synchronises: the one read-back
+            res[:, 1] += shift
+            return res
+
+        def loop(cells):
+            c = cells_ok(cells)
+            res = np.full((len(c), 3), np.nan)
+            for g, row in enumerate(c):
+                if row[d] > 0.0:   # (nlml_hyper refuses a noise that is not positive: such a cell is NaN)
+                    f, _, m, s2 = self.nlml_hyper(Xd, yd, row[:d], row[d], fit_mean, fit_scale, kernel)
+                    res[g] = (f, m, s2)
+            return res
+
+        return wave if route == "wave" else loop
+
+    def nlml_hyper_cells(self, X, y, cells, fit_mean: bool = True, fit_scale: bool = True, kernel: str = "se", route=None):
+        """[G x 3] host array (L, mean, scale^2) - nlml_hyper()'s value, mean and scale^2, no gradient - at every row
+        (ls_1 ... ls_d, rho) of cells [G x (d + 1)].  N <= 64 and a family of HYPER_CELLS_KERNELS: one launch of the
+        wave-per-cell kernel (csrc/hyper_wave.hip) and one read-back; otherwise nlml_hyper() cell by cell - the same values
+        within rounding, one factorisation and one read-back per cell.  A row is NaN in all three entries where nlml_hyper()'s
+        outputs are NaN (matrix not positive definite, scale^2 not positive); the loop also answers NaN for rho <= 0, which the
+        kernel takes as it comes.  d <= 16; the surrogate held by this object is not touched."""
+        return self.nlml_hyper_cells_fn(X, y, fit_mean, fit_scale, kernel, route)(cells)
+
     def loo(self, scale2: float = 1.0):
         """Leave-one-out prediction of every observation from the factorisation held by this object (gpbo_loo_f64: the diagonal
         of K^-1 is the row sums of squares of U, so nothing is refitted): device tensors (mu [N], var [N], kinv_diag [N]) in

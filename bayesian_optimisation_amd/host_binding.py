@@ -249,6 +249,9 @@ class PointSelectorHost(PointSelector):
 
     def __init__(self, verbose: bool = False, chunk: int = 0, likelihood: str = "reference", ard: str = "grid",
                  noise0: float = 1e-2, noise_bounds=(1e-6, 1.0), kernel: str = "se"):
+        if ard == "marginal":
+            raise ValueError("ard='marginal' needs PointSelector, the device class (the ensemble of factorisations does not "
+                             "outlive a host-pointer call)")
         super().__init__(device=None, verbose=verbose, shard_candidates=False, likelihood=likelihood, ard=ard, noise0=noise0,
                          noise_bounds=noise_bounds, kernel=kernel)
         self.lib = _lib.load()

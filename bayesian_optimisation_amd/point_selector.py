@@ -33,7 +33,8 @@ Differences from the reference, all deliberate:
     `ard="gradient"` (fit the length scales by maximising the marginal likelihood with its gradient instead of the grid
     search; INTEGRATION.md "ARD fit modes"), and `ard="hyper"` (fit noise, signal variance and a constant mean together with
     the length scales; every attribute and acquisition value is then in the units of `measured_vals`: INTEGRATION.md
-    "Fitting the whole model").
+    "Fitting the whole model"), and `ard="marginal"` (that fit, then LCB / EI, `mean_func` and `cov_func` integrated over
+    `n_models` samples of the hyperparameter posterior: INTEGRATION.md "Integrating over the hyperparameters").
 Layout: what the surrogate IS besides its length scales (covariance family, diagonal terms, the units of y) is one record,
 model.SurrogateModel, built once per update_surrogate() and read by every later call; what `length_scales` spans is one
 model.LengthScaleSpace, which _select_kernel_params / tune_kernel / _fit_kernel ask for the middle, the box, the grid and the
@@ -71,7 +72,8 @@ def _plot_hooks():
 class PointSelector:
     def __init__(self, device=None, verbose: bool = False, shard_candidates: bool = True, precision: str = "fp64",
                  incremental: bool = False, state_path=None, dense_outputs: bool = True, likelihood: str = "reference",
-                 ard: str = "grid", noise0: float = 1e-2, noise_bounds=(1e-6, 1.0), kernel: str = "se"):
+                 ard: str = "grid", noise0: float = 1e-2, noise_bounds=(1e-6, 1.0), kernel: str = "se", n_models: int = 16,
+                 posterior_sweeps: int = 10, seed: int = 0):
         # attribute protocol of point_selector.py:15-40
         self.feature_domain = None
         self.predicted_pts = None
@@ -112,21 +114,36 @@ class PointSelector:
         # noise0 inside noise_bounds - with the constant mean m and the signal variance s^2 at their closed-form optima
         # (csrc/hyper.hip).  The surrogate is then the GP of (y - m) / s with K = k(X,X) + rho I and prior variance 1 + rho,
         # and everything this class reports is mapped back to the units of y.
-        if ard not in ("grid", "gradient", "hyper"):
-            raise ValueError("ard must be 'grid' (the reference's grid search), 'gradient' (ML-II fit of the length scales) or "
-                             "'hyper' (ML-II fit of length scales, noise, signal variance and mean)")
+        # "marginal" (not in the reference): everything "hyper" does, then the acquisition INTEGRATED over the hyperparameter
+        # posterior (Snoek, Larochelle & Adams 2012): n_models chains of slice sampling in (log ls, log rho), started at the
+        # optimum and run for posterior_sweeps sweeps (hyper_posterior.py, every step one launch of csrc/hyper_wave.hip),
+        # give an equal-weight ensemble of models (ensemble.py, csrc/ensemble.hip); mean_func / cov_func are the mean and the
+        # standard deviation of the mixture of their predictions, LCB / EI the average of theirs.  One seed, one result.
+        if ard not in ("grid", "gradient", "hyper", "marginal"):
+            raise ValueError("ard must be 'grid' (the reference's grid search), 'gradient' (ML-II fit of the length scales), "
+                             "'hyper' (ML-II fit of length scales, noise, signal variance and mean) or 'marginal' (that fit, "
+                             "then the acquisition integrated over samples of the hyperparameter posterior)")
         self._ard = ard
+        self._fits_model = ard in ("hyper", "marginal")   # the surrogate is a fitted model.SurrogateModel, in the units of y
+        from ._lib import ENSEMBLE_MAX_S
+        if int(n_models) != n_models or not 1 <= int(n_models) <= ENSEMBLE_MAX_S:
+            raise ValueError(f"n_models must be an integer in [1, {ENSEMBLE_MAX_S}], got {n_models!r}")
+        if int(posterior_sweeps) != posterior_sweeps or int(posterior_sweeps) < 0:
+            raise ValueError(f"posterior_sweeps must be a non-negative integer, got {posterior_sweeps!r}")
+        self._n_models, self._posterior_sweeps, self._seed = int(n_models), int(posterior_sweeps), int(seed)
+        self.hyper_samples = None      # ard="marginal": the sampled models of the last update_surrogate() (dict)
+        self._ens = None
         nlo, nhi = (float(v) for v in noise_bounds)
         if not (0.0 < nlo <= nhi < np.inf) or not nlo <= float(noise0) <= nhi:
             raise ValueError("noise_bounds must satisfy 0 < lower <= upper < inf and hold noise0")
         self._noise0, self._noise_bounds = float(noise0), (nlo, nhi)
-        if ard == "hyper":
+        if self._fits_model:
             if precision != "fp64":
-                raise ValueError("ard='hyper' needs precision='fp64' (the screens are tuned to the reference's prior variance)")
+                raise ValueError(f"ard={ard!r} needs precision='fp64' (the screens are tuned to the reference's prior variance)")
             if incremental or state_path is not None:
-                raise ValueError("ard='hyper' refits the model at every update: incremental / state_path are not available")
+                raise ValueError(f"ard={ard!r} refits the model at every update: incremental / state_path are not available")
             if not dense_outputs:
-                raise ValueError("ard='hyper' needs dense_outputs=True (the prefix bound assumes the reference's jitters)")
+                raise ValueError(f"ard={ard!r} needs dense_outputs=True (the prefix bound assumes the reference's jitters)")
         # kernel="se" (default): the reference's squared exponential, every code path as it was.  "matern32" / "matern52" (not in
         # the reference, whose docs name them as its first planned improvement): the Matern families on the fp64 path -
         # factorisation, scoring, LCB / EI, loo() and the ML-II fits (ard="gradient" / "hyper", or preset kernel_params);
@@ -138,7 +155,7 @@ class PointSelector:
         if kernel != "se":
             if ard == "grid":
                 raise ValueError(f"kernel={kernel!r} with ard='grid': the grid kernels generate squared-exponential entries; use "
-                                 "ard='gradient' or ard='hyper' (preset kernel_params still skip the search)")
+                                 "ard='gradient', ard='hyper' or ard='marginal' (preset kernel_params still skip the search)")
             if precision != "fp64":
                 raise ValueError(f"kernel={kernel!r} needs precision='fp64', got precision={precision!r} (the screens build "
                                  "squared-exponential entries)")
@@ -233,7 +250,7 @@ class PointSelector:
         Xs = np.asarray(self.predicted_pts, dtype=np.float64)
         ls = self._select_kernel_params(X)
         # ard="hyper": the fitted model, the GP of (y - m) / s with K = k(X,X) + rho I; otherwise the reference's frozen one
-        fit = (self.noise, 0.0, self.y_mean, self.y_scale, True) if self._ard == "hyper" else ()
+        fit = (self.noise, 0.0, self.y_mean, self.y_scale, True) if self._fits_model else ()
         self._model = SurrogateModel(self._kernel, *fit)
         return X, y, Xs, ls
 
@@ -265,6 +282,9 @@ class PointSelector:
         self._cov = {"cov_pred": None, "cov_meas": None, "cov_meas_pred": None}
         self._lazy = {"cov_meas": gp.cov_meas_host}
         self._mu_dev = self._sigma_dev = None
+        if self._ard == "marginal":
+            self._update_marginal(X, y, Xs, ls, lo, hi)
+            return
         if not self._dense:
             self.mean_func = self.cov_func = self.acq_func_eval = None
             self._cached = {}
@@ -285,19 +305,72 @@ class PointSelector:
         # The three covariance attributes of point_selector.py:38-40 are read by nobody on the reference's call path
         # (select_parameters.py reads mean_func / cov_func / acq_func_eval only): they are copied out of the device
         # on first access instead of on every call (the 2,500 x 2,500 cov_pred copy was 6.4 of 7.9 ms of a C1 step).
+        self._lazy_cov_pred(gp, Xs, ls, model, diag_add)
+
+    def _lazy_cov_pred(self, gp, Xs, ls, model, diag_add):
+        M, N = len(Xs), gp.N
         if M * N <= COV_MEAS_PRED_MAX:
             self._lazy["cov_meas_pred"] = lambda: gp.cov_meas_pred_host(Xs, diag_add)
         if M <= COV_PRED_MAX_M:
             self._lazy["cov_pred"] = lambda: gp.kxx_host(Xs, ls, model.jitter1, model.jitter2)
+
+    def _update_marginal(self, X, y, Xs, ls, lo, hi):
+        """update_surrogate() with ard="marginal", behind the ML-II fit and the factorisation of its model (kernel_params,
+        noise, y_mean, y_scale, last_fit, the cov_* attributes and loo() stay that model's): sample the hyperparameter
+        posterior from the optimum, factorise the ensemble, publish the integrated mean_func / cov_func / LCB(4).  With
+        several ranks every rank samples the same chains with the same deterministic kernels (as _fit_kernel): no collective
+        before the arg-max."""
+        from . import hyper_posterior
+        from .ensemble import DeviceEnsemble
+
+        gp, model, d = self._gp, self._model, X.shape[1]
+        S = self._n_models
+        if len(X) < 2:
+            # one observation: nothing to sample from; the single model of the one-observation branch
+            cells = np.concatenate([ls, [self.noise]])[None, :]
+            prof = np.array([[np.nan, self.y_mean, self.y_scale ** 2]])
+            counters = dict(n_batches=0, min_margin=float("inf"), kept=0)
+        else:
+            lower, upper, _ = self._space(d).box_and_start()
+            zlo = np.log(np.concatenate([lower, [self._noise_bounds[0]]]))
+            zhi = np.log(np.concatenate([upper, [self._noise_bounds[1]]]))
+            cells_fn = gp.nlml_hyper_cells_fn(X, y, True, True, self._kernel)
+            z0 = np.tile(np.log(np.concatenate([ls, [self.noise]])), (S, 1))
+            r = hyper_posterior.sample(lambda Z: cells_fn(np.exp(Z))[:, 0], z0, zlo, zhi, self._posterior_sweeps, self._seed)
+            cells = np.exp(r.states)
+            prof = cells_fn(cells)   # (L, m, s^2) of the final states
+            counters = dict(n_batches=r.n_batches + 1, min_margin=r.min_margin, kept=r.kept)
+        n = len(cells)
+        w = np.full(n, 1.0 / n)
+        self.hyper_samples = dict(ls=cells[:, :d].copy(), noise=cells[:, d].copy(), y_mean=prof[:, 1].copy(),
+                                  y_scale=np.sqrt(prof[:, 2]), weight=w, nlml=prof[:, 0].copy(),
+                                  sweeps=self._posterior_sweeps, seed=self._seed, **counters)
+        hs = self.hyper_samples
+        models = [(hs["ls"][s], SurrogateModel(self._kernel, float(hs["noise"][s]), 0.0, float(hs["y_mean"][s]),
+                                               float(hs["y_scale"][s]), True), float(w[s])) for s in range(n)]
+        if self._ens is None:
+            self._ens = DeviceEnsemble(self._device)
+        self._ens.factorise(X, y, models)                                 # (raises LinAlgError naming the model)
+        res = self._ens.score(self._cand[0], acquisition="lcb", explore=4.0, dense=True, idx_offset=lo)
+        best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
+        mean, sd, acq = (t.cpu().numpy() for t in D.gather_concat_tensors([res.mean, res.sd, res.acq], len(Xs)))
+        self._publish(mean, sd, acq, best)                                # (the ensemble reports in the units of y)
+        self._lazy_cov_pred(gp, Xs, ls, model, 0.0)
+
+    def _not_in_marginal_mode(self, what: str):
+        if self._ard == "marginal":
+            raise ValueError(f"{what} is not available with ard='marginal' (it works on one model's posterior): use "
+                             "lower_confidence_bound() / expected_improvement(), or ard='hyper'")
 
     def _space(self, d: int) -> LengthScaleSpace:
         return LengthScaleSpace(self.length_scales, self._ls_cells, d)
 
     def _select_kernel_params(self, X) -> np.ndarray:
         """point_selector.py:60-73: preset, ARD grid search (n > 1) or the middle of each length-scale axis."""
-        if self._ard == "hyper" and self._preset_kernel_params:
-            raise ValueError("ard='hyper' fits the length scales with the rest of the model: set_kernel_params() is not available")
-        if self._ard == "hyper" and len(X[:, 0]) < 2:
+        if self._fits_model and self._preset_kernel_params:
+            raise ValueError(f"ard={self._ard!r} fits the length scales with the rest of the model: set_kernel_params() is not "
+                             "available")
+        if self._fits_model and len(X[:, 0]) < 2:
             # nothing to fit from one observation: the mean is that observation, unit scale, the starting noise
             self.noise, self.y_mean, self.y_scale = self._noise0, float(np.asarray(self.measured_vals, dtype=np.float64)[0]), 1.0
             self.last_fit = None
@@ -384,7 +457,7 @@ class PointSelector:
         plot2, plot1 = _plot_hooks()
         if self._gp is None:
             self._gp = DeviceGP(self._device)
-        if self._ard in ("gradient", "hyper"):
+        if self._ard in ("gradient", "hyper", "marginal"):
             self._fit_kernel(X, y)
             return
         space = self._space(X.shape[1])
@@ -403,7 +476,7 @@ class PointSelector:
         values.  With several ranks every rank fits the same problem with the same deterministic kernels: no collective."""
         space = self._space(X.shape[1])
         lower, upper, ls0 = space.box_and_start()
-        if self._ard == "hyper":
+        if self._fits_model:
             # the same box and start for the length scales; the noise-to-signal ratio joins them, mean and scale are profiled
             if np.ptp(y) == 0.0:
                 raise np.linalg.LinAlgError("the likelihood is not finite: constant measured_vals leave no signal variance to fit")
@@ -415,7 +488,7 @@ class PointSelector:
         self.hyperparam_obj = [float(v) for v in res.trace]
         self.nlogml = np.asarray(res.trace, dtype=np.float64)
         self.last_fit = res.as_dict()
-        if self._ard == "hyper":
+        if self._fits_model:
             self.last_fit.update(y_mean=self.y_mean, y_scale=self.y_scale)
         self._log(f"ARD fit: {res.reason} after {res.n_iter} steps / {res.n_eval} evaluations, nlml {res.nlml:.12g}")
 
@@ -433,6 +506,11 @@ class PointSelector:
         """(acquisition values over all candidates [M] or None, (best value, flat index, NaN count)) of an acquisition that
         is not in the cache, in the units of y: what each class provides to _finish."""
         model, lo = self._model, self._lo_hi[0]
+        if self._ard == "marginal":   # one more pass of the ensemble; its parameters and values are in the units of y
+            res = self._ens.score(self._cand[0], acquisition=kind, dense=True, idx_offset=lo, **kw)
+            best = D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
+            M = int(np.prod([int(v) for v in self.feature_domain]))
+            return D.gather_concat_tensors([res.acq], M)[0].cpu().numpy(), best
         if not self._dense:
             res = self._gp.score_bound(self._cand[0], acquisition=kind, idx_offset=lo, diag_add=self._cand[1], **kw)
             return None, D.allreduce_argmax(res.best_val, res.best_idx, res.nan_count)
@@ -470,6 +548,7 @@ class PointSelector:
         of the first batch with the largest qEI, and leaves the per-batch values in `acq_func_eval` (1-D).
         Fixed base samples: default_rng(seed).standard_normal((n_samples, 8)).  Batches are sharded over the
         ranks like single candidates are."""
+        self._not_in_marginal_mode("q_expected_improvement()")
         need_se(self._kernel, "q_expected_improvement()")
         self._need_update()
         fd = [int(v) for v in self.feature_domain]
@@ -518,6 +597,7 @@ class PointSelector:
         acq_func_eval stay as update_surrogate() set them (the selection works on copies of the device posterior).
         Needs precision="fp64", dense_outputs=True and candidates of another shape than the observations (the N == M
         quirk); candidates sharded over more than one rank are OUT OF SCOPE: NotImplementedError."""
+        self._not_in_marginal_mode("select_batch()")
         need_se(self._kernel, "select_batch()")
         self._need_update()
         if self._precision != "fp64":
@@ -546,6 +626,7 @@ class PointSelector:
         non-finite coordinate; candidates sharded over more than one rank are OUT OF SCOPE: NotImplementedError."""
         from .thompson import select_params
 
+        self._not_in_marginal_mode("select_thompson()")
         need_se(self._kernel, "select_thompson()")
         self._need_update()
         Xs = np.asarray(self.predicted_pts, dtype=np.float64)
@@ -593,6 +674,7 @@ class PointSelector:
         xi).  mean_func / cov_func / acq_func_eval and every other attribute stay as they are; IndexError when the
         acquisition contains NaN.  With sharded candidates every rank refines the same global starts on the replicated
         factorisation (same bits on every rank, no collective)."""
+        self._not_in_marginal_mode("refine_next()")
         need_se(self._kernel, "refine_next()")
         kw, starts, lo, hi = self._refine_inputs(n_starts, iters, acquisition, explore, xi)
         r = self._gp.refine(starts, lo, hi, iters=int(iters), prior_var=self._model.prior_var, **self._model.acq_kw(kw))

@@ -631,6 +631,45 @@ int gpbo_nlml_grad_host_kern_f64(const double *X_host, const double *y_host, int
 int gpbo_nlml_hyper_host_kern_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host,
                                   int32_t kernel, double noise, int32_t flags, double *out_host /* [d + 4] */);
 
+/* ---- The acquisition integrated over the hyperparameter posterior (ard="marginal"; Snoek, Larochelle & Adams 2012; not in the
+ * reference).  Two pieces: the likelihood of gpbo_nlml_hyper_f64 at MANY cells in one launch, which a sampler of exp(-L) drives, and
+ * the scoring of candidates under an ensemble of the sampled models.
+ *
+ * gpbo_nlml_hyper_cells_f64 (csrc/hyper_wave.hip): cells [G x (d + 1)] doubles on the device, row g = (ls_1 ... ls_d, rho);
+ *   out [G x 3] doubles on the device, row g = (L, m, s^2) with the meaning of out[0], out[2 + d], out[3 + d] of
+ *   gpbo_nlml_hyper_f64 at (ls, noise = rho); no gradient.  One wave per cell, the cell's matrix in registers:
+ *   1 <= N <= GPBO_HYPER_CELLS_MAX_N, 1 <= d <= GPBO_MAX_D, 1 <= G <= 2^28, kernel a GPBO_KERNEL_*, flags a combination of
+ *   GPBO_HYPER_MEAN | GPBO_HYPER_SCALE (GPBO_ERR_ARG otherwise, before any launch).  A row is NaN in all three entries when a pivot
+ *   of K0(ls) + rho I is not positive and finite, when 1 . Kt^-1 1 is not or when s^2 is not; the other rows do not see it.
+ *   y: the profile is formed from y . Kt^-1 y, 1 . Kt^-1 y and 1 . Kt^-1 1, which cancels like (mean / sd)^2 of the y passed in:
+ *   with GPBO_HYPER_MEAN pass y - mean(y) and add the shift back to m (L and s^2 do not see it).  Enqueues only; no atomics: two
+ *   launches give the same bits.
+ *
+ * gpbo_ensemble_acq_f64 (csrc/ensemble.hip): S models that share (X, N, d, kernel) score M candidates in one call.
+ *   U [S][Np][Np] and alpha [S][Np]: model s as gpbo_factorise_kern_f64 writes it for ((y - m_s) / s_s, ls_s, jitter1 = rho_s,
+ *   jitter2 = 0);  ls_host [S x d];  model_host [S x 4] = (weight w_s >= 0, prior_var = 1 + rho_s, y_mean m_s, y_scale s_s > 0);
+ *   p0, p1: the acquisition parameters in the units of y (LCB: explore, -; EI: f_best, xi).
+ *   For each model in index order the fp64 pass of gpbo_posterior_acq_kern_f64 writes the model's dense mu, sigma into the
+ *   workspace and one kernel folds them, with mu_y = m_s + s_s mu, sigma_y = s_s sigma and shift = sum_s w_s m_s, into
+ *       acq += w_s acquisition(kind, mu_y, sigma_y, p0, p1),   dm += w_s (mu_y - shift),   dv += w_s (sigma_y^2 + (mu_y - shift)^2)
+ *   after the last model: mean_out = shift + dm, sd_out = sqrt(max(dv - dm^2, 0)), acq_out = acq (each optional, [M]) and the
+ *   first arg-max of acq over the candidates that are not NaN (result->nan_count counts those that are; ties to the lower index).
+ *   Every sum in a fixed order, nothing atomic but that count: the same bits from call to call and for any chunk.
+ *   1 <= S <= GPBO_ENSEMBLE_MAX_S, 1 <= d <= GPBO_MAX_D, Np = gpbo_padded_n(N), chunk as for gpbo_posterior_acq_f64, weights
+ *   finite and >= 0 with a positive sum, y_scale and prior_var positive and finite, U 16-byte aligned (GPBO_ERR_ARG otherwise,
+ *   before any launch);  work: gpbo_ensemble_workspace_bytes(Np, chunk, M) bytes (negative: invalid sizes), 256-byte aligned
+ *   (GPBO_ERR_WORKSPACE).  Enqueues only; info of the factorisations is the caller's to check. */
+#define GPBO_HYPER_CELLS_MAX_N 64
+#define GPBO_ENSEMBLE_MAX_S 64
+int gpbo_nlml_hyper_cells_f64(const double *X, const double *y, int64_t N, int32_t d, const double *cells /* [G x (d + 1)] */,
+                              int64_t G, int32_t kernel, int32_t flags, double *out /* [G x 3] */, void *stream);
+int64_t gpbo_ensemble_workspace_bytes(int64_t Np, int64_t chunk, int64_t M);
+int gpbo_ensemble_acq_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d, int32_t S,
+                          const double *ls_host /* [S x d] */, int32_t kernel, const double *U /* [S][Np][Np] */,
+                          const double *alpha /* [S][Np] */, const double *model_host /* [S x 4] */, int32_t acq_kind, double p0,
+                          double p1, int64_t idx_offset, int64_t chunk, double *mean_out, double *sd_out, double *acq_out,
+                          gpbo_result *result, void *work, int64_t work_bytes, void *stream);
+
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;
  * transB = 0: B is [K x N]; transB = 1: B is [N x K].  lower_only = 1 skips 64x64 tiles strictly above

@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian_optimisation_amd", "csrc")
 UNITS = ["kernel_build", "kstar_mfma", "gemm_f64", "factor", "cholinv", "subset", "update", "sigma_acq", "batch", "refine", "thompson",
          "ard",
-         "ard_wave", "ard_grad", "hyper", "posterior_f32", "rescore", "ozaki"]
+         "ard_wave", "ard_grad", "hyper", "hyper_wave", "ensemble", "posterior_f32", "rescore", "ozaki"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 

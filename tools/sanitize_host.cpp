@@ -187,6 +187,33 @@ int main() {
         EXPECT(gpbo_thompson_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr,
                                       nullptr, nullptr, nullptr, &info_t) == GPBO_ERR_ARG);
     }
+    // the likelihood of many hyperparameter cells and the ensemble pass (tests/test_marginal_abi_cpu.py): the size limits, the
+    // model table read on the host (weights, scales, every model's length scales), the workspace one byte short
+    {
+        EXPECT(gpbo_nlml_hyper_cells_f64(pd, pd, 65, 2, pd, 4, 0, 3, pd, nullptr) == GPBO_ERR_ARG);
+        EXPECT(gpbo_nlml_hyper_cells_f64(pd, pd, 20, 17, pd, 4, 0, 3, pd, nullptr) == GPBO_ERR_ARG);
+        EXPECT(gpbo_nlml_hyper_cells_f64(pd, pd, 20, 2, pd, 0, 0, 3, pd, nullptr) == GPBO_ERR_ARG);
+        EXPECT(gpbo_nlml_hyper_cells_f64(pd, pd, 20, 2, pd, 4, 3, 3, pd, nullptr) == GPBO_ERR_ARG);
+        EXPECT(gpbo_nlml_hyper_cells_f64(pd, pd, 20, 2, pd, 4, 0, 4, pd, nullptr) == GPBO_ERR_ARG);
+        double lss[GPBO_ENSEMBLE_MAX_S * 2], model[GPBO_ENSEMBLE_MAX_S * 4];
+        for (int s = 0; s < GPBO_ENSEMBLE_MAX_S; ++s) {
+            lss[2 * s] = lss[2 * s + 1] = 0.5;
+            model[4 * s] = 1.0 / GPBO_ENSEMBLE_MAX_S, model[4 * s + 1] = 1.01, model[4 * s + 2] = 40.0, model[4 * s + 3] = 7.0;
+        }
+        const int64_t we = gpbo_ensemble_workspace_bytes(128, 512, 1000);
+        auto ens = [&](int32_t S, int32_t d, int64_t wbytes) {
+            return gpbo_ensemble_acq_f64(pd, 1000, pd, 100, 128, d, S, lss, 0, pd, pd, model, 0, 4.0, 0.0, 0, 512, nullptr, nullptr,
+                                         nullptr, reinterpret_cast<gpbo_result *>(p), p, wbytes, nullptr);
+        };
+        EXPECT(we > gpbo_posterior_workspace_bytes(128, 512, 1000) && gpbo_ensemble_workspace_bytes(100, 512, 1000) == -1);
+        EXPECT(ens(0, 2, we) == GPBO_ERR_ARG && ens(GPBO_ENSEMBLE_MAX_S + 1, 2, we) == GPBO_ERR_ARG && ens(4, 17, we) == GPBO_ERR_ARG);
+        EXPECT(ens(GPBO_ENSEMBLE_MAX_S, 2, we - 1) == GPBO_ERR_WORKSPACE);   // (reads all 64 rows of both tables)
+        model[4 * 63] = -0.25;
+        EXPECT(ens(GPBO_ENSEMBLE_MAX_S, 2, we) == GPBO_ERR_ARG && ens(63, 2, we - 1) == GPBO_ERR_WORKSPACE);
+        model[4 * 63] = 0.25;
+        lss[2 * 63 + 1] = 0.0;
+        EXPECT(ens(GPBO_ENSEMBLE_MAX_S, 2, we) == GPBO_ERR_ARG);
+    }
     EXPECT(gpbo_potrf_f64(pd, 100, pd, pi, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_trtri_f64(pd, pd, 100, pd, pd, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_nlml_grid_f64(pd, pd, 177, 2, pd, 4, 1e-4, reinterpret_cast<float *>(p), nullptr) == GPBO_ERR_ARG);
