@@ -148,6 +148,35 @@ def test_a_cell_that_is_not_positive_definite_is_nan_and_its_neighbours_are_unto
     assert np.all(np.isfinite(fixed)) and np.all(fixed[:, 1] == pytest.approx(3.0, rel=1e-12)) and np.all(fixed[:, 2] == 1.0)
 
 
+@pytest.mark.parametrize("d", [1, 3, 16])
+@pytest.mark.parametrize("N", [1, 16, 17, 33, 48, 49, 64])
+def test_without_a_profile_the_cells_kernel_is_the_grid_kernel_up_to_the_order_of_one_sum(N, d):
+    """Both kernels are built on csrc/wave_cell.h.  With flags = 0, the squared exponential and rho = jitter the cells kernel
+    factors the same matrix by the same instructions as the grid kernel in its log-det mode, so every z_c and the log det are
+    the same numbers; the grid kernel then sums the N terms z_c^2 >= 0 in column order and the cells kernel by a butterfly.
+    Each order is within (N - 1) 2^-53 relative of the exact sum and the rest of the value costs a few roundings:
+        |L_cells - L_grid| <= 64 * 2^-52 * (quad + |logdet| + N log 2 pi),   quad, logdet: tests/hyper_ref.py.
+    Both sides of every compiled size (48 / 49: the row index that is no mask, lanes beyond NMAX), padded features, a feature
+    count that is no power of two and the widest one; five cells: a partly filled second workgroup."""
+    rho, log2pi = 1e-4, np.log(2.0 * np.pi)
+    X, y, ls = _problem(N, d)
+    cells = _cells(ls, rho)
+    assert _gp().ARD_KERNEL == "wave" and _gp().hyper_cells_route(N) == "wave"
+    out = _gp().nlml_hyper_cells(X, y, cells, fit_mean=False, fit_scale=False)
+    grid = _gp().nlml_grid(X, y, cells[:, :d], jitter=rho, likelihood="logdet")
+    assert out.shape == (5, 3) and grid.shape == (5,) and grid.dtype == np.float64
+    assert np.all(out[:, 1] == 0.0) and np.all(out[:, 2] == 1.0)
+    worst = 0.0
+    for cell, lc, lg in zip(cells, out[:, 0], grid):
+        p = H.nlml_hyper(X, y, cell[:d], rho, False, False, with_parts=True)
+        quad = float(p["r"] @ p["alpha"])
+        logdet = float(np.linalg.slogdet(H.kernel(X, cell[:d])[0] + rho * np.eye(N))[1])
+        bound = 64 * 2.0 ** -52 * (quad + abs(logdet) + N * log2pi)
+        worst = max(worst, abs(lc - lg) / bound)
+        assert np.isfinite(lc) and np.isfinite(lg) and abs(lc - lg) <= bound, (lc, lg, bound)
+    print(f"N {N} d {d}: largest |L_cells - L_grid| / bound {worst:.3f}")
+
+
 def test_two_launches_give_the_same_bits_and_leave_the_surrogate_alone():
     X, y, ls = _problem(64, 2)
     gp = DeviceGP(device="cuda:0")
