@@ -9,6 +9,7 @@
 //   gpbo_select_qei_host_f64       = the same step with q = 8 Monte-Carlo qEI as the acquisition
 //   gpbo_select_batch_host_f64     = the same step, then q points for parallel evaluation (not in the reference; batch.hip)
 //   gpbo_thompson_host_f64         = the factorisation, then q points as minimisers of posterior sample paths (thompson.hip)
+//   gpbo_nei_host_f64              = the factorisation and its noise-free twin, then noisy expected improvement (nei.hip)
 //   gpbo_refine_host_f64           = the factorisation, then gradient refinement of given starts off the grid (refine.hip)
 //   gpbo_nlml_grid_host_f64        = tune_kernel()'s likelihood grid (float32, the reference's det underflow)
 //   gpbo_nlml_grid_logdet_host_f64 = the same grid in fp64 with log det from the factor
@@ -347,6 +348,66 @@ extern "C" int gpbo_thompson_host_f64(const double *X, const double *y, int64_t 
     bool okc = A.d2h(idx_out, dout, sizeof(int64_t) * S) && A.d2h(val_out, dout + S, sizeof(double) * S) &&
                A.d2h(nan_out, dout + 2 * (int64_t)S, sizeof(int64_t) * S);
     if (f_out) okc = okc && A.d2h(f_out, df, sizeof(double) * S * M);
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+}
+
+// Noisy expected improvement on host arrays: the factorisation, its noise-free twin (jitters (delta, 0)), gpbo_nei_fantasies_f64 and
+// gpbo_posterior_nei_kern_f64 (csrc/nei.hip).
+extern "C" int gpbo_nei_host_f64(const double *X, const double *y, int64_t N, int32_t d, const double *ls, int32_t kernel,
+                                 double jitter1, double jitter2, double delta, const double *Xs, int64_t M, const double *Z,
+                                 const double *E, int32_t S, double xi, int64_t chunk, const double *best_in, double *mu_out,
+                                 double *sigma_out, double *acq_out, double *best_out, gpbo_result *result, int32_t *info) {
+    if (!X || !y || !ls || !Xs || !Z || !E || !result || !info) return GPBO_ERR_ARG;
+    if (N < 1 || M < 1 || d < 1 || d > GPBO_MAX_D || !kernel_ok(kernel, d) || !length_scales_ok(ls, d)) return GPBO_ERR_ARG;
+    const double rho = jitter1 + jitter2;
+    if (!(delta > 0.0) || !(delta <= rho) || !(rho < __builtin_huge_val()) || !(xi - xi == 0.0)) return GPBO_ERR_ARG;
+    if (chunk == 0) chunk = (int64_t)1 << 17;
+    if (!chunk_ok(chunk)) return GPBO_ERR_ARG;
+    chunk = clamp_chunk(chunk, M);
+    Surrogate G(N, d, kernel);
+    const int64_t Np = G.Np;
+    const int64_t wfan = gpbo_nei_fantasies_workspace_bytes(Np, S);
+    const int64_t wnei = gpbo_posterior_nei_workspace_bytes(Np, chunk, M, S);
+    if (wfan < 0 || wnei < 0) return GPBO_ERR_ARG;   // S, M out of range
+
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    double *dXs = A.alloc<double>(M * d);
+    double *dZ = A.alloc<double>((int64_t)S * N), *dE = A.alloc<double>((int64_t)S * N);
+    double *dA = A.alloc<double>((int64_t)S * Np), *dF = A.alloc<double>((int64_t)S * Np), *dbest = A.alloc<double>(S);
+    double *dK0 = A.alloc<double>(Np * Np), *dU0 = A.alloc<double>(Np * Np), *dalpha0 = A.alloc<double>(Np);
+    int32_t *dinfo0 = A.alloc<int32_t>(1);
+    gpbo_result *dres = A.alloc<gpbo_result>(1);
+    double *dmu = mu_out ? A.alloc<double>((int64_t)S * M) : nullptr;
+    double *dsig = sigma_out ? A.alloc<double>(M) : nullptr;
+    double *dacq = acq_out ? A.alloc<double>(M) : nullptr;
+    // one workspace serves the four calls in turn (hipMalloc: 256-byte aligned)
+    int rc = G.stage(A, X, y, G.work_bytes(wfan > wnei ? wfan : wnei));
+    if (rc != GPBO_OK) return rc;
+    if (!A.h2d(dXs, Xs, sizeof(double) * M * d) || !A.h2d(dZ, Z, sizeof(double) * S * N) || !A.h2d(dE, E, sizeof(double) * S * N))
+        return GPBO_ERR_LAUNCH;
+    rc = G.factorise(A, ls, jitter1, jitter2);
+    if (rc != GPBO_OK) return rc;
+    int32_t info0 = 0;
+    rc = gpbo_factorise_kern_f64(G.X, G.y, N, d, ls, kernel, delta, 0.0, Np, dK0, dU0, dalpha0, dinfo0, G.work, G.wfact, A.st());
+    if (rc != GPBO_OK) return rc;
+    if (!A.d2h(info, G.info, sizeof(int32_t)) || !A.d2h(&info0, dinfo0, sizeof(int32_t)) || !A.sync()) return GPBO_ERR_LAUNCH;
+    if (*info == 0) *info = info0;
+    if (*info != 0) {  // not positive definite: nothing to sample from
+        *result = {0.0, -1, 0, 0};
+        return GPBO_OK;
+    }
+    rc = gpbo_nei_fantasies_f64(dK0, dU0, G.U, G.y, N, Np, dZ, dE, sqrt(rho - delta), S, dA, dF, dbest, G.work, wfan, A.st());
+    if (rc != GPBO_OK) return rc;
+    if (best_in && !A.h2d(dbest, best_in, sizeof(double) * S)) return GPBO_ERR_LAUNCH;
+    rc = gpbo_posterior_nei_kern_f64(dXs, M, G.X, N, Np, d, ls, kernel, dU0, dA, dbest, S, 1.0 + delta, xi, 0, chunk, dmu, M, dsig,
+                                     dacq, dres, G.work, wnei, A.st());
+    if (rc != GPBO_OK) return rc;
+    bool okc = A.d2h(result, dres, sizeof(gpbo_result));
+    if (mu_out) okc = okc && A.d2h(mu_out, dmu, sizeof(double) * S * M);
+    if (sigma_out) okc = okc && A.d2h(sigma_out, dsig, sizeof(double) * M);
+    if (acq_out) okc = okc && A.d2h(acq_out, dacq, sizeof(double) * M);
+    if (best_out) okc = okc && A.d2h(best_out, dbest, sizeof(double) * S);
     return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 

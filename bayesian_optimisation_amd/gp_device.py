@@ -132,6 +132,34 @@ class ThompsonResult:
         return int(np.sum(self.nan_counts))
 
 
+@dataclass
+class Fantasies:
+    """What DeviceGP.fantasies returns: S samples of the latent function at the observed points and the noise-free twin they
+    are scored with, as device tensors (include/gpbo.h).  Valid until the next factorise() / append() / load_state_dict() of
+    the surrogate that made them."""
+    A: object                        # fp64 [S x Np]: the weights, mu_s(x) = k(x) . A_s (zero on the padding)
+    F: object                        # fp64 [S x Np]: the fantasy values at the observations (zero on the padding)
+    best: object                     # fp64 [S]: min_{i < N} F_s[i], the incumbent of each fantasy
+    K0d: object                      # fp64 [Np x Np]: the twin's matrix K0 + delta I
+    U0: object                       # fp64 [Np x Np]: the twin's factor, U0 U0^T = K0d^-1
+    n_fantasies: int
+    seed: int
+    delta: float
+    epoch: tuple = ()                # the factorisation they belong to
+
+
+@dataclass
+class NeiResult:
+    """What DeviceGP.score_nei / select_nei return."""
+    best_val: float
+    best_idx: int
+    nan_count: int
+    fantasy_best: object             # fp64 [S] device tensor: the incumbents the expected improvements were measured against
+    acq: Optional[object] = None     # dense=True: torch fp64 device tensors, NEI [M] ...
+    sigma: Optional[object] = None   # ... the twin's standard deviation [M] ...
+    mu: Optional[object] = None      # ... and the S means [S x M]
+
+
 def refine_params(P: int, d: int, iters: int, step0: float) -> tuple:
     """(iters, step0) as the C ABI takes them; refuses what gpbo_refine_f64 refuses (include/gpbo.h)."""
     if not 1 <= int(P) <= _lib.REFINE_MAX_P:
@@ -208,6 +236,7 @@ class DeviceGP(LikelihoodFits):
         # workspaces, kept from call to call and only ever grown (_workspace)
         self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
         self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = self._work_loo = None
+        self._work_nei = None
         self._epoch = 0              # counts factorise() / append() / load_state_dict(): ThompsonPaths belong to one of them
         self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
         self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
@@ -307,8 +336,9 @@ class DeviceGP(LikelihoodFits):
                   check: bool = True, order: str = "arrival", kernel: str = "se"):
         """K = k(X,X) + jitter; K = L L^T; U = L^-T; alpha = K^-1 y   (point_selector.py:79, 89-90).
         kernel: "se" (the reference's squared exponential), "matern32" or "matern52" (include/gpbo.h: GPBO_KERNEL_*; d <= 16,
-        order="arrival").  score() / score_async(), kxx_host(), cov_meas_host(), cov_meas_pred_host(), loo() and
-        acquisition_on_posterior() follow it; everything else of this class raises ValueError for a Matern surrogate.
+        order="arrival").  score() / score_async(), kxx_host(), cov_meas_host(), cov_meas_pred_host(), loo(),
+        acquisition_on_posterior() and fantasies() / score_nei() / select_nei() follow it; everything else of this class raises
+        ValueError for a Matern surrogate.
         order="fps": the observations are factorised in their farthest-point order (gpbo_fps_order_f64: `bound_prefix()`
         members spread over the region the observations occupy, then the others in arrival order) instead of the order in
         which they arrived.  A GP's posterior does not depend on the order of its observations - every scoring call returns
@@ -1026,6 +1056,103 @@ class DeviceGP(LikelihoodFits):
         r = self.thompson_score(self.thompson_paths(n_paths, n_features, seed), Xsd, idx_offset=idx_offset)
         keep = first_distinct(r.indices, q)
         return ThompsonResult(indices=r.indices[keep], values=r.values[keep], nan_counts=r.nan_counts)
+
+    # -- noisy expected improvement: EI averaged over fantasies of the incumbent (csrc/nei.hip) ----------
+    def fantasies(self, n_fantasies: int = 16, seed: int = 0, delta: float = 1e-6) -> Fantasies:
+        """n_fantasies samples of the LATENT function at the observed points from the posterior, and the noise-free twin
+        (a second factorisation of the same X, ls and kernel with jitters (delta, 0)) they are scored with.  The model is
+        latent covariance K0 + delta I plus noise of variance rho - delta, rho = jitter1 + jitter2 of this surrogate.  The
+        draws are nei.nei_draws(N, n_fantasies, seed).  Needs factorise(order="arrival") and d <= 16; every kernel family.
+        ValueError on bad parameters (delta > rho included) before any GPU work; LinAlgError when the twin is not positive
+        definite.  Valid until the next factorise() / append() / load_state_dict()."""
+        from .nei import nei_draws, nei_params
+
+        S, seed, _, delta = nei_params(n_fantasies, seed, 0.0, delta, rho=self.jitter1 + self.jitter2)
+        self._need_unrolled_d("fantasies()")
+        if self.N < 1:
+            raise _lib.GpboError("fantasies() needs a factorised surrogate")
+        if self.perm is not None:
+            raise ValueError("fantasies() needs factorise(order='arrival')")
+        torch = self.torch
+        Z, E = nei_draws(self.N, S, seed)
+        N, Np = self.N, self.Np
+        with torch.cuda.device(self.device):
+            K0d = torch.empty((Np, Np), dtype=torch.float64, device=self.device)
+            U0 = torch.empty((Np, Np), dtype=torch.float64, device=self.device)
+            alpha0 = torch.empty(Np, dtype=torch.float64, device=self.device)
+            info0 = torch.zeros(1, dtype=torch.int32, device=self.device)
+            wbytes = int(self.lib.gpbo_factorise_workspace_bytes(Np))
+            work = self._workspace("_work_fact", wbytes)
+            st = self.lib.gpbo_factorise_kern_f64(self._ptr(self.X), self._ptr(self.y), N, self.d,
+                                                  self.ls_h.ctypes.data_as(C.c_void_p), self._kid(), delta, 0.0, Np,
+                                                  self._ptr(K0d), self._ptr(U0), self._ptr(alpha0), self._ptr(info0),
+                                                  self._ptr(work), wbytes, self._stream())
+            _lib.check(st, "gpbo_factorise_kern_f64")
+            Zd, Ed = self._dev(Z), self._dev(E)
+            A = torch.empty((S, Np), dtype=torch.float64, device=self.device)
+            F = torch.empty((S, Np), dtype=torch.float64, device=self.device)
+            best = torch.empty(S, dtype=torch.float64, device=self.device)
+            need = int(self.lib.gpbo_nei_fantasies_workspace_bytes(Np, S))
+            wn = self._workspace("_work_nei", need)
+            noise_sd = float(np.sqrt(max((self.jitter1 + self.jitter2) - delta, 0.0)))
+            st = self.lib.gpbo_nei_fantasies_f64(self._ptr(K0d), self._ptr(U0), self._ptr(self.U), self._ptr(self.y), N, Np,
+                                                 self._ptr(Zd), self._ptr(Ed), noise_sd, S, self._ptr(A), self._ptr(F),
+                                                 self._ptr(best), self._ptr(wn), need, self._stream())
+            _lib.check(st, "gpbo_nei_fantasies_f64")
+            info = int(info0.item())   # synchronises: Zd and Ed have been consumed
+        if info != 0:
+            raise np.linalg.LinAlgError(f"the noise-free twin (k(X,X) + {delta!r} I) is not positive definite (pivot {info} of "
+                                        f"{N}): raise delta")
+        return Fantasies(A, F, best, K0d, U0, S, seed, delta, (id(self), self._epoch))
+
+    def score_nei(self, fantasies: Fantasies, Xs, xi: float = 0.0, best=None, dense: bool = False,
+                  idx_offset: int = 0, check: bool = True) -> NeiResult:
+        """NEI(x) = mean_s EI(mu_s(x), sigma_0(x); best_s, xi) at the rows of Xs and its first arg-max
+        (gpbo_posterior_nei_kern_f64: the variance pass on the twin, the S means from the pass's K(X*,X) image on the matrix
+        cores).  best: S incumbents to use in the place of the fantasies' minima.  dense=True: also NEI [M], sigma_0 [M] and
+        the means [S x M] on the device.  One read-back (synchronises).  A candidate with a NaN coordinate counts in
+        nan_count and is never chosen; IndexError when no candidate is left (check=False: the caller looks at best_idx itself -
+        a shard of a larger candidate set)."""
+        from .nei import nei_best, nei_params
+
+        if not isinstance(fantasies, Fantasies) or fantasies.epoch != (id(self), self._epoch):
+            raise ValueError("these fantasies do not belong to the surrogate as it is now: call fantasies() again after "
+                             "factorise() / append()")
+        S = fantasies.n_fantasies
+        _, _, xi, _ = nei_params(S, 0, xi)
+        b = nei_best(best, S)
+        torch = self.torch
+        Xsd, M = self._candidates(Xs)
+        with torch.cuda.device(self.device):
+            bd = fantasies.best if b is None else self._dev(b)
+            chunk = self._chunk_for(M)
+            need = int(self.lib.gpbo_posterior_nei_workspace_bytes(self.Np, chunk, M, S))
+            work = self._workspace("_work_nei", need)
+            acq = sigma = mu = None
+            if dense:
+                acq = torch.empty(M, dtype=torch.float64, device=self.device)
+                sigma = torch.empty(M, dtype=torch.float64, device=self.device)
+                mu = torch.empty((S, M), dtype=torch.float64, device=self.device)
+            st = self.lib.gpbo_posterior_nei_kern_f64(
+                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
+                self._kid(), self._ptr(fantasies.U0), self._ptr(fantasies.A), self._ptr(bd), S, 1.0 + fantasies.delta, xi,
+                int(idx_offset), chunk, self._ptr(mu), M, self._ptr(sigma), self._ptr(acq), self._ptr(self._result),
+                self._ptr(work), need, self._stream())
+            _lib.check(st, "gpbo_posterior_nei_kern_f64")
+            v, i, n = self.read_result(self._result)   # synchronises: Xsd has been consumed
+        if check and not int(idx_offset) <= i < int(idx_offset) + M:
+            raise IndexError(NAN_ACQUISITION)
+        return NeiResult(v, i, n, bd, acq, sigma, mu)
+
+    def select_nei(self, Xs, n_fantasies: int = 16, seed: int = 0, xi: float = 0.0, delta: float = 1e-6,
+                   dense: bool = False, idx_offset: int = 0, check: bool = True) -> NeiResult:
+        """fantasies() and score_nei() in one call: the next point by noisy expected improvement."""
+        from .nei import nei_params
+
+        nei_params(n_fantasies, seed, xi, delta, rho=self.jitter1 + self.jitter2)   # (refused before any GPU work)
+        Xsd, _ = self._candidates(Xs)
+        return self.score_nei(self.fantasies(n_fantasies, seed, delta), Xsd, xi=xi, dense=dense, idx_offset=idx_offset,
+                              check=check)
 
     # -- acquisition gradients and off-grid refinement (csrc/refine.hip, DESIGN 4d) -------------------------------
     def _points(self, Xq, what: str):

@@ -200,6 +200,35 @@ def select_thompson(X, y, ls, Xs, q: int, n_paths=None, n_features: int = 2048, 
                 f=f)
 
 
+def select_nei(X, y, ls, Xs, n_fantasies: int = 16, seed: int = 0, xi: float = 0.0, delta: float = 1e-6, best=None,
+               dense: bool = True, dense_means: bool = False, chunk: int = 0, lib=None, jitter1: float = JITTER_KERNEL,
+               jitter2: float = JITTER_ASSEMBLY, kernel: str = "se") -> dict:
+    """Noisy expected improvement on host arrays (gpbo_nei_host_f64: the factorisation, its noise-free twin, the fantasies and
+    the scoring in one call; the draws are nei.nei_draws(N, n_fantasies, seed)).  best: incumbents to use in the place of the
+    fantasies' minima.  Returns dict(best_val, best_idx, nan_count, info, acq [M], sigma [M], mu [S x M] with dense_means=True,
+    fantasy_best [S])."""
+    from .nei import nei_best, nei_draws, nei_params
+
+    kid = _lib.kernel_id(kernel)
+    X, y, ls, Xs, N, d, M = _problem(X, y, ls, Xs)
+    S, seed, xi, delta = nei_params(n_fantasies, seed, xi, delta, rho=float(jitter1) + float(jitter2))
+    b = nei_best(best, S)
+    if d > _lib.MAX_D:
+        raise ValueError(f"noisy expected improvement needs d <= {_lib.MAX_D}, got d = {d}")
+    lib = lib or _lib.load()
+    Z, E = (_f64(a) for a in nei_draws(N, S, seed))
+    acq, sigma = (np.empty(M) if dense else None for _ in range(2))
+    mu = np.empty((S, M)) if dense_means else None
+    fbest = np.empty(S)
+    out = _Result()
+    _lib.note_hip_use()
+    st = lib.gpbo_nei_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(jitter1), float(jitter2), delta, _ptr(Xs), M, _ptr(Z),
+                               _ptr(E), S, xi, int(chunk), _ptr(b), _ptr(mu), _ptr(sigma), _ptr(acq), _ptr(fbest), out.res_ptr,
+                               out.info_ptr)
+    _lib.check(st, "gpbo_nei_host_f64")
+    return dict(out.decode(), acq=acq, sigma=sigma, mu=mu, fantasy_best=fbest)
+
+
 def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
            iters: int = 30, step0: float = 0.1, lib=None) -> dict:
     """Off-grid refinement on host arrays (gpbo_refine_host_f64: factorisation and refinement in one call).  Returns
@@ -344,6 +373,15 @@ class PointSelectorHost(PointSelector):
         X, y, ls, Xs = self._surrogate_inputs()
         r = self._factorised(select_thompson(X, y, ls, Xs, q, n_features=n_features, seed=seed, lib=self.lib))
         return self._batch_indices(r["indices"], int(np.sum(r["nan_counts"])))
+
+    def _nei_scores(self, S, seed, xi, delta):
+        """PointSelector.noisy_expected_improvement on the host-pointer route (gpbo_nei_host_f64): the same fantasies for the
+        same seed, the same values."""
+        X, y, ls, Xs = self._surrogate_inputs()
+        m = self._model
+        r = self._factorised(select_nei(X, m.to_model(y), ls, Xs, S, seed, xi=xi, delta=delta, chunk=self._chunk, lib=self.lib,
+                                        jitter1=m.jitter1, jitter2=m.jitter2, kernel=m.kernel))
+        return r["acq"], (r["best_val"], r["best_idx"], r["nan_count"]), r["fantasy_best"]
 
     def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
         """PointSelector.refine_next on the host-pointer route (gpbo_refine_host_f64): the same d coordinates, the same

@@ -23,7 +23,8 @@ Differences from the reference, all deliberate:
     A caller that plots or post-processes these arrays at the reference's 1e-8 should stay with precision="fp64".
     The screens' tolerance is verified per call on every re-scored candidate and a strided sample, not proven for each
     candidate: the route that is exact by construction is `dense_outputs=False` (the prefix bound).
-    Also extra: `expected_improvement(xi)`,
+    Also extra: `expected_improvement(xi)`, `noisy_expected_improvement()` (EI averaged over samples of the best latent value at
+    the observed points instead of measured against min(measured_vals), the luckiest noise draw: INTEGRATION.md 9),
     `q_expected_improvement()`, `select_thompson(q)` (q points as the minimisers of posterior sample paths), `select_batch(q)` (q points for parallel evaluation: greedy Kriging believer / GP-BUCB /
     constant liar), `refine_next()` (the next point off the grid: the best candidates polished by acquisition gradients), `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
     calls go through the exact prefix bound), `kernel_params` may be preset (then no
@@ -186,6 +187,7 @@ class PointSelector:
         self._inc = None               # (X, y, ls) of the factorisation held by self._gp
         self.last_update = None        # "factorise" | "append": what the last update_surrogate() did
         self.last_screen = None        # screened precisions: DeviceGP.last_screen of the last acquisition + sigma_abs_tol
+        self.fantasy_best = None       # noisy_expected_improvement(): the incumbent of every fantasy [S], in the units of y
 
     # ------------------------------------------------------------------------------------------
     def _cov_get(self, name):
@@ -530,7 +532,7 @@ class PointSelector:
         if key not in self._cached:   # another acquisition on the same data: one more pass through the kernels
             acq, best = self._score_acq(kind, **kw)
             self._cached[key] = (None if acq is None else acq.reshape(fd), best)
-        acq, (best_val, best_idx, nan_count) = self._cached[key]
+        acq, (best_val, best_idx, nan_count) = self._cached[key][:2]
         self.acq_func_eval = acq
         if nan_count > 0 or best_idx >= int(np.prod(fd)) or (self._NEGATIVE_INDEX_IS_NAN and best_idx < 0):
             # the reference: amax is NaN, the comparison is empty, [0] raises (point_selector.py:207)
@@ -701,3 +703,45 @@ class PointSelector:
         self._need_update()
         f_best = float(np.min(np.asarray(self.measured_vals, dtype=np.float64)))
         return self._finish(("ei", f_best, float(xi)), "ei", f_best=f_best, xi=float(xi))
+
+    def _nei_scores(self, S, seed, xi, delta):
+        """(NEI over all candidates [M], (best value, flat index, NaN count), the fantasies' incumbents [S]) in the units of the
+        MODEL: what each class provides to noisy_expected_improvement()."""
+        lo = self._lo_hi[0]
+        r = self._gp.select_nei(self._cand[0], S, seed, xi=xi, delta=delta, dense=True, idx_offset=lo, check=False)
+        best = D.allreduce_argmax(r.best_val, r.best_idx, r.nan_count)
+        M = int(np.prod([int(v) for v in self.feature_domain]))
+        return D.gather_concat_tensors([r.acq], M)[0].cpu().numpy(), best, r.fantasy_best.cpu().numpy()
+
+    def noisy_expected_improvement(self, n_fantasies=16, seed=0, xi=0.0, delta=1e-6):
+        """Not in the reference: noisy expected improvement (Letham, Karrer, Ottoni & Bakshy 2019) for minimisation.  The
+        observations are noisy, so min(measured_vals) - the incumbent of expected_improvement() - is the luckiest noise draw and
+        not the best function value.  Here n_fantasies samples of the latent function at the observed points are drawn from the
+        posterior (DeviceGP.fantasies, DESIGN 4j: latent covariance k + delta, noise rho - delta with rho the model's diagonal
+        term; delta in the units of the model, where the signal variance is 1), a noise-free model is conditioned on each, and
+        the expected improvements - each against its own sample's minimum - are averaged.  Returns the multi-index as
+        expected_improvement() does; acq_func_eval holds the values and fantasy_best [n_fantasies] the incumbents, both in the
+        units of measured_vals.  One seed gives the same fantasies on every rank of a sharded call and in PointSelectorHost.
+        Every model record and kernel= work; candidates of the observations' shape are scored without the N == M quirk.
+        ard="marginal", a screened precision= and dense_outputs=False raise ValueError; IndexError when the acquisition
+        contains NaN."""
+        from .nei import nei_params
+
+        self._not_in_marginal_mode("noisy_expected_improvement()")
+        if self._precision != "fp64":
+            raise ValueError(f"noisy_expected_improvement() needs precision='fp64', got precision={self._precision!r} (the "
+                             "fantasies are conditioned on the fp64 posterior)")
+        if not self._dense:
+            raise ValueError("noisy_expected_improvement() needs dense_outputs=True (dense_outputs=False factorises the "
+                             "observations in another order than the draws)")
+        S, seed, xi, delta = nei_params(n_fantasies, seed, xi, delta)
+        self._need_update()
+        model = self._model
+        nei_params(S, seed, xi, delta, rho=model.jitter1 + model.jitter2)
+        key = ("nei", S, seed, xi, delta)
+        if key not in self._cached:
+            acq, best, fbest = self._nei_scores(S, seed, model.acq_kw(dict(xi=xi))["xi"], delta)
+            fd = [int(v) for v in self.feature_domain]
+            self._cached[key] = (model.acq_to_y("ei", acq).reshape(fd), model.best_to_y("ei", best), model.mean_to_y(fbest))
+        self.fantasy_best = self._cached[key][2]
+        return self._finish(key, "nei")

@@ -670,6 +670,54 @@ int gpbo_ensemble_acq_f64(const double *Xs, int64_t M, const double *X, int64_t 
                           double p1, int64_t idx_offset, int64_t chunk, double *mean_out, double *sd_out, double *acq_out,
                           gpbo_result *result, void *work, int64_t work_bytes, void *stream);
 
+/* ---- Noisy expected improvement: EI averaged over fantasies of the incumbent (csrc/nei.hip; Letham, Karrer, Ottoni &
+ * Bakshy 2019; not in the reference).  Everything in the units of the model.  rho = jitter1 + jitter2 of the factorisation (U,
+ * K~ = K0 + rho I), 0 < delta <= rho the nugget of the noise-free TWIN: a second factorisation of the same X, ls and kernel with
+ * jitters (delta, 0), of which K0d (its Kp = K0 + delta I) and U0 (U0 U0^T = K0d^-1) are used.
+ *
+ * gpbo_nei_fantasies_f64: S samples of the latent function at the observed points from the posterior.  Z, E [S x N] unit normal
+ *   draws (device; column n belongs to row n of the factorised X), noise_sd = sqrt(rho - delta):
+ *     B_s = U0 z_s,  g_s = K0d B_s,  r_s = y - g_s - noise_sd e_s,  A_s = B_s + K~^-1 r_s,  F_s = K0d A_s,  best_s = min_{i < N} F_s[i]
+ *   (cov g = K0d exactly and K0d^-1 g_s = B_s by construction: no solve with the ill-conditioned K0d).  F_s has mean K0d K~^-1 y and
+ *   covariance K0d - K0d K~^-1 K0d; with rho = delta every F_s is y.  A_out, F_out [S x Np] (zero on the padding), best_out [S].
+ *   Five dense products of [64 x Np] with [Np x Np] on the matrix cores; the minimum does not read the padding.
+ * gpbo_posterior_nei_kern_f64: NEI(x) = (1 / S) sum_s EI(mu_s(x), sigma_0(x); best_s, xi) over the M rows of Xs, with
+ *   mu_s(x) = k(x) . A_s and sigma_0 the variance pass of gpbo_posterior_acq_kern_f64 on U0 with prior_var (= 1 + delta), EI as
+ *   GPBO_ACQ_EI; first arg-max, NaN rule and tie rule as every other acquisition (a candidate with a NaN coordinate counts once
+ *   in nan_count and is never chosen).  The means come from the K(X*,X)^T image the pass has built for its variance launch, read
+ *   once, all S of them on the matrix cores: about one EI pass whatever S, and no covariance entry of its own - every
+ *   kernel family.  A [S x Np] and best [S]: device (best need not be the row minima).  mu_out: optional dense [S x ldm],
+ *   ldm >= M; sigma_out, acq_out: optional [M].  The sums run in a fixed order, k ascending in one wave: the same bits from call
+ *   to call, and means that do not depend on the chunk.  sigma_0 comes from one call of the pass per chunk, which chooses the
+ *   column groups of its variance kernel by the candidates of that call: the same bits for any chunk except across the line of
+ *   32,768 candidates per chunk at N > 1,920, where it differs by the rounding of another summation order.
+ * 1 <= S <= GPBO_NEI_MAX_S, 1 <= d <= GPBO_MAX_D, Np = gpbo_padded_n(N), chunk as for gpbo_posterior_acq_f64, ls > 0, prior_var
+ *   positive and finite, xi and noise_sd finite, noise_sd >= 0, K0d / U0 / U 16-byte aligned (GPBO_ERR_ARG otherwise, before any HIP
+ *   call);  work: gpbo_nei_fantasies_workspace_bytes(Np, S) / gpbo_posterior_nei_workspace_bytes(Np, chunk, M, S) bytes (negative:
+ *   invalid sizes), 256-byte aligned (GPBO_ERR_WORKSPACE).  Both calls only enqueue; only the integer NaN counter is atomic.
+ * gpbo_nei_host_f64: both factorisations + fantasies + scoring on host arrays (conventions of gpbo_select_next_host_kern_f64: X,
+ *   y, N, d, ls, kernel, jitter1, jitter2, Xs, M, chunk = 0 for the default);  Z_host, E_host [S x N];  best_in_host: NULL for
+ *   the row minima, or [S] incumbents to use instead;  mu_out_host optional [S x M], sigma_out_host / acq_out_host optional [M],
+ *   best_out_host optional [S] (the incumbents used);  info_host: 0, or the failing pivot of either factorisation - then nothing
+ *   is scored and best_idx = -1.  0 < delta <= jitter1 + jitter2 (GPBO_ERR_ARG). */
+#define GPBO_NEI_MAX_S 64
+int64_t gpbo_nei_fantasies_workspace_bytes(int64_t Np, int32_t S);
+int gpbo_nei_fantasies_f64(const double *K0d, const double *U0, const double *U, const double *y, int64_t N, int64_t Np,
+                           const double *Z /* [S x N] */, const double *E /* [S x N] */, double noise_sd, int32_t S,
+                           double *A_out /* [S x Np], zero on the padding */, double *F_out /* [S x Np] */,
+                           double *best_out /* [S] */, void *work, int64_t work_bytes, void *stream);
+int64_t gpbo_posterior_nei_workspace_bytes(int64_t Np, int64_t chunk, int64_t M, int32_t S);
+int gpbo_posterior_nei_kern_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
+                                const double *ls_host, int32_t kernel, const double *U0, const double *A /* [S x Np] */,
+                                const double *best /* [S], device */, int32_t S, double prior_var, double xi, int64_t idx_offset,
+                                int64_t chunk, double *mu_out /* optional [S x ldm] */, int64_t ldm, double *sigma_out,
+                                double *acq_out, gpbo_result *result, void *work, int64_t work_bytes, void *stream);
+int gpbo_nei_host_f64(const double *X_host, const double *y_host, int64_t N, int32_t d, const double *ls_host, int32_t kernel,
+                      double jitter1, double jitter2, double delta, const double *Xs_host, int64_t M, const double *Z_host,
+                      const double *E_host, int32_t S, double xi, int64_t chunk, const double *best_in_host,
+                      double *mu_out_host, double *sigma_out_host, double *acq_out_host, double *best_out_host,
+                      gpbo_result *result_host, int32_t *info_host);
+
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;
  * transB = 0: B is [K x N]; transB = 1: B is [N x K].  lower_only = 1 skips 64x64 tiles strictly above

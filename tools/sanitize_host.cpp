@@ -187,6 +187,32 @@ int main() {
         EXPECT(gpbo_thompson_host_f64(nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr,
                                       nullptr, nullptr, nullptr, &info_t) == GPBO_ERR_ARG);
     }
+    // noisy expected improvement (tests/test_nei_abi_cpu.py): the ranges of S, d, the chunk, the dense means' leading dimension,
+    // the noise's standard deviation, the workspaces one byte short
+    {
+        gpbo_result res_n;
+        int32_t info_n = 0;
+        auto score = [&](int64_t M, int32_t d, int32_t S, int64_t chunk, double *mu, int64_t ldm, int64_t wbytes) {
+            return gpbo_posterior_nei_kern_f64(pd, M, pd, 100, 128, d, ls, 0, pd, pd, pd, S, 1.000001, 0.0, 0, chunk, mu, ldm, nullptr,
+                                               nullptr, &res_n, p, wbytes, nullptr);
+        };
+        auto fantasies = [&](int64_t N, int64_t Np, int32_t S, double sd, int64_t wbytes) {
+            return gpbo_nei_fantasies_f64(pd, pd, pd, pd, N, Np, pd, pd, sd, S, pd, pd, pd, p, wbytes, nullptr);
+        };
+        const int64_t wn = gpbo_posterior_nei_workspace_bytes(128, 512, 1000, 16), wf = gpbo_nei_fantasies_workspace_bytes(128, 16);
+        EXPECT(wn > 0 && wf > 0 && gpbo_posterior_nei_workspace_bytes(128, 512, 1000, 65) == -1 &&
+               gpbo_posterior_nei_workspace_bytes(128, 500, 1000, 16) == -1 && gpbo_nei_fantasies_workspace_bytes(100, 16) == -1);
+        EXPECT(score(1000, 2, 0, 512, nullptr, 0, wn) == GPBO_ERR_ARG && score(1000, 2, 65, 512, nullptr, 0, wn) == GPBO_ERR_ARG);
+        EXPECT(score(1000, 17, 16, 512, nullptr, 0, wn) == GPBO_ERR_ARG && score(1000, 2, 16, 500, nullptr, 0, wn) == GPBO_ERR_ARG);
+        EXPECT(score(0, 2, 16, 512, nullptr, 0, wn) == GPBO_ERR_ARG && score(1000, 2, 16, 512, pd, 999, wn) == GPBO_ERR_ARG);
+        EXPECT(score(1000, 2, 16, 512, nullptr, 0, wn - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(fantasies(129, 128, 16, 0.3, wf) == GPBO_ERR_ARG && fantasies(100, 128, 65, 0.3, wf) == GPBO_ERR_ARG);
+        EXPECT(fantasies(100, 128, 16, -0.1, wf) == GPBO_ERR_ARG && fantasies(100, 128, 16, 0.0, wf - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(gpbo_nei_host_f64(pd, pd, 100, 2, ls, 0, 0.09, 0.0, 0.1, pd, 1000, pd, pd, 16, 0.0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, &res_n, &info_n) == GPBO_ERR_ARG);   // delta > rho
+        EXPECT(gpbo_nei_host_f64(pd, pd, 100, 2, ls, 0, 0.09, 0.0, 1e-6, pd, 1000, pd, pd, 65, 0.0, 0, nullptr, nullptr, nullptr, nullptr,
+                                 nullptr, &res_n, &info_n) == GPBO_ERR_ARG);
+    }
     // the likelihood of many hyperparameter cells and the ensemble pass (tests/test_marginal_abi_cpu.py): the size limits, the
     // model table read on the host (weights, scales, every model's length scales), the workspace one byte short
     {
