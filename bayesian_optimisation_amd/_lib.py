@@ -172,6 +172,8 @@ SIGNATURES = {
                                     _p, _p, _p, _p, _p]),
     "gpbo_gemm_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
                                 _i32, _i32, _p]),
+    "gpbo_gemm_tri_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
+                                    _i32, _i32, _i32, _i32, _p]),
 }
 
 _lib = None

@@ -1,7 +1,8 @@
 // Strided-batched fp64 GEMM on the gfx950 matrix cores (v_mfma_f64_16x16x4_f64).
 //
-// Serves the factorisation only: the Cholesky panel solve and trailing
-// SYRK/GEMM update, and the block-recursive triangular inverse.  None of this exists in the
+// Serves the factorisation: the Cholesky panel solve and trailing
+// SYRK/GEMM update, and the block-recursive triangular inverse - and the dense products of
+// refine.hip, thompson.hip and nei.hip.  None of this exists in the
 // reference, which calls np.linalg.inv (/root/reference/point_selector.py:89).
 //
 // C_b = alpha * A_b * op(B_b) + beta * C_b, all row-major.
@@ -139,29 +140,33 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(int64_t M, int64_t N, int
 
 }  // namespace
 
-int gpbo_gemm_launch(int transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
-                     int64_t strideA, const double *B, int64_t ldb, int64_t strideB, double beta, double *C,
-                     int64_t ldc, int64_t strideC, int batch, int lower_only, hipStream_t st) {
-    return gpbo_gemm_launch_tri(transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
-                                lower_only, 0, st);
-}
-
-int gpbo_gemm_launch_tri(int transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
-                         int64_t strideA, const double *B, int64_t ldb, int64_t strideB, double beta, double *C,
-                         int64_t ldc, int64_t strideC, int batch, int lower_only, int tri, hipStream_t st) {
+// The one place that checks a call and chooses the tile variant.  tile: 0 = the rule below, 32 or 64 = that variant
+// (gpbo_gemm_tri_f64, for the tests).  Everything the kernel relies on and cannot see is refused here, before a launch:
+//  - 16-byte loads of A and B: aligned bases, even leading dimensions, even batch strides;
+//  - rows that do not overlap: a leading dimension of at least the row length (for C an overlap is a write race);
+//  - C == A only with N == 64, ldc == lda and T = 64: one workgroup then owns a whole 64-row tile of A and reads it
+//    completely before it writes (the in-place panel solve).  With more column tiles, or C == B, one workgroup
+//    overwrites what another still reads.
+static int gemm_launch_checked(int transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
+                               int64_t strideA, const double *B, int64_t ldb, int64_t strideB, double beta, double *C,
+                               int64_t ldc, int64_t strideC, int batch, int lower_only, int tri, int tile, hipStream_t st) {
     if (M <= 0 || N <= 0 || batch <= 0) return GPBO_OK;
     if (tri < 0 || tri > 2 || (tri == 1 && (transB || K != N)) || (tri == 2 && K != M)) return GPBO_ERR_ARG;
     if (!A || !B || !C || M % 64 || N % 64 || K % BK || K <= 0 || (lda & 1) || (ldb & 1)) return GPBO_ERR_ARG;
     if (((uintptr_t)A | (uintptr_t)B) & 15) return GPBO_ERR_ARG;
     if (N / 32 > 65535 || M / 32 > 65535 || batch > 65535) return GPBO_ERR_ARG;
+    if (lda < K || ldb < (transB ? K : N) || ldc < N) return GPBO_ERR_ARG;
+    if (batch > 1 && ((strideA | strideB) & 1)) return GPBO_ERR_ARG;
+    const bool in_place = (const double *)C == A;
+    if ((const double *)C == B || (in_place && (N != 64 || ldc != lda))) return GPBO_ERR_ARG;
+    if ((tile != 0 && tile != 32 && tile != 64) || (tile == 32 && in_place)) return GPBO_ERR_ARG;
     // up to 2048 tiles of 64 x 64 (8 per CU) the 32 x 32 variant wins: four times the workgroups, a quarter of the
     // dependent MFMAs per k tile.  Measured, whole factorisation in ms with the switch at 128 / 512 / 2048 / 8192 tiles:
     // N = 2048: 1.28 / 1.17 / 1.17 / 1.18;  N = 4096: 3.55 / 3.48 / 3.41 / 3.41;  N = 8192: 15.1 / - / 14.7 / 16.1
     int64_t tiles64 = (M / 64) * (N / 64) * batch;
     if (lower_only) tiles64 = (M / 64) * (M / 64 + 1) / 2 * batch;
-    // (not when C aliases an operand: the in-place panel solve relies on one workgroup owning a whole 64-row tile,
-    //  which it reads completely before it writes)
-    const bool small = tiles64 < 2048 && C != A && C != B;
+    // (not in place: see above)
+    const bool small = tile ? tile == 32 : (tiles64 < 2048 && !in_place);
     const int T = small ? 32 : 64;
     dim3 grid((unsigned)(N / T), (unsigned)(M / T), (unsigned)batch);
 #define GPBO_GEMM_LAUNCH(TB, TT)                                                                                        \
@@ -177,10 +182,32 @@ int gpbo_gemm_launch_tri(int transB, int64_t M, int64_t N, int64_t K, double alp
     return GPBO_OK;
 }
 
+int gpbo_gemm_launch(int transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
+                     int64_t strideA, const double *B, int64_t ldb, int64_t strideB, double beta, double *C,
+                     int64_t ldc, int64_t strideC, int batch, int lower_only, hipStream_t st) {
+    return gemm_launch_checked(transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
+                               lower_only, 0, 0, st);
+}
+
+int gpbo_gemm_launch_tri(int transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
+                         int64_t strideA, const double *B, int64_t ldb, int64_t strideB, double beta, double *C,
+                         int64_t ldc, int64_t strideC, int batch, int lower_only, int tri, hipStream_t st) {
+    return gemm_launch_checked(transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
+                               lower_only, tri, 0, st);
+}
+
 extern "C" int gpbo_gemm_f64(int32_t transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A,
                              int64_t lda, int64_t strideA, const double *B, int64_t ldb, int64_t strideB,
                              double beta, double *C, int64_t ldc, int64_t strideC, int32_t batch,
                              int32_t lower_only, void *stream) {
-    return gpbo_gemm_launch(transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
-                            lower_only, gpbo_stream(stream));
+    return gemm_launch_checked(transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
+                               lower_only, 0, 0, gpbo_stream(stream));
+}
+
+extern "C" int gpbo_gemm_tri_f64(int32_t transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A,
+                                 int64_t lda, int64_t strideA, const double *B, int64_t ldb, int64_t strideB,
+                                 double beta, double *C, int64_t ldc, int64_t strideC, int32_t batch,
+                                 int32_t lower_only, int32_t tri, int32_t tile, void *stream) {
+    return gemm_launch_checked(transB, M, N, K, alpha, A, lda, strideA, B, ldb, strideB, beta, C, ldc, strideC, batch,
+                               lower_only, tri, tile, gpbo_stream(stream));
 }

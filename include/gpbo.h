@@ -721,10 +721,30 @@ int gpbo_nei_host_f64(const double *X_host, const double *y_host, int64_t N, int
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;
  * transB = 0: B is [K x N]; transB = 1: B is [N x K].  lower_only = 1 skips 64x64 tiles strictly above
- * the block diagonal (SYRK-style update of a lower triangle). */
+ * the block diagonal (SYRK-style update of a lower triangle).  M, N or batch <= 0 is an empty product: GPBO_OK,
+ * nothing is read.  beta == 0: C is written and never read (it may hold NaN).
+ * The contract, checked on the host (GPBO_ERR_ARG before anything is launched):
+ *  - A and B are 16-byte aligned; lda, ldb are even, and so are strideA, strideB when batch > 1 (16-byte loads);
+ *  - each leading dimension is at least the row length: lda >= K, ldb >= (transB ? K : N), ldc >= N;
+ *  - K > 0; batch <= 65535; M / 32 and N / 32 <= 65535;
+ *  - C may alias A only with N == 64 and ldc == lda (one workgroup then owns a whole 64-row tile, which it
+ *    reads completely before it writes: the in-place panel solve of the factorisation); C may never alias B.
+ *    Operands that overlap in any other way are the caller's error and are not detected. */
 int gpbo_gemm_f64(int32_t transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
                   int64_t strideA, const double *B, int64_t ldb, int64_t strideB, double beta, double *C,
                   int64_t ldc, int64_t strideC, int32_t batch, int32_t lower_only, void *stream);
+
+/* The same product with the two choices the library otherwise makes itself (exported for tests):
+ * tri = 0: dense;  1: B [K x N] is lower triangular (transB = 0, K == N): the k range of a column tile starts at the
+ * tile's first column;  2: A [M x K] is lower triangular (K == M): the k range of a row tile ends at the tile's last
+ * row (the two products of each level of gpbo_trtri_f64; the 64 x 64 blocks of the zero triangle that lie strictly above
+ * the block diagonal are not read).
+ * tile = 0: the library's own rule (32 x 32 tiles below 2048 tiles of 64 x 64, 64 x 64 from there up and in place);
+ * 32 or 64: that variant (32 is refused when C aliases A).  Otherwise the contract of gpbo_gemm_f64. */
+int gpbo_gemm_tri_f64(int32_t transB, int64_t M, int64_t N, int64_t K, double alpha, const double *A, int64_t lda,
+                      int64_t strideA, const double *B, int64_t ldb, int64_t strideB, double beta, double *C,
+                      int64_t ldc, int64_t strideC, int32_t batch, int32_t lower_only, int32_t tri, int32_t tile,
+                      void *stream);
 
 #ifdef __cplusplus
 }

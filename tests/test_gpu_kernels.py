@@ -85,7 +85,8 @@ def test_kxx(env, N, d):
     assert np.array_equal(pad, expect)
 
 
-@pytest.mark.parametrize("n", [128, 256, 384, 640, 1024, 4096, 4288])  # >= 4096: two block columns per trailing update
+# >= 4096: two block columns per trailing update;  192: the second level of the inverse is the ragged pair alone (no full pair)
+@pytest.mark.parametrize("n", [128, 192, 256, 384, 640, 1024, 4096, 4288])
 def test_potrf_trtri_alpha(env, n):
     t, lib = env.torch, env.lib
     A = _spd(n, n)

@@ -1,5 +1,6 @@
 """TFLOP/s of the factorisation's fp64 MFMA GEMM (gpbo_gemm_f64) on the shapes the Cholesky / triangular inverse use.
-M a multiple of 128 takes the 128 x 128 tile, M = 64 (2k+1) the 64 x 64 tile: python tools/bench_gemm.py"""
+The library chooses the tile itself: 32 x 32 below 2048 tiles of 64 x 64 (counted over the lower triangle when lower = 1),
+64 x 64 from there up; the pairs M and M - 64 show that nothing depends on M % 128: python tools/bench_gemm.py"""
 import ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -243,6 +243,21 @@ int main() {
     EXPECT(gpbo_potrf_f64(pd, 100, pd, pi, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_trtri_f64(pd, pd, 100, pd, pd, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_nlml_grid_f64(pd, pd, 177, 2, pd, 4, 1e-4, reinterpret_cast<float *>(p), nullptr) == GPBO_ERR_ARG);
+    // the fp64 GEMM (tests/test_host_gemm_args_cpu.py has every rule): short leading dimensions, an odd batch stride, the
+    // alias rule, an unknown tile; the empty product is fine with no pointers at all
+    {
+        double *pa = pd, *pb = pd + 32, *pc = pd + 64;   // distinct, 16-byte aligned, never dereferenced
+        auto gemm = [&](int64_t N, int64_t lda, int64_t ldc, int64_t sA, const double *A, const double *B, double *Cc, int32_t batch,
+                        int32_t tile) {
+            return gpbo_gemm_tri_f64(1, 64, N, 64, 1.0, A, lda, sA, B, 64, 0, 0.0, Cc, ldc, 64 * ldc, batch, 0, 0, tile, nullptr);
+        };
+        EXPECT(gemm(64, 62, 64, 0, pa, pb, pc, 1, 0) == GPBO_ERR_ARG && gemm(128, 64, 126, 0, pa, pb, pc, 1, 0) == GPBO_ERR_ARG);
+        EXPECT(gemm(64, 64, 64, 4097, pa, pb, pc, 2, 0) == GPBO_ERR_ARG);
+        EXPECT(gemm(64, 64, 64, 0, pa, pb, pb, 1, 0) == GPBO_ERR_ARG && gemm(128, 64, 128, 0, pa, pb, pa, 1, 0) == GPBO_ERR_ARG);
+        EXPECT(gemm(64, 64, 64, 0, pa, pb, pa, 1, 32) == GPBO_ERR_ARG && gemm(64, 64, 64, 0, pa, pb, pc, 1, 16) == GPBO_ERR_ARG);
+        EXPECT(gpbo_gemm_f64(0, 64, 64, 16, 1.0, pa, 14, 0, pb, 64, 0, 0.0, pc, 64, 0, 1, 0, nullptr) == GPBO_ERR_ARG);
+        EXPECT(gpbo_gemm_tri_f64(0, 0, 64, 16, 1.0, nullptr, 0, 0, nullptr, 0, 0, 0.0, nullptr, 0, 0, 1, 0, 0, 0, nullptr) == GPBO_OK);
+    }
     // the fused factorisation: S must be 16-byte aligned (LDS-DMA reads it in 16-byte pieces), ld even and >= 2 Np
     EXPECT(gpbo_cholinv_f64(pd + 1, 512, 256, pi, nullptr, nullptr) == GPBO_ERR_ARG);
     EXPECT(gpbo_cholinv_f64(pd, 511, 256, pi, nullptr, nullptr) == GPBO_ERR_ARG);
