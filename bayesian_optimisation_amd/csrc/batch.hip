@@ -236,27 +236,30 @@ __global__ void batch_record_kernel(gpbo_result *__restrict__ result, int j, int
 }
 
 struct Layout {
-    int64_t rec_off, nan_off, acq_off, part_val_off, part_idx_off, xsc_off, kj_off, tmp_off, beta_off, t_off, total, ldt, nblk;
+    BatchRec *rec;
+    unsigned long long *nan;
+    void *acq;   // gpbo_acq_workspace_bytes() for member 0's arg-max
+    double *part_val;
+    int64_t *part_idx;
+    double *xsc, *kj, *tmp, *beta, *t;
+    int64_t total, ldt, nblk;
+    Layout(void *work, int64_t Np, int64_t M, int32_t q) {
+        Carver c(work);
+        nblk = (M + 511) / 512;
+        ldt = align_up(M, 2);
+        rec = c.take<BatchRec>(1);
+        nan = c.take<unsigned long long>(32);   // 256 bytes
+        acq = c.take_bytes(gpbo_acq_workspace_bytes());
+        part_val = c.take<double>(nblk);
+        part_idx = c.take<int64_t>(nblk);
+        xsc = c.take<double>(Np * GPBO_MAX_D);
+        kj = c.take<double>(Np);
+        tmp = c.take<double>(Np);
+        beta = c.take<double>(Np);
+        t = c.take<double>(ldt * (q > 1 ? q - 1 : 1));
+        total = c.total();
+    }
 };
-
-Layout layout(int64_t Np, int64_t M, int32_t q) {
-    Layout L;
-    L.nblk = (M + 511) / 512;
-    L.ldt = align_up(M, 2);
-    int64_t o = 0;
-    L.rec_off = o;      o += align_up((int64_t)sizeof(BatchRec), 256);
-    L.nan_off = o;      o += 256;
-    L.acq_off = o;      o += align_up(gpbo_acq_workspace_bytes(), 256);
-    L.part_val_off = o; o += align_up(8 * L.nblk, 256);
-    L.part_idx_off = o; o += align_up(8 * L.nblk, 256);
-    L.xsc_off = o;      o += align_up(8 * Np * GPBO_MAX_D, 256);
-    L.kj_off = o;       o += align_up(8 * Np, 256);
-    L.tmp_off = o;      o += align_up(8 * Np, 256);
-    L.beta_off = o;     o += align_up(8 * Np, 256);
-    L.t_off = o;        o += align_up(8 * L.ldt * (q > 1 ? q - 1 : 1), 256);
-    L.total = o;
-    return L;
-}
 
 bool sizes_ok(int64_t Np, int64_t M, int32_t q) {
     return np_ok(Np) && Np <= (1 << 20) && M >= 1 && M <= ((int64_t)1 << 40) && q >= 1 && q <= GPBO_BATCH_MAX_Q && q <= M;
@@ -266,7 +269,7 @@ bool sizes_ok(int64_t Np, int64_t M, int32_t q) {
 
 extern "C" int64_t gpbo_batch_workspace_bytes(int64_t Np, int64_t M, int32_t q) {
     if (!sizes_ok(Np, M, q)) return GPBO_ERR_ARG;
-    return layout(Np, M, q).total;
+    return Layout(nullptr, Np, M, q).total;
 }
 
 extern "C" int gpbo_select_batch_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
@@ -282,51 +285,41 @@ extern "C" int gpbo_select_batch_f64(const double *Xs, int64_t M, const double *
     if (fantasy != GPBO_FANTASY_BELIEVER && fantasy != GPBO_FANTASY_LIE) return GPBO_ERR_ARG;
     if (fantasy == GPBO_FANTASY_LIE && !std::isfinite(lie)) return GPBO_ERR_ARG;
     if (!std::isfinite(prior_var) || !std::isfinite(jitter1) || !std::isfinite(jitter2)) return GPBO_ERR_ARG;
-    const Layout L = layout(Np, M, q);
+    const Layout L(work, Np, M, q);
     if (work_bytes < L.total || !aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
 
     BatchLs ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.il2[k] = ls.isc[k] = 0.0;
     (void)length_scale_scalings(ls_host, d, ls.il2, ls.isc);   // (cannot refuse: length_scales_ok above has)
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    BatchRec *rec = reinterpret_cast<BatchRec *>(w + L.rec_off);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
-    double *part_val = reinterpret_cast<double *>(w + L.part_val_off);
-    int64_t *part_idx = reinterpret_cast<int64_t *>(w + L.part_idx_off);
-    double *Xsc = reinterpret_cast<double *>(w + L.xsc_off);
-    double *kj = reinterpret_cast<double *>(w + L.kj_off);
-    double *tmp = reinterpret_cast<double *>(w + L.tmp_off);
-    double *beta = reinterpret_cast<double *>(w + L.beta_off);
-    double *T = reinterpret_cast<double *>(w + L.t_off);
     const double kappa_minus_prior = ((1.0 + jitter1) + jitter2) - prior_var;   // 0 for the prior_var the classes pass
 
-    if (hipMemsetAsync(rec, 0, sizeof(BatchRec), st) != hipSuccess || hipMemsetAsync(info, 0, sizeof(int32_t), st) != hipSuccess)
+    if (hipMemsetAsync(L.rec, 0, sizeof(BatchRec), st) != hipSuccess || hipMemsetAsync(info, 0, sizeof(int32_t), st) != hipSuccess)
         return GPBO_ERR_LAUNCH;
     // member 0: the arg-max of the posterior as it came in (the plain pass's own acquisition on the same mu / sigma)
-    int rc = gpbo_acq_argmax_f64(mu, sigma, M, acq_kind, p0, p1, idx_offset, nullptr, result, w + L.acq_off,
+    int rc = gpbo_acq_argmax_f64(mu, sigma, M, acq_kind, p0, p1, idx_offset, nullptr, result, L.acq,
                                  gpbo_acq_workspace_bytes(), stream);
     if (rc != GPBO_OK) return rc;
-    hipLaunchKernelGGL(batch_record_kernel, dim3(1), dim3(1), 0, st, result, 0, idx_offset, rec, idx_out, val_out);
+    hipLaunchKernelGGL(batch_record_kernel, dim3(1), dim3(1), 0, st, result, 0, idx_offset, L.rec, idx_out, val_out);
     GPBO_CHECK_LAUNCH();
     if (q == 1) return GPBO_OK;
-    rc = gpbo_scale_points_launch(X, N, Np, d, ls_host, Xsc, nullptr, stream);
+    rc = gpbo_scale_points_launch(X, N, Np, d, ls_host, L.xsc, nullptr, stream);
     if (rc != GPBO_OK) return rc;
     for (int j = 0; j + 1 < q; ++j) {
         hipLaunchKernelGGL(batch_pivot_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, st, Xs, M, X, (int)N, (int)Np,
-                           (int)d, ls, mu, sigma, T, L.ldt, j, kappa_minus_prior, (int)fantasy, lie, rec, kj, nan_count, info);
+                           (int)d, ls, mu, sigma, L.t, L.ldt, j, kappa_minus_prior, (int)fantasy, lie, L.rec, L.kj, L.nan, info);
         GPBO_CHECK_LAUNCH();
-        rc = gpbo_alpha_f64(U, kj, N, Np, tmp, beta, stream);
+        rc = gpbo_alpha_f64(U, L.kj, N, Np, L.tmp, L.beta, stream);
         if (rc != GPBO_OK) return rc;
-#define CALL(DD)                                                                                                            \
-    hipLaunchKernelGGL(batch_downdate_kernel<DD>, dim3((unsigned)L.nblk), dim3(256), 0, st, Xs, M, Xsc, (int)N, ls, beta, rec, \
-                       j, T, L.ldt, mu, sigma, (int)acq_kind, p0, p1, idx_offset, part_val, part_idx, nan_count)
+#define CALL(DD)                                                                                                                     \
+    hipLaunchKernelGGL(batch_downdate_kernel<DD>, dim3((unsigned)L.nblk), dim3(256), 0, st, Xs, M, L.xsc, (int)N, ls, L.beta, L.rec, \
+                       j, L.t, L.ldt, mu, sigma, (int)acq_kind, p0, p1, idx_offset, L.part_val, L.part_idx, L.nan)
         GPBO_FOR_D(d, CALL)
 #undef CALL
         GPBO_CHECK_LAUNCH();
-        rc = gpbo_launch_argmax_finish(part_val, part_idx, L.nblk, nan_count, result, st);
+        rc = gpbo_launch_argmax_finish(L.part_val, L.part_idx, L.nblk, L.nan, result, st);
         if (rc != GPBO_OK) return rc;
-        hipLaunchKernelGGL(batch_record_kernel, dim3(1), dim3(1), 0, st, result, j + 1, idx_offset, rec, idx_out, val_out);
+        hipLaunchKernelGGL(batch_record_kernel, dim3(1), dim3(1), 0, st, result, j + 1, idx_offset, L.rec, idx_out, val_out);
         GPBO_CHECK_LAUNCH();
     }
     return GPBO_OK;

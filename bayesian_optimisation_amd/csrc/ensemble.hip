@@ -87,20 +87,28 @@ __global__ __launch_bounds__(256) void ensemble_fold_kernel(const double *__rest
     }
 }
 
+static_assert(FOLD_BLOCKS_MAX * 8 % 256 == 0, "the partial records are carved in whole 256-byte granules");
 struct EnsembleLayout {
-    int64_t post, vec, mu_off, sigma_off, acc_off, pval_off, pidx_off, nan_off, res_off, total;
-    EnsembleLayout(int64_t Np, int64_t chunk, int64_t M) {
-        post = align_up(gpbo_posterior_workspace_bytes_split(Np, chunk, M, 1), 256);
-        vec = align_up((int64_t)sizeof(double) * M, 256);
-        int64_t o = post;
-        mu_off = o;     o += vec;
-        sigma_off = o;  o += vec;
-        acc_off = o;    o += 3 * vec;
-        pval_off = o;   o += FOLD_BLOCKS_MAX * 8;
-        pidx_off = o;   o += FOLD_BLOCKS_MAX * 8;
-        nan_off = o;    o += 256;
-        res_off = o;    o += 256;   // the per-model pass's own result record: not reported
-        total = o;
+    void *post_work;   // the workspace of the per-model fp64 pass, post bytes
+    double *mu, *sigma, *acc_acq, *acc_dm, *acc_dv, *pval;
+    int64_t *pidx;
+    unsigned long long *nan;
+    gpbo_result *res;   // the per-model pass's own result record: not reported
+    int64_t post, total;
+    EnsembleLayout(void *work, int64_t Np, int64_t chunk, int64_t M) {
+        Carver c(work);
+        post = gpbo_posterior_workspace_bytes_split(Np, chunk, M, 1);
+        post_work = c.take_bytes(post);
+        mu = c.take<double>(M);
+        sigma = c.take<double>(M);
+        acc_acq = c.take<double>(M);
+        acc_dm = c.take<double>(M);
+        acc_dv = c.take<double>(M);
+        pval = c.take<double>(FOLD_BLOCKS_MAX);
+        pidx = c.take<int64_t>(FOLD_BLOCKS_MAX);
+        nan = c.take<unsigned long long>(32);   // 256 bytes
+        res = static_cast<gpbo_result *>(c.take_bytes(256));
+        total = c.total();
     }
 };
 
@@ -110,7 +118,7 @@ bool positive_finite(double v) { return v > 0.0 && v < __builtin_huge_val(); }
 
 extern "C" int64_t gpbo_ensemble_workspace_bytes(int64_t Np, int64_t chunk, int64_t M) {
     if (gpbo_posterior_workspace_bytes_split(Np, chunk, M, 1) < 0 || M > ((int64_t)1 << 40)) return GPBO_ERR_ARG;
-    return EnsembleLayout(Np, chunk, M).total;
+    return EnsembleLayout(nullptr, Np, chunk, M).total;
 }
 
 extern "C" int gpbo_ensemble_acq_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d, int32_t S,
@@ -135,18 +143,10 @@ extern "C" int gpbo_ensemble_acq_f64(const double *Xs, int64_t M, const double *
     if (!(wsum > 0.0)) return GPBO_ERR_ARG;
     if (!aligned_to(U, 16)) return GPBO_ERR_ARG;
     if (!aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
-    const EnsembleLayout L(Np, chunk, M);
+    const EnsembleLayout L(work, Np, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    auto vec = [&](int64_t off) { return reinterpret_cast<double *>(w + off); };
-    double *mu = vec(L.mu_off), *sigma = vec(L.sigma_off);
-    double *acc_acq = vec(L.acc_off), *acc_dm = vec(L.acc_off + L.vec), *acc_dv = vec(L.acc_off + 2 * L.vec);
-    double *part_val = vec(L.pval_off);
-    int64_t *part_idx = reinterpret_cast<int64_t *>(w + L.pidx_off);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
-    gpbo_result *scratch = reinterpret_cast<gpbo_result *>(w + L.res_off);
-    if (hipMemsetAsync(nan_count, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
+    if (hipMemsetAsync(L.nan, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
     int64_t nblk = (M + 255) / 256;
     if (nblk > FOLD_BLOCKS_MAX) nblk = FOLD_BLOCKS_MAX;
     for (int s = 0; s < S; ++s) {
@@ -154,13 +154,13 @@ extern "C" int gpbo_ensemble_acq_f64(const double *Xs, int64_t M, const double *
         const GpModel gp = {X, N, Np, d, ls_host + (int64_t)s * d, U + (int64_t)s * Np * Np, alpha + (int64_t)s * Np, m[1], kernel};
         // (the pass's own acquisition and arg-max, in model units, are not used: LCB with explore 0 is the cheapest it has)
         int rc = gpbo_posterior_acq_f64_split(Xs, M, gp, {GPBO_ACQ_LCB, 0.0, 0.0}, 0.0, idx_offset, chunk,
-                                              {mu, sigma, nullptr, nullptr}, scratch, work, L.post, nullptr, 1, 0, stream);
+                                              {L.mu, L.sigma, nullptr, nullptr}, L.res, L.post_work, L.post, nullptr, 1, 0, stream);
         if (rc != GPBO_OK) return rc;
         const bool first = s == 0, last = s == S - 1;
-#define GPBO_FOLD_LAUNCH(F, LL)                                                                                                  \
-    hipLaunchKernelGGL((ensemble_fold_kernel<F, LL>), dim3((unsigned)nblk), dim3(256), 0, st, mu, sigma, M, m[0], m[2], m[3], shift, \
-                       (int)acq_kind, p0, p1, acc_acq, acc_dm, acc_dv, idx_offset, mean_out, sd_out, acq_out, part_val, part_idx,  \
-                       nan_count)
+#define GPBO_FOLD_LAUNCH(F, LL)                                                                                                          \
+    hipLaunchKernelGGL((ensemble_fold_kernel<F, LL>), dim3((unsigned)nblk), dim3(256), 0, st, L.mu, L.sigma, M, m[0], m[2], m[3], shift, \
+                       (int)acq_kind, p0, p1, L.acc_acq, L.acc_dm, L.acc_dv, idx_offset, mean_out, sd_out, acq_out, L.pval, L.pidx,      \
+                       L.nan)
         if (first && last) GPBO_FOLD_LAUNCH(true, true);
         else if (first) GPBO_FOLD_LAUNCH(true, false);
         else if (last) GPBO_FOLD_LAUNCH(false, true);
@@ -168,5 +168,5 @@ extern "C" int gpbo_ensemble_acq_f64(const double *Xs, int64_t M, const double *
 #undef GPBO_FOLD_LAUNCH
         GPBO_CHECK_LAUNCH();
     }
-    return gpbo_launch_argmax_finish(part_val, part_idx, nblk, nan_count, result, st);
+    return gpbo_launch_argmax_finish(L.pval, L.pidx, nblk, L.nan, result, st);
 }

@@ -177,6 +177,8 @@ int gpbo_launch_transpose_upper(const double *W, int64_t Np, double *U, hipStrea
 int gpbo_launch_argmax_finish(const double *part_val, const int64_t *part_idx, int64_t nparts,
                               const unsigned long long *nan_count, gpbo_result *result, hipStream_t st);
 int64_t gpbo_posterior_workspace_bytes_split(int64_t Np, int64_t chunk, int64_t M, int split_max);
+// the K(X*,X)^T image a pass over ONE chunk (M <= chunk) leaves in its workspace: [Np x chunk] doubles, leading dimension chunk
+const double *gpbo_posterior_chunk_image(const void *work, int64_t Np, int64_t chunk, int64_t M);
 // the fp64 pass behind every extern "C" scoring entry of sigma_acq.hip (split_max, n_prefix: see its definition); out.var unused
 int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp, const Acquisition &acq, double diag_add,
                                  int64_t idx_offset, int64_t chunk, const DenseOut &out, gpbo_result *result, void *work,

@@ -1,6 +1,7 @@
 // Host-side plumbing shared by the scoring drivers (sigma_acq.hip, posterior_f32.hip, ozaki.hip, rescore.hip, host_api.hip)
-// and the launchers below them: size arithmetic, the argument refusals, environment switches, the profile-slot bookkeeping,
-// the dense outputs of a chunk, the model / acquisition views, the length-scale scalings, the dispatch over d.
+// and the launchers below them: size arithmetic, the workspace carver, the argument refusals, environment switches, the
+// profile-slot bookkeeping, the dense outputs of a chunk, the model / acquisition views, the length-scale scalings, the
+// dispatch over d.
 // Host only: no device code in this file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,6 +20,25 @@ inline int64_t clamp_chunk(int64_t chunk, int64_t M) {
     const int64_t need = round_up_granule(M);
     return chunk > need ? need : chunk;
 }
+
+// ---- a workspace as consecutive 256-byte aligned regions.  Every layout is a struct of typed pointers that ONE function carves
+// in region order: with a null base it only counts (the *_workspace_bytes query returns total()), with `work` it hands out the
+// pointers the kernels get, so the type and count of the size pass are those of the pointer.
+class Carver {
+    char *base_;
+    int64_t off_ = 0;
+
+public:
+    explicit Carver(void *base) : base_(static_cast<char *>(base)) {}
+    void *take_bytes(int64_t n) {   // a nested workspace or an opaque region
+        void *p = base_ ? base_ + off_ : nullptr;
+        off_ += align_up(n, 256);
+        return p;
+    }
+    template <class T>
+    T *take(int64_t count) { return static_cast<T *>(take_bytes((int64_t)sizeof(T) * count)); }
+    int64_t total() const { return off_; }
+};
 
 // ---- refusals (each entry point keeps its own order of checks: GPBO_ERR_ARG before GPBO_ERR_WORKSPACE before any HIP call)
 inline bool chunk_ok(int64_t chunk) {
@@ -54,7 +74,7 @@ inline bool length_scale_scalings(const double *ls_host, int d, double *il2, dou
 }
 
 // ---- one kernel instance per feature count: CALL(1) ... CALL(GPBO_MAX_D) by the run-time d, inside a function that returns a
-// status.  (kernel_build.hip, ozaki.hip and kstar_mfma.hip join when their counter passes are next re-collected.)
+// status.  Every dispatch over d goes through it.
 #define GPBO_FOR_D(d, CALL)           \
     switch ((d)) {                    \
         case 1: CALL(1); break;       \

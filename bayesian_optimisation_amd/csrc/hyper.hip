@@ -161,11 +161,22 @@ bool positive_finite(double v) { return v > 0.0 && v < __builtin_huge_val(); }
 
 // the workspace of gpbo_nlml_hyper_f64: the gradient's own, then six [Np] vectors and the scalars
 struct HyperLayout {
-    int64_t wgrad, vec, total;
-    HyperLayout(int64_t Np, int32_t d) {
-        wgrad = align256(gpbo_nlml_grad_workspace_bytes(Np, d));
-        vec = align256((int64_t)sizeof(double) * Np);
-        total = wgrad + 6 * vec + 256 + 256;   // kappa, ones, tmp, b, alpha / s, r / s | scal | the gradient's out
+    void *grad_work;
+    double *kappa, *ones, *tmp, *b, *alpha_std, *r_std, *scal, *gout;
+    int64_t wgrad, total;
+    HyperLayout(void *work, int64_t Np, int32_t d) {
+        Carver c(work);
+        wgrad = gpbo_nlml_grad_workspace_bytes(Np, d);
+        grad_work = c.take_bytes(wgrad);
+        kappa = c.take<double>(Np);
+        ones = c.take<double>(Np);
+        tmp = c.take<double>(Np);
+        b = c.take<double>(Np);
+        alpha_std = c.take<double>(Np);   // alpha / s
+        r_std = c.take<double>(Np);       // r / s
+        scal = c.take<double>(32);
+        gout = c.take<double>(32);        // the gradient's out
+        total = c.total();
     }
 };
 
@@ -179,7 +190,7 @@ int launch_rowsum(const double *U, int64_t N, int64_t Np, double *kappa, double 
 
 extern "C" int64_t gpbo_nlml_hyper_workspace_bytes(int64_t Np, int32_t d) {
     if (gpbo_nlml_grad_workspace_bytes(Np, d) < 0) return GPBO_ERR_ARG;
-    return HyperLayout(Np, d).total;
+    return HyperLayout(nullptr, Np, d).total;
 }
 
 extern "C" int gpbo_nlml_hyper_f64(const double *U, const double *alpha, const double *y, const double *X, int64_t N,
@@ -202,24 +213,19 @@ extern "C" int gpbo_nlml_hyper_kern_f64(const double *U, const double *alpha, co
     if (!positive_finite(noise) || (flags & ~(GPBO_HYPER_MEAN | GPBO_HYPER_SCALE))) return GPBO_ERR_ARG;
     if (!length_scales_ok(ls_host, d)) return GPBO_ERR_ARG;
     if (!aligned_to(U, 16) || !aligned_to(work, 16)) return GPBO_ERR_ARG;
-    const HyperLayout L(Np, d);
+    const HyperLayout L(work, Np, d);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
-    char *w = reinterpret_cast<char *>(work);
-    auto vec = [&](int k) { return reinterpret_cast<double *>(w + L.wgrad + k * L.vec); };
-    double *kappa = vec(0), *ones = vec(1), *tmp = vec(2), *b = vec(3), *alpha_std = vec(4), *r_std = vec(5);
-    double *scal = reinterpret_cast<double *>(w + L.wgrad + 6 * L.vec);
-    double *gout = scal + 32;
     hipStream_t st = gpbo_stream(stream);
-    int rc = launch_rowsum(U, N, Np, kappa, ones, st);
+    int rc = launch_rowsum(U, N, Np, L.kappa, L.ones, st);
     if (rc != GPBO_OK) return rc;
-    rc = gpbo_alpha_f64(U, ones, N, Np, tmp, b, stream);
+    rc = gpbo_alpha_f64(U, L.ones, N, Np, L.tmp, L.b, stream);
     if (rc != GPBO_OK) return rc;
-    hipLaunchKernelGGL(hyper_profile_kernel, dim3(1), dim3(PROFILE_THREADS), 0, st, alpha, b, y, kappa, N, Np, (int)flags,
-                       alpha_std, r_std, alpha_std_out, scal);
+    hipLaunchKernelGGL(hyper_profile_kernel, dim3(1), dim3(PROFILE_THREADS), 0, st, alpha, L.b, y, L.kappa, N, Np, (int)flags,
+                       L.alpha_std, L.r_std, alpha_std_out, L.scal);
     GPBO_CHECK_LAUNCH();
-    rc = gpbo_nlml_grad_kern_f64(U, alpha_std, r_std, X, N, Np, d, ls_host, kernel, info, gout, work, L.wgrad, stream);
+    rc = gpbo_nlml_grad_kern_f64(U, L.alpha_std, L.r_std, X, N, Np, d, ls_host, kernel, info, L.gout, L.grad_work, L.wgrad, stream);
     if (rc != GPBO_OK) return rc;
-    hipLaunchKernelGGL(hyper_finish_kernel, dim3(1), dim3(64), 0, st, gout, scal, (int)d, N, noise, info, out);
+    hipLaunchKernelGGL(hyper_finish_kernel, dim3(1), dim3(64), 0, st, L.gout, L.scal, (int)d, N, noise, info, out);
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
 }

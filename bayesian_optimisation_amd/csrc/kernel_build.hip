@@ -315,12 +315,7 @@ __global__ __launch_bounds__(256) void kstar_mu_anyd_kernel(const double *__rest
 static int make_ls_anyd(const double *ls_host, int d, hipStream_t st, double **dev_out) {
     if (!ls_host || d < 1 || d > GPBO_MAX_D_ANY) return GPBO_ERR_ARG;
     std::vector<double> h(2 * (size_t)d);
-    for (int k = 0; k < d; ++k) {
-        const double l = ls_host[k];
-        if (!(l > 0.0)) return GPBO_ERR_ARG;
-        h[k] = 1.0 / (l * l);
-        h[d + k] = 1.0 / (l * 1.4142135623730950488);
-    }
+    if (!length_scale_scalings(ls_host, d, h.data(), h.data() + d)) return GPBO_ERR_ARG;
     double *p = nullptr;
     if (hipMallocAsync(reinterpret_cast<void **>(&p), sizeof(double) * 2 * d, st) != hipSuccess) return GPBO_ERR_LAUNCH;
     // (pageable source: the runtime stages the bytes before the call returns, so `h` may go out of scope)
@@ -353,35 +348,8 @@ int gpbo_kstar_mu_anyd(const double *Xs, int64_t Mc, const double *X, int64_t N,
 static int make_ls(const double *ls_host, int d, LsArgs *out) {
     if (!ls_host || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
     for (int k = 0; k < GPBO_MAX_D; ++k) out->il2[k] = out->isc[k] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        const double l = ls_host[k];
-        if (!(l > 0.0)) return GPBO_ERR_ARG;
-        out->il2[k] = 1.0 / (l * l);
-        out->isc[k] = 1.0 / (l * 1.4142135623730950488);
-    }
-    return GPBO_OK;
+    return length_scale_scalings(ls_host, d, out->il2, out->isc) ? GPBO_OK : GPBO_ERR_ARG;
 }
-
-#define GPBO_DISPATCH_D(d, CALL) \
-    switch (d) {                 \
-        case 1: CALL(1); break;  \
-        case 2: CALL(2); break;  \
-        case 3: CALL(3); break;  \
-        case 4: CALL(4); break;  \
-        case 5: CALL(5); break;  \
-        case 6: CALL(6); break;  \
-        case 7: CALL(7); break;  \
-        case 8: CALL(8); break;  \
-        case 9: CALL(9); break;  \
-        case 10: CALL(10); break; \
-        case 11: CALL(11); break; \
-        case 12: CALL(12); break; \
-        case 13: CALL(13); break; \
-        case 14: CALL(14); break; \
-        case 15: CALL(15); break; \
-        case 16: CALL(16); break; \
-        default: return GPBO_ERR_ARG; \
-    }
 
 int gpbo_kxx_launch(const double *X, int64_t N, int32_t d, const double *ls_host, int32_t kernel, double jitter1,
                     double jitter2, double *Kp, int64_t Np, double *K2, int64_t ld2, int32_t *info0, void *stream) {
@@ -411,7 +379,7 @@ int gpbo_kxx_launch(const double *X, int64_t N, int32_t d, const double *ls_host
     if (kernel == GPBO_KERNEL_MATERN32) KXX_LAUNCH(DD, GPBO_KERNEL_MATERN32);     \
     else if (kernel == GPBO_KERNEL_MATERN52) KXX_LAUNCH(DD, GPBO_KERNEL_MATERN52); \
     else KXX_LAUNCH(DD, GPBO_KERNEL_SE)
-    GPBO_DISPATCH_D(d, CALL)
+    GPBO_FOR_D(d, CALL)
 #undef CALL
 #undef KXX_LAUNCH
     GPBO_CHECK_LAUNCH();
@@ -508,7 +476,7 @@ int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t 
     else KSTAR_LAUNCH(DD, 0, false)
 #endif
     (void)variant;
-    GPBO_DISPATCH_D(d, CALL)
+    GPBO_FOR_D(d, CALL)
 #undef CALL
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
@@ -537,7 +505,7 @@ int gpbo_kstar_mu_mixed(const double *Xs, int64_t Mc, const double *Xsc, int64_t
     else                                                                                                             \
         hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, float, false>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, \
                            Xsc, (int)N, ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)Np)
-    GPBO_DISPATCH_D(d, CALL)
+    GPBO_FOR_D(d, CALL)
 #undef CALL
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;

@@ -296,6 +296,19 @@ __global__ __launch_bounds__(256) void kstar_mu_mfma_kernel(const double *__rest
     }
 }
 
+// the prep buffer: the centred observation rows, then the record of their sums
+struct PrepLayout {
+    double *Bp;
+    ObsPrep *prep;
+    int64_t total;
+    PrepLayout(const void *prep_buf, int64_t Np) {
+        Carver c(const_cast<void *>(prep_buf));
+        Bp = c.take<double>(Np * KP_MAX);
+        prep = c.take<ObsPrep>(1);
+        total = c.total();
+    }
+};
+
 }  // namespace
 
 // observations per workgroup = per partial of the mean (mu_part has Np / slice rows): the candidate operands of a wave
@@ -303,7 +316,7 @@ __global__ __launch_bounds__(256) void kstar_mu_mfma_kernel(const double *__rest
 int gpbo_kstar_mfma_slice(int64_t Np) { return (Np % 256 == 0) ? 256 : 128; }
 
 int64_t gpbo_kstar_mfma_prep_bytes(int64_t Np) {
-    return align_up((int64_t)sizeof(double) * Np * KP_MAX, 256) + align_up((int64_t)sizeof(ObsPrep), 256);
+    return PrepLayout(nullptr, Np).total;
 }
 
 // once per call: centred observation rows, S0, S1 (alpha: the factorisation's, padded with zeros to Np)
@@ -312,16 +325,11 @@ int gpbo_kstar_mfma_prep(const double *X, int64_t N, int64_t Np, int32_t d, cons
     if (!X || !ls_host || !alpha || !prep_buf || N < 1 || Np < N || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
     IscArgs ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.isc[k] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        if (!(ls_host[k] > 0.0)) return GPBO_ERR_ARG;
-        ls.isc[k] = 1.0 / (ls_host[k] * 1.4142135623730950488);
-    }
+    if (!length_scale_scalings(ls_host, d, nullptr, ls.isc)) return GPBO_ERR_ARG;
     const int KP = (d + 2 + 3) / 4 * 4;
-    double *Bp = reinterpret_cast<double *>(prep_buf);
-    ObsPrep *prep = reinterpret_cast<ObsPrep *>(reinterpret_cast<char *>(prep_buf) +
-                                                align_up((int64_t)sizeof(double) * Np * KP_MAX, 256));
+    const PrepLayout L(prep_buf, Np);
     hipLaunchKernelGGL(obs_prep_kernel, dim3(1), dim3(1024), 0, gpbo_stream(stream), X, (int)N, (int)Np, (int)d, ls, alpha, KP,
-                       Bp, prep);
+                       L.Bp, L.prep);
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
 }
@@ -337,18 +345,16 @@ int gpbo_kstar_mu_mfma(const double *Xs, int64_t Mc, int64_t N, int64_t Np, int3
     if (store_rows < 0 || store_rows > Np || store_rows % KS) return GPBO_ERR_ARG;
     IscArgs ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.isc[k] = 0.0;
-    for (int k = 0; k < d; ++k) ls.isc[k] = 1.0 / (ls_host[k] * 1.4142135623730950488);
+    if (!length_scale_scalings(ls_host, d, nullptr, ls.isc)) return GPBO_ERR_ARG;   // (the prep call has refused it already)
     const int KQ = (d + 3) / 4, KP = (d + 2 + 3) / 4 * 4;
     const double gamma = 2.0 * (2.0 * (d + 2) + 8.0) * 1.1102230246251565e-16;   // 2^-53
     const double eps_acc = 2.0 * (2.0 * 64.0 + 4.0 + (double)(Np / 64) + (double)(Np / 256)) * 1.1102230246251565e-16;
-    const double *Bp = reinterpret_cast<const double *>(prep_buf);
-    const ObsPrep *prep = reinterpret_cast<const ObsPrep *>(reinterpret_cast<const char *>(prep_buf) +
-                                                            align_up((int64_t)sizeof(double) * Np * KP_MAX, 256));
+    const PrepLayout L(prep_buf, Np);
     const int64_t used = round_up_granule(Mc);
     const int OB = gpbo_kstar_mfma_slice(Np);
     dim3 grid((unsigned)(used / 256), (unsigned)(Np / OB));
-#define GPBO_KM_LAUNCH(Q)                                                                                              \
-    hipLaunchKernelGGL((kstar_mu_mfma_kernel<Q>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, (int)d, ls, Bp, prep, alpha, \
+#define GPBO_KM_LAUNCH(Q)                                                                                                           \
+    hipLaunchKernelGGL((kstar_mu_mfma_kernel<Q>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, (int)d, ls, L.Bp, L.prep, alpha, \
                        (int)N, gamma, eps_acc, KsT, ldk, mu_part, (int)store_rows, OB, KP)
     switch (KQ) {
         case 1: GPBO_KM_LAUNCH(1); break;

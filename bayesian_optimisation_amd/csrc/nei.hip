@@ -210,45 +210,44 @@ __global__ __launch_bounds__(256) void nei_rowmin_kernel(const double *__restric
     if (tid == 0) best[s] = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
 }
 
-struct FantasyLayout {
-    int64_t mat, p_off, q_off, r_off, total;
-    explicit FantasyLayout(int64_t Np) {
-        mat = align_up(8 * 64 * Np, 256);
-        p_off = 0;
-        q_off = mat;
-        r_off = 2 * mat;
-        total = 3 * mat;
+struct FantasyLayout {   // three [64 x Np] matrices
+    double *P, *Q, *R;
+    int64_t total;
+    FantasyLayout(void *work, int64_t Np) {
+        Carver c(work);
+        P = c.take<double>(64 * Np);
+        Q = c.take<double>(64 * Np);
+        R = c.take<double>(64 * Np);
+        total = c.total();
     }
 };
 
 struct NeiLayout {
-    int64_t post, vec, at_off, best_off, nan0_off, sigma_off, pval_off, pidx_off, nan_off, res_off, total, nparts;
-    NeiLayout(int64_t Np, int64_t chunk, int64_t M, int32_t S) {
-        post = align_up(gpbo_posterior_workspace_bytes_split(Np, chunk, M < chunk ? M : chunk, 1), 256);   // one chunk per call
-        vec = align_up(8 * M, 256);
-        nparts = (M + NEI_TILE_MIN - 1) / NEI_TILE_MIN;   // (capacity: the wider tile writes fewer)
-        int64_t o = post;
-        at_off = o;     o += align_up(8 * Np * padded_fantasies(S), 256);
-        best_off = o;   o += align_up(8 * GPBO_NEI_MAX_S, 256);
-        nan0_off = o;   o += vec;
-        sigma_off = o;  o += vec;
-        pval_off = o;   o += align_up(8 * nparts, 256);
-        pidx_off = o;   o += align_up(8 * nparts, 256);
-        nan_off = o;    o += 256;
-        res_off = o;    o += 256;   // the pass's own result record: not reported
-        total = o;
+    void *post_work;   // the workspace of a one-chunk fp64 pass, post bytes
+    double *at, *best, *nan0, *sigma, *pval;
+    int64_t *pidx;
+    unsigned long long *nan;
+    gpbo_result *res;   // the pass's own result record: not reported
+    int64_t post, total;
+    NeiLayout(void *work, int64_t Np, int64_t chunk, int64_t M, int32_t S) {
+        Carver c(work);
+        post = gpbo_posterior_workspace_bytes_split(Np, chunk, M < chunk ? M : chunk, 1);   // one chunk per call
+        const int64_t nparts = (M + NEI_TILE_MIN - 1) / NEI_TILE_MIN;   // (capacity: the wider tile writes fewer)
+        post_work = c.take_bytes(post);
+        at = c.take<double>(Np * padded_fantasies(S));
+        best = c.take<double>(GPBO_NEI_MAX_S);
+        nan0 = c.take<double>(M);
+        sigma = c.take<double>(M);
+        pval = c.take<double>(nparts);
+        pidx = c.take<int64_t>(nparts);
+        nan = c.take<unsigned long long>(32);   // 256 bytes
+        res = static_cast<gpbo_result *>(c.take_bytes(256));
+        total = c.total();
     }
 };
 
 bool fantasies_ok(int32_t S) { return S >= 1 && S <= GPBO_NEI_MAX_S; }
 bool is_finite(double v) { return v - v == 0.0; }
-
-// The K(X*,X)^T image of a pass over ONE chunk (M <= chunk) inside that pass's workspace: PosteriorLayout (sigma_acq.hip) opens
-// with the chunk buffer, [Np x chunk] doubles with the leading dimension `chunk`, and a one-chunk pass has no second buffer.  Kept
-// here, beside its only reader, instead of next to gpbo_posterior_workspace_bytes_split: sigma_acq.hip and gpbo_internal.h are
-// the sources the committed counter passes are stamped with (profiles/source_hash.py).  Should that layout move, every value
-// test of tests/test_gpu_nei.py fails: the means would be read from somewhere else.
-inline const double *posterior_chunk_image(const void *post_work) { return reinterpret_cast<const double *>(post_work); }
 
 // nei_kernel on the image of the chunk that starts at candidate `start`.
 struct NeiRun {
@@ -288,7 +287,7 @@ int nei_chunk(const NeiRun &r, int64_t start, int64_t Mc, const double *KsT, int
 
 extern "C" int64_t gpbo_nei_fantasies_workspace_bytes(int64_t Np, int32_t S) {
     if (!np_ok(Np) || Np > (1 << 20) || !fantasies_ok(S)) return GPBO_ERR_ARG;
-    return FantasyLayout(Np).total;
+    return FantasyLayout(nullptr, Np).total;
 }
 
 extern "C" int gpbo_nei_fantasies_f64(const double *K0d, const double *U0, const double *U, const double *y, int64_t N,
@@ -298,12 +297,10 @@ extern "C" int gpbo_nei_fantasies_f64(const double *K0d, const double *U0, const
     if (!fantasies_ok(S) || N < 1 || !np_ok(Np) || Np > (1 << 20) || N > Np) return GPBO_ERR_ARG;
     if (!(noise_sd >= 0.0) || !is_finite(noise_sd)) return GPBO_ERR_ARG;
     if (!aligned_to(K0d, 16) || !aligned_to(U0, 16) || !aligned_to(U, 16)) return GPBO_ERR_ARG;   // the GEMM's B operands
-    const FantasyLayout L(Np);
+    const FantasyLayout L(work, Np);
     if (work_bytes < L.total || !aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    double *P = reinterpret_cast<double *>(w + L.p_off), *Q = reinterpret_cast<double *>(w + L.q_off);
-    double *R = reinterpret_cast<double *>(w + L.r_off);
+    double *P = L.P, *Q = L.Q, *R = L.R;
     const dim3 grid((unsigned)((64 * Np + 255) / 256));
     hipLaunchKernelGGL(nei_pack_kernel, grid, dim3(256), 0, st, Z, (int)S, N, Np, P);
     GPBO_CHECK_LAUNCH();
@@ -329,7 +326,7 @@ extern "C" int gpbo_nei_fantasies_f64(const double *K0d, const double *U0, const
 
 extern "C" int64_t gpbo_posterior_nei_workspace_bytes(int64_t Np, int64_t chunk, int64_t M, int32_t S) {
     if (gpbo_posterior_workspace_bytes_split(Np, chunk, M, 1) < 0 || M > NEI_MAX_M || !fantasies_ok(S)) return GPBO_ERR_ARG;
-    return NeiLayout(Np, chunk, M, S).total;
+    return NeiLayout(nullptr, Np, chunk, M, S).total;
 }
 
 extern "C" int gpbo_posterior_nei_kern_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
@@ -344,22 +341,19 @@ extern "C" int gpbo_posterior_nei_kern_f64(const double *Xs, int64_t M, const do
     if (!(prior_var > 0.0) || !is_finite(prior_var) || !is_finite(xi) || (mu_out && ldm < M)) return GPBO_ERR_ARG;
     if (!aligned_to(U0, 16)) return GPBO_ERR_ARG;
     if (!aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
-    const NeiLayout L(Np, chunk, M, S);
+    const NeiLayout L(work, Np, chunk, M, S);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    auto vec = [&](int64_t off) { return reinterpret_cast<double *>(w + off); };
-    double *At = vec(L.at_off), *best_p = vec(L.best_off), *nan0 = vec(L.nan0_off);
-    double *sigma = sigma_out ? sigma_out : vec(L.sigma_off);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
-    gpbo_result *scratch = reinterpret_cast<gpbo_result *>(w + L.res_off);
+    double *At = L.at, *best_p = L.best, *nan0 = L.nan0;
+    double *sigma = sigma_out ? sigma_out : L.sigma;
+    unsigned long long *nan_count = L.nan;
+    gpbo_result *scratch = L.res;
     const int Sp = padded_fantasies(S);
     if (hipMemsetAsync(nan_count, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
     hipLaunchKernelGGL(nei_prep_kernel, dim3((unsigned)((Np * Sp + 255) / 256)), dim3(256), 0, st, A, best, (int)S, Sp, N, Np, At,
                        best_p);
     GPBO_CHECK_LAUNCH();
-    NeiRun run = {N, At, best_p, nan0, sigma, (int)S, Sp, xi, idx_offset, mu_out, ldm, acq_out, vec(L.pval_off),
-                  reinterpret_cast<int64_t *>(w + L.pidx_off), nan_count};
+    NeiRun run = {N, At, best_p, nan0, sigma, (int)S, Sp, xi, idx_offset, mu_out, ldm, acq_out, L.pval, L.pidx, nan_count};
     // The pass with the twin's factor, one chunk per call: sigma_0 of the chunk's candidates, its own mean with A_0 as alpha -
     // which marks the candidates with a NaN coordinate - and, left behind in its workspace, the chunk's K(X*,X)^T image.  The
     // pass's acquisition and arg-max are not used (LCB with explore 0 is the cheapest it has).
@@ -370,9 +364,10 @@ extern "C" int gpbo_posterior_nei_kern_f64(const double *Xs, int64_t M, const do
     for (int64_t s = 0; s < M; s += chunk) {
         const int64_t Mc = (M - s < chunk) ? (M - s) : chunk;
         int rc = gpbo_posterior_acq_f64_split(Xs + s * d, Mc, gp, {GPBO_ACQ_LCB, 0.0, 0.0}, 0.0, idx_offset + s, chunk,
-                                              {nan0 + s, sigma + s, nullptr, nullptr}, scratch, work, L.post, nullptr, 1, 0, stream);
+                                              {nan0 + s, sigma + s, nullptr, nullptr}, scratch, L.post_work, L.post, nullptr, 1, 0,
+                                              stream);
         if (rc != GPBO_OK) return rc;
-        rc = nei_chunk(run, s, Mc, posterior_chunk_image(work), chunk, st);
+        rc = nei_chunk(run, s, Mc, gpbo_posterior_chunk_image(L.post_work, Np, chunk, Mc), chunk, st);
         if (rc != GPBO_OK) return rc;
     }
     const int tile = nei_tile(Sp);

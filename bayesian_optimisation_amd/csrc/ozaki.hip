@@ -823,10 +823,6 @@ __global__ __launch_bounds__(512) void sigma_i8c_kernel(const char *__restrict__
     if (tid < CBM) ss_part[(int64_t)grp * ldk + (int64_t)tile * CBM + tid] = red[tid] + red[CBM + tid];
 }
 
-struct LayoutI8 {
-    int64_t a8_off, mup_off, xsc_off, pval_off, pidx_off, nan_off, ssp_off, total, nparts_cap;
-};
-
 #ifndef GPBO_I8_G
 #define GPBO_I8_G 8
 #endif
@@ -839,22 +835,42 @@ int i8_groups(int64_t Np) {
     return (GPBO_I8_G <= nJ / 2) ? GPBO_I8_G : (int)(nJ / 2);
 }
 
-LayoutI8 layout_i8(int64_t Np, int64_t chunk, int64_t M) {
-    LayoutI8 L;
-    const int64_t nchunks = (M + chunk - 1) / chunk;
-    L.nparts_cap = nchunks * ((chunk + 255) / 256);   // partials of the 128-row fused epilogue or the 256-row split one
-    if (L.nparts_cap < nchunks * (chunk / BM)) L.nparts_cap = nchunks * (chunk / BM);
-    int64_t off = 0;
-    L.a8_off = off; off += align_up(Np * chunk * NSA, 256);
-    L.mup_off = off; off += align_up((int64_t)sizeof(double) * (Np / KS_SLICE) * chunk, 256);
-    L.xsc_off = off; off += align_up((int64_t)sizeof(double) * Np * GPBO_MAX_D, 256);
-    L.pval_off = off; off += align_up((int64_t)sizeof(double) * L.nparts_cap, 256);
-    L.pidx_off = off; off += align_up((int64_t)sizeof(int64_t) * L.nparts_cap, 256);
-    L.nan_off = off; off += 256;
-    L.ssp_off = off; off += align_up((int64_t)sizeof(double) * I8_GROUPS_MAX * chunk, 256);
-    L.total = off;
-    return L;
-}
+struct LayoutI8 {
+    char *a8;
+    double *mup, *xsc, *pval;
+    int64_t *pidx;
+    unsigned long long *nan;
+    double *ssp;
+    int64_t total;
+    LayoutI8(void *work, int64_t Np, int64_t chunk, int64_t M) {
+        Carver c(work);
+        const int64_t nchunks = (M + chunk - 1) / chunk;
+        int64_t nparts_cap = nchunks * ((chunk + 255) / 256);   // partials of the 128-row fused epilogue or the 256-row split one
+        if (nparts_cap < nchunks * (chunk / BM)) nparts_cap = nchunks * (chunk / BM);
+        a8 = c.take<char>(Np * chunk * NSA);
+        mup = c.take<double>((Np / KS_SLICE) * chunk);
+        xsc = c.take<double>(Np * GPBO_MAX_D);
+        pval = c.take<double>(nparts_cap);
+        pidx = c.take<int64_t>(nparts_cap);
+        nan = c.take<unsigned long long>(32);   // 256 bytes
+        ssp = c.take<double>(I8_GROUPS_MAX * chunk);
+        total = c.total();
+    }
+};
+
+// the factor image gpbo_prepare_i8 leaves in `u8`: the int8 fragments of U, its column scales and their inverses
+struct ImageI8 {
+    char *slices;
+    double *scale, *inv;
+    int64_t total;
+    ImageI8(const void *u8, int64_t Np) {
+        Carver c(const_cast<void *>(u8));
+        slices = c.take<char>(Np * Np * NS);
+        scale = c.take<double>(Np);
+        inv = c.take<double>(Np);
+        total = c.total();
+    }
+};
 
 }  // namespace
 
@@ -874,7 +890,7 @@ extern "C" int gpbo_i8_stamps_read(unsigned long long *out4_host, int reset) {
 
 extern "C" int64_t gpbo_prepare_i8_bytes(int64_t Np) {
     if (!np_ok(Np) || Np > GPBO_I8_MAX_N) return GPBO_ERR_ARG;
-    return align_up(Np * Np * NS, 256) + 2 * align_up((int64_t)sizeof(double) * Np, 256);
+    return ImageI8(nullptr, Np).total;
 }
 
 extern "C" int gpbo_prepare_i8(const double *U, int64_t Np, void *u8, int64_t u8_bytes, void *stream) {
@@ -883,9 +899,9 @@ extern "C" int gpbo_prepare_i8(const double *U, int64_t Np, void *u8, int64_t u8
     if (need < 0) return GPBO_ERR_ARG;
     if (u8_bytes < need) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *U8 = reinterpret_cast<char *>(u8);
-    double *scale = reinterpret_cast<double *>(U8 + align_up(Np * Np * NS, 256));
-    double *inv = scale + align_up((int64_t)sizeof(double) * Np, 256) / 8;
+    const ImageI8 I(u8, Np);
+    char *U8 = I.slices;
+    double *scale = I.scale, *inv = I.inv;
     hipLaunchKernelGGL(u_colscale_kernel, dim3((unsigned)(Np / 64)), dim3(1024), 0, st, U, (int)Np, scale, inv);
     hipLaunchKernelGGL(u_slices_kernel, dim3((unsigned)(Np / 256 + (Np % 256 ? 1 : 0)), (unsigned)(Np / 16)), dim3(256), 0, st,
                        U, (int)Np, inv, U8);
@@ -895,7 +911,7 @@ extern "C" int gpbo_prepare_i8(const double *U, int64_t Np, void *u8, int64_t u8
 
 extern "C" int64_t gpbo_posterior_workspace_bytes_i8(int64_t Np, int64_t chunk, int64_t M) {
     if (!np_ok(Np) || Np > GPBO_I8_MAX_N || !chunk_ok(chunk) || M < 1) return GPBO_ERR_ARG;
-    return layout_i8(Np, chunk, M).total;
+    return LayoutI8(nullptr, Np, chunk, M).total;
 }
 
 namespace {
@@ -911,25 +927,16 @@ int posterior_i8_impl(bool coarse, const double *Xs, int64_t M, const GpModel &g
     if (!chunk_ok(chunk)) return GPBO_ERR_ARG;
     if (!acq_kind_ok(acq.kind)) return GPBO_ERR_ARG;
     if (!aligned_to(work, 256) || !aligned_to(u8, 256)) return GPBO_ERR_ARG;
-    const LayoutI8 L = layout_i8(Np, chunk, M);
+    const LayoutI8 L(work, Np, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     LsArgsI8 ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.isc[k] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        if (!(ls_host[k] > 0.0)) return GPBO_ERR_ARG;
-        ls.isc[k] = 1.0 / (ls_host[k] * 1.4142135623730950488);
-    }
+    if (!length_scale_scalings(ls_host, d, nullptr, ls.isc)) return GPBO_ERR_ARG;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    char *A8 = w + L.a8_off;
-    double *mu_part = reinterpret_cast<double *>(w + L.mup_off);
-    double *Xsc = reinterpret_cast<double *>(w + L.xsc_off);
-    double *part_val = reinterpret_cast<double *>(w + L.pval_off);
-    int64_t *part_idx = reinterpret_cast<int64_t *>(w + L.pidx_off);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
-    const char *U8 = reinterpret_cast<const char *>(u8);
-    const double *colscale = reinterpret_cast<const double *>(U8 + align_up(Np * Np * NS, 256));
-    int rc = gpbo_scale_points_launch(X, N, Np, d, ls_host, Xsc, nan_count, stream);
+    const ImageI8 I(u8, Np);
+    const char *U8 = I.slices;
+    const double *colscale = I.scale;
+    int rc = gpbo_scale_points_launch(X, N, Np, d, ls_host, L.xsc, L.nan, stream);
     if (rc != GPBO_OK) return rc;
     const int64_t RT = chunk / 32;
     int64_t nparts = 0;
@@ -941,21 +948,15 @@ int posterior_i8_impl(bool coarse, const double *Xs, int64_t M, const GpModel &g
         const int64_t used = (Mc + 255) / 256 * 256;
         dim3 kgrid((unsigned)(used / 256), (unsigned)(Np / KS_SLICE));
         const bool nt = Np * chunk * (coarse ? CNA : NSA) > ((int64_t)1 << 30);
-#define CALL1(DD, NTT, NAA)                                                                                               \
-    hipLaunchKernelGGL((kstar_slices_kernel<DD, NTT, NAA>), kgrid, dim3(256), 0, st, Xs + s * d, Mc, Xsc, (int)N, ls, alpha,  \
-                       A8, RT, mu_part, chunk)
+#define CALL1(DD, NTT, NAA)                                                                                                    \
+    hipLaunchKernelGGL((kstar_slices_kernel<DD, NTT, NAA>), kgrid, dim3(256), 0, st, Xs + s * d, Mc, L.xsc, (int)N, ls, alpha, \
+                       L.a8, RT, L.mup, chunk)
 #define CALL(DD)                                                                                                          \
     do {                                                                                                                  \
         if (coarse) { if (nt) CALL1(DD, true, CNA); else CALL1(DD, false, CNA); }                                         \
         else { if (nt) CALL1(DD, true, NSA); else CALL1(DD, false, NSA); }                                                \
     } while (0)
-        switch (d) {
-            case 1: CALL(1); break;   case 2: CALL(2); break;   case 3: CALL(3); break;   case 4: CALL(4); break;
-            case 5: CALL(5); break;   case 6: CALL(6); break;   case 7: CALL(7); break;   case 8: CALL(8); break;
-            case 9: CALL(9); break;   case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break;
-            case 13: CALL(13); break; case 14: CALL(14); break; case 15: CALL(15); break; case 16: CALL(16); break;
-            default: return GPBO_ERR_ARG;
-        }
+        GPBO_FOR_D(d, CALL)
 #undef CALL
 #undef CALL1
         const int64_t nblk = (Mc + BM - 1) / BM;
@@ -963,33 +964,32 @@ int posterior_i8_impl(bool coarse, const double *Xs, int64_t M, const GpModel &g
         const int G = i8_groups(Np);
         const DenseOut o = out.at(s);
         int64_t nparts_here = nblk;
-        double *ss_part = reinterpret_cast<double *>(w + L.ssp_off);
-        const bool split = coarse || G > 1;   // partial sums to ss_part, the epilogue in split_finish_kernel
+        const bool split = coarse || G > 1;   // partial sums to L.ssp, the epilogue in split_finish_kernel
         if (coarse) {   // 256-row tiles
             const int64_t nblk_c = (Mc + CBM - 1) / CBM;
             const int64_t grid = (G > 1) ? (nblk_c + 7) / 8 * 8 * G : nblk_c;
-            hipLaunchKernelGGL(sigma_i8c_kernel, dim3((unsigned)grid), dim3(512), 0, st, A8, RT, U8, (int)Np, colscale, chunk, G,
-                               (int)nblk_c, ss_part);
+            hipLaunchKernelGGL(sigma_i8c_kernel, dim3((unsigned)grid), dim3(512), 0, st, L.a8, RT, U8, (int)Np, colscale, chunk, G,
+                               (int)nblk_c, L.ssp);
             nparts_here = nblk_c;
         } else {
             const DenseOut ko = split ? DenseOut{} : o;
             const int64_t grid = split ? (nblk + 7) / 8 * 8 * G : nblk;
-            hipLaunchKernelGGL(sigma_i8_kernel, dim3((unsigned)grid), dim3(512), 0, st, A8, RT, U8, (int)Np, colscale, mu_part,
+            hipLaunchKernelGGL(sigma_i8_kernel, dim3((unsigned)grid), dim3(512), 0, st, L.a8, RT, U8, (int)Np, colscale, L.mup,
                                (int)(Np / KS_SLICE), chunk, Mc, gp.prior_var, (int)acq.kind, acq.p0, acq.p1, idx_offset + s,
-                               ko.mu, ko.sigma, ko.acq, ko.var, part_val + nparts, part_idx + nparts, nan_count, G, (int)nblk,
-                               split ? ss_part : (double *)nullptr);
+                               ko.mu, ko.sigma, ko.acq, ko.var, L.pval + nparts, L.pidx + nparts, L.nan, G, (int)nblk,
+                               split ? L.ssp : (double *)nullptr);
             if (split) nparts_here = (Mc + 255) / 256;
         }
         if (split) {
-            int rc2 = gpbo_launch_split_finish(ss_part, G, chunk, mu_part, (int)(Np / KS_SLICE), Mc, gp.prior_var, acq,
-                                               idx_offset + s, o, part_val + nparts, part_idx + nparts, nan_count, st);
+            int rc2 = gpbo_launch_split_finish(L.ssp, G, chunk, L.mup, (int)(Np / KS_SLICE), Mc, gp.prior_var, acq,
+                                               idx_offset + s, o, L.pval + nparts, L.pidx + nparts, L.nan, st);
             if (rc2 != GPBO_OK) return rc2;
         }
         if (!slots.end(st, Mc)) return GPBO_ERR_LAUNCH;
         GPBO_CHECK_LAUNCH();
         nparts += nparts_here;
     }
-    return gpbo_launch_argmax_finish(part_val, part_idx, nparts, nan_count, result, st);
+    return gpbo_launch_argmax_finish(L.pval, L.pidx, nparts, L.nan, result, st);
 }
 }  // namespace
 

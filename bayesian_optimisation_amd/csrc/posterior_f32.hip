@@ -223,23 +223,23 @@ __global__ __launch_bounds__(512) void sigma_acq_f32_kernel(
 }
 
 struct Layout32 {
-    int64_t kst_off, mup_off, xsc_off, pval_off, pidx_off, nan_off, total, nparts_cap;
+    float *kst;
+    double *mup, *xsc, *pval;
+    int64_t *pidx;
+    unsigned long long *nan;
+    int64_t total;
+    Layout32(void *work, int64_t Np32, int64_t chunk, int64_t M) {
+        Carver c(work);
+        const int64_t nparts_cap = (M + chunk - 1) / chunk * (chunk / BM);
+        kst = c.take<float>(Np32 * chunk);
+        mup = c.take<double>((Np32 / KS_SLICE) * chunk);
+        xsc = c.take<double>(Np32 * GPBO_MAX_D);
+        pval = c.take<double>(nparts_cap);
+        pidx = c.take<int64_t>(nparts_cap);
+        nan = c.take<unsigned long long>(32);   // 256 bytes
+        total = c.total();
+    }
 };
-
-Layout32 layout32(int64_t Np32, int64_t chunk, int64_t M) {
-    Layout32 L;
-    const int64_t nchunks = (M + chunk - 1) / chunk;
-    L.nparts_cap = nchunks * (chunk / BM);
-    int64_t off = 0;
-    L.kst_off = off; off += align_up((int64_t)sizeof(float) * Np32 * chunk, 256);
-    L.mup_off = off; off += align_up((int64_t)sizeof(double) * (Np32 / KS_SLICE) * chunk, 256);
-    L.xsc_off = off; off += align_up((int64_t)sizeof(double) * Np32 * GPBO_MAX_D, 256);
-    L.pval_off = off; off += align_up((int64_t)sizeof(double) * L.nparts_cap, 256);
-    L.pidx_off = off; off += align_up((int64_t)sizeof(int64_t) * L.nparts_cap, 256);
-    L.nan_off = off; off += 256;
-    L.total = off;
-    return L;
-}
 
 }  // namespace
 
@@ -260,7 +260,7 @@ extern "C" int gpbo_prepare_f32(const double *U, const double *alpha, int64_t Np
 
 extern "C" int64_t gpbo_posterior_workspace_bytes_f32(int64_t Np32, int64_t chunk, int64_t M) {
     if (Np32 < BN || Np32 % BN || chunk < 1024 || chunk % 1024 || chunk > GPBO_CHUNK_MAX || M < 1) return GPBO_ERR_ARG;
-    return layout32(Np32, chunk, M).total;
+    return Layout32(nullptr, Np32, chunk, M).total;
 }
 
 extern "C" int gpbo_posterior_acq_f32(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np32, int32_t d,
@@ -274,18 +274,11 @@ extern "C" int gpbo_posterior_acq_f32(const double *Xs, int64_t M, const double 
     if (chunk < 1024 || chunk % 1024 || chunk > GPBO_CHUNK_MAX) return GPBO_ERR_ARG;
     if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
     if (!aligned_to(work, 256) || !aligned_to(U32, 16)) return GPBO_ERR_ARG;
-    const Layout32 L = layout32(Np32, chunk, M);
+    const Layout32 L(work, Np32, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    float *KsT = reinterpret_cast<float *>(w + L.kst_off);
-    double *mu_part = reinterpret_cast<double *>(w + L.mup_off);
-    double *Xsc = reinterpret_cast<double *>(w + L.xsc_off);
-    double *part_val = reinterpret_cast<double *>(w + L.pval_off);
-    int64_t *part_idx = reinterpret_cast<int64_t *>(w + L.pidx_off);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
     // observations / (ls sqrt 2) in fp64, once per call; the same launch clears the NaN counter
-    int rc = gpbo_scale_points_launch(X, N, Np32, d, ls_host, Xsc, nan_count, stream);
+    int rc = gpbo_scale_points_launch(X, N, Np32, d, ls_host, L.xsc, L.nan, stream);
     if (rc != GPBO_OK) return rc;
     int64_t nparts = 0;
     const DenseOut out = {mu_out, sigma_out, acq_out, var_out};
@@ -294,18 +287,18 @@ extern "C" int gpbo_posterior_acq_f32(const double *Xs, int64_t M, const double 
         const int64_t Mc = (M - s < chunk) ? (M - s) : chunk;
         // K(X*,X) launches are timed like the fp64 path's: the launches of this call form one chain on the stream
         if (!slots.kstar(st, s > 0)) return GPBO_ERR_LAUNCH;
-        rc = gpbo_kstar_mu_mixed(Xs + s * d, Mc, Xsc, N, Np32, d, ls_host, alpha, diag_add, idx_offset + s, KsT, chunk,
-                                 mu_part, stream);
+        rc = gpbo_kstar_mu_mixed(Xs + s * d, Mc, L.xsc, N, Np32, d, ls_host, alpha, diag_add, idx_offset + s, L.kst, chunk,
+                                 L.mup, stream);
         if (rc != GPBO_OK) return rc;
         const int64_t nblk = (Mc + BM - 1) / BM;
         if (!slots.begin(st)) return GPBO_ERR_LAUNCH;
         const DenseOut o = out.at(s);
-        hipLaunchKernelGGL(sigma_acq_f32_kernel, dim3((unsigned)nblk), dim3(512), 0, st, KsT, chunk, U32, (int)Np32, mu_part,
+        hipLaunchKernelGGL(sigma_acq_f32_kernel, dim3((unsigned)nblk), dim3(512), 0, st, L.kst, chunk, U32, (int)Np32, L.mup,
                            (int)(Np32 / KS_SLICE), Mc, prior_var, (int)acq_kind, p0, p1, idx_offset + s, o.mu, o.sigma, o.acq,
-                           o.var, part_val + nparts, part_idx + nparts, nan_count);
+                           o.var, L.pval + nparts, L.pidx + nparts, L.nan);
         if (!slots.end(st, Mc)) return GPBO_ERR_LAUNCH;
         GPBO_CHECK_LAUNCH();
         nparts += nblk;
     }
-    return gpbo_launch_argmax_finish(part_val, part_idx, nparts, nan_count, result, st);
+    return gpbo_launch_argmax_finish(L.pval, L.pidx, nparts, L.nan, result, st);
 }

@@ -322,22 +322,22 @@ __global__ __launch_bounds__(256) void refine_finish_kernel(const RefinePoint *_
 }
 
 struct Layout {
-    int64_t Pp, xsc_off, ks_off, vt_off, wt_off, rec_off, trial_off, total;
+    double *xsc, *ks, *vt, *wt;
+    RefinePoint *rec;   // the stepping state: null in the workspace of the gradient call
+    double *trial;
+    int64_t Pp, total;
+    Layout(void *work, int64_t Np, int64_t P, bool stepping) {
+        Carver c(work);
+        Pp = align_up(P, 64);
+        xsc = c.take<double>(Np * GPBO_MAX_D);
+        ks = c.take<double>(Pp * Np);
+        vt = c.take<double>(Pp * Np);
+        wt = c.take<double>(Pp * Np);
+        rec = stepping ? c.take<RefinePoint>(Pp) : nullptr;
+        trial = stepping ? c.take<double>(Pp * GPBO_MAX_D) : nullptr;
+        total = c.total();
+    }
 };
-
-Layout layout(int64_t Np, int64_t P, bool stepping) {
-    Layout L;
-    L.Pp = align_up(P, 64);
-    int64_t o = 0;
-    L.xsc_off = o;   o += align_up(8 * Np * GPBO_MAX_D, 256);
-    L.ks_off = o;    o += align_up(8 * L.Pp * Np, 256);
-    L.vt_off = o;    o += align_up(8 * L.Pp * Np, 256);
-    L.wt_off = o;    o += align_up(8 * L.Pp * Np, 256);
-    L.rec_off = o;   if (stepping) o += align_up((int64_t)sizeof(RefinePoint) * L.Pp, 256);
-    L.trial_off = o; if (stepping) o += align_up(8 * L.Pp * GPBO_MAX_D, 256);
-    L.total = o;
-    return L;
-}
 
 bool sizes_ok(int64_t Np, int64_t P) { return np_ok(Np) && Np <= (1 << 20) && P >= 1 && P <= GPBO_REFINE_MAX_P; }
 
@@ -394,16 +394,11 @@ int evaluate(const Eval &e, const double *pts, int mode, double step0, RefinePoi
 }
 
 int make_eval(Eval *e, const Layout &L, const double *X, int64_t N, int64_t Np, int64_t P, int32_t d, const double *ls_host,
-              const double *U, const double *alpha, double prior_var, int32_t acq_kind, double p0, double p1, void *work,
-              void *stream) {
-    char *w = reinterpret_cast<char *>(work);
+              const double *U, const double *alpha, double prior_var, int32_t acq_kind, double p0, double p1, void *stream) {
     e->X = X; e->U = U; e->alpha = alpha;
     e->N = (int)N; e->Np = (int)Np; e->P = (int)P; e->Pp = (int)L.Pp; e->d = (int)d;
     e->prior_var = prior_var; e->p0 = p0; e->p1 = p1; e->kind = (int)acq_kind;
-    e->Xsc = reinterpret_cast<double *>(w + L.xsc_off);
-    e->Ks = reinterpret_cast<double *>(w + L.ks_off);
-    e->Vt = reinterpret_cast<double *>(w + L.vt_off);
-    e->Wt = reinterpret_cast<double *>(w + L.wt_off);
+    e->Xsc = L.xsc; e->Ks = L.ks; e->Vt = L.vt; e->Wt = L.wt;
     e->st = gpbo_stream(stream);
     return gpbo_scale_points_launch(X, N, Np, d, ls_host, e->Xsc, nullptr, stream);
 }
@@ -420,12 +415,12 @@ bool model_ok(const double *X, int64_t N, int64_t Np, int32_t d, const double *l
 
 extern "C" int64_t gpbo_posterior_grad_workspace_bytes(int64_t Np, int64_t P) {
     if (!sizes_ok(Np, P)) return GPBO_ERR_ARG;
-    return layout(Np, P, false).total;
+    return Layout(nullptr, Np, P, false).total;
 }
 
 extern "C" int64_t gpbo_refine_workspace_bytes(int64_t Np, int64_t P) {
     if (!sizes_ok(Np, P)) return GPBO_ERR_ARG;
-    return layout(Np, P, true).total;
+    return Layout(nullptr, Np, P, true).total;
 }
 
 extern "C" int gpbo_posterior_grad_f64(const double *Xq, int64_t P, const double *X, int64_t N, int64_t Np, int32_t d,
@@ -434,11 +429,11 @@ extern "C" int gpbo_posterior_grad_f64(const double *Xq, int64_t P, const double
                                        double *acq_out, double *dmu_out, double *dsigma_out, double *dacq_out, void *work,
                                        int64_t work_bytes, void *stream) {
     if (!Xq || !work || !model_ok(X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, P)) return GPBO_ERR_ARG;
-    const Layout L = layout(Np, P, false);
+    const Layout L(work, Np, P, false);
     if (work_bytes < L.total || !aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
     Eval e;
     if (!make_box(ls_host, nullptr, nullptr, d, &e.box)) return GPBO_ERR_ARG;
-    int rc = make_eval(&e, L, X, N, Np, P, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, work, stream);
+    int rc = make_eval(&e, L, X, N, Np, P, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, stream);
     if (rc != GPBO_OK) return rc;
     return evaluate(e, Xq, MODE_EVAL, 0.0, nullptr, nullptr, mu_out, sigma_out, acq_out, dmu_out, dsigma_out, dacq_out);
 }
@@ -451,24 +446,21 @@ extern "C" int gpbo_refine_f64(double *Xq, int64_t P, const double *lower_host, 
     if (!Xq || !lower_host || !upper_host || !result || !work) return GPBO_ERR_ARG;
     if (!model_ok(X, N, Np, d, ls_host, U, alpha, prior_var, acq_kind, P)) return GPBO_ERR_ARG;
     if (iters < 0 || iters > 1000 || !(step0 > 0.0) || !std::isfinite(step0)) return GPBO_ERR_ARG;
-    const Layout L = layout(Np, P, true);
+    const Layout L(work, Np, P, true);
     Eval e;
     if (!make_box(ls_host, lower_host, upper_host, d, &e.box)) return GPBO_ERR_ARG;
     if (work_bytes < L.total || !aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
-    int rc = make_eval(&e, L, X, N, Np, P, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, work, stream);
+    int rc = make_eval(&e, L, X, N, Np, P, d, ls_host, U, alpha, prior_var, acq_kind, p0, p1, stream);
     if (rc != GPBO_OK) return rc;
-    char *w = reinterpret_cast<char *>(work);
-    RefinePoint *rec = reinterpret_cast<RefinePoint *>(w + L.rec_off);
-    double *trial = reinterpret_cast<double *>(w + L.trial_off);
     hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((P * d + 255) / 256)), dim3(256), 0, e.st, Xq, (int)P, (int)d, e.box,
-                       trial);
+                       L.trial);
     GPBO_CHECK_LAUNCH();
     for (int it = 0; it <= iters; ++it) {
-        rc = evaluate(e, trial, it == 0 ? MODE_START : MODE_STEP, step0, rec, trial, nullptr, nullptr, nullptr, nullptr,
+        rc = evaluate(e, L.trial, it == 0 ? MODE_START : MODE_STEP, step0, L.rec, L.trial, nullptr, nullptr, nullptr, nullptr,
                       nullptr, nullptr);
         if (rc != GPBO_OK) return rc;
     }
-    hipLaunchKernelGGL(refine_finish_kernel, dim3(1), dim3(256), 0, e.st, rec, (int)P, (int)d, e.box, Xq, acq_out, acq0_out,
+    hipLaunchKernelGGL(refine_finish_kernel, dim3(1), dim3(256), 0, e.st, L.rec, (int)P, (int)d, e.box, Xq, acq_out, acq0_out,
                        accepted_out, pg_out, result);
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;

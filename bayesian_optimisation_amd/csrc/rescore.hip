@@ -252,30 +252,7 @@ __global__ __launch_bounds__(SB) void rescore_finish_kernel(const double *__rest
     }
 }
 
-struct RescoreLayout {
-    int64_t part_off, L_off, count_off, list_off, rows_off, mu_off, sig_off, acq_off, out_off, post_off, post_bytes, total;
-};
-
 constexpr int SCREEN_BLOCKS = 1024;
-
-RescoreLayout rescore_layout(int64_t Np, int64_t cap, int64_t chunk64) {
-    RescoreLayout L;
-    int64_t off = 0;
-    L.part_off = off; off += align_up((int64_t)sizeof(double) * SCREEN_BLOCKS, 256);
-    L.L_off = off; off += 256;
-    L.count_off = off; off += 256;
-    L.out_off = off; off += 256;
-    L.list_off = off; off += align_up((int64_t)sizeof(int64_t) * cap, 256);
-    L.rows_off = off; off += align_up((int64_t)sizeof(double) * cap * GPBO_MAX_D, 256);
-    L.mu_off = off; off += align_up((int64_t)sizeof(double) * cap, 256);
-    L.sig_off = off; off += align_up((int64_t)sizeof(double) * cap, 256);
-    L.acq_off = off; off += align_up((int64_t)sizeof(double) * cap, 256);
-    L.post_off = off;
-    L.post_bytes = gpbo_posterior_workspace_bytes_split(Np, chunk64, cap, GPBO_RESCORE_SPLIT_MAX);
-    off += align_up(L.post_bytes, 256);
-    L.total = off;
-    return L;
-}
 
 // the pieces of a rescoring workspace
 struct RescoreWork {
@@ -284,21 +261,22 @@ struct RescoreWork {
     RescoreOut *out;
     int64_t *list;
     double *rows, *mu64, *sig64, *acq64;
-    void *post;
-    int64_t post_bytes;
-    RescoreWork(void *work, const RescoreLayout &L) {
-        char *w = reinterpret_cast<char *>(work);
-        part = reinterpret_cast<double *>(w + L.part_off);
-        Ldev = reinterpret_cast<double *>(w + L.L_off);
-        count = reinterpret_cast<unsigned long long *>(w + L.count_off);
-        out = reinterpret_cast<RescoreOut *>(w + L.out_off);
-        list = reinterpret_cast<int64_t *>(w + L.list_off);
-        rows = reinterpret_cast<double *>(w + L.rows_off);
-        mu64 = reinterpret_cast<double *>(w + L.mu_off);
-        sig64 = reinterpret_cast<double *>(w + L.sig_off);
-        acq64 = reinterpret_cast<double *>(w + L.acq_off);
-        post = w + L.post_off;
-        post_bytes = L.post_bytes;
+    void *post;   // the workspace of the column-split fp64 pass over at most cap candidates, post_bytes
+    int64_t post_bytes, total;
+    RescoreWork(void *work, int64_t Np, int64_t cap, int64_t chunk64) {
+        Carver c(work);
+        part = c.take<double>(SCREEN_BLOCKS);
+        Ldev = static_cast<double *>(c.take_bytes(256));
+        count = static_cast<unsigned long long *>(c.take_bytes(256));
+        out = static_cast<RescoreOut *>(c.take_bytes(256));
+        list = c.take<int64_t>(cap);
+        rows = c.take<double>(cap * GPBO_MAX_D);
+        mu64 = c.take<double>(cap);
+        sig64 = c.take<double>(cap);
+        acq64 = c.take<double>(cap);
+        post_bytes = gpbo_posterior_workspace_bytes_split(Np, chunk64, cap, GPBO_RESCORE_SPLIT_MAX);
+        post = c.take_bytes(post_bytes);
+        total = c.total();
     }
 };
 
@@ -325,7 +303,7 @@ int score_list(const double *Xs, const GpModel &gp, const Acquisition &acq, int6
 
 extern "C" int64_t gpbo_rescore_workspace_bytes(int64_t Np, int64_t cap, int64_t chunk64) {
     if (cap < 1 || gpbo_posterior_workspace_bytes(Np, chunk64, cap) < 0) return GPBO_ERR_ARG;
-    return rescore_layout(Np, cap, chunk64).total;
+    return RescoreWork(nullptr, Np, cap, chunk64).total;
 }
 
 extern "C" int gpbo_rescore_f64(const double *Xs, int64_t M, const double *mu, const double *var32, const double *X,
@@ -339,12 +317,11 @@ extern "C" int gpbo_rescore_f64(const double *Xs, int64_t M, const double *mu, c
         return GPBO_ERR_ARG;
     if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
     if (gpbo_posterior_workspace_bytes(Np, chunk64, cap) < 0 || !aligned_to(work, 256)) return GPBO_ERR_ARG;
-    const RescoreLayout L = rescore_layout(Np, cap, chunk64);
-    if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
+    const RescoreWork W(work, Np, cap, chunk64);
+    if (work_bytes < W.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
     const GpModel gp = {X, N, Np, d, ls_host, U, alpha, prior_var};
     const Acquisition acq = {acq_kind, p0, p1};
-    const RescoreWork W(work, L);
 
     int64_t nblk = (M + SB - 1) / SB;
     if (nblk > SCREEN_BLOCKS) nblk = SCREEN_BLOCKS;
@@ -410,12 +387,11 @@ extern "C" int gpbo_bound_select_f64(const double *Xs, int64_t M, const double *
     if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
     if (acq_kind == GPBO_ACQ_LCB && !(p0 >= 0.0)) return GPBO_ERR_ARG;   // the bound needs an acquisition that increases with sigma
     if (gpbo_posterior_workspace_bytes(Np, chunk64, cap) < 0 || !aligned_to(work, 256)) return GPBO_ERR_ARG;
-    const RescoreLayout L = rescore_layout(Np, cap, chunk64);
-    if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
+    const RescoreWork W(work, Np, cap, chunk64);
+    if (work_bytes < W.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
     const GpModel gp = {X, N, Np, d, ls_host, U, alpha, prior_var};
     const Acquisition acq = {acq_kind, p0, p1};
-    const RescoreWork W(work, L);
     double *const part = W.part, *const Ldev = W.Ldev, *const mu64 = W.mu64, *const sig64 = W.sig64, *const acq64 = W.acq64;
     unsigned long long *const count = W.count;
     RescoreOut *const out = W.out;

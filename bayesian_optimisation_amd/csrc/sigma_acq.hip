@@ -523,8 +523,33 @@ Helper *helper_for_current_device() {
 
 static_assert(BN == GPBO_NPAD, "f64_column_groups (host_driver.h) counts column blocks of GPBO_NPAD");
 
+// The workspace of the fp64 pass.  Two chunk buffers when there is more than one chunk (K(X*,X) of chunk c+1 can be built on a
+// helper stream while the variance kernel of chunk c runs); with one chunk kst[1] / mup[1] alias the only buffer.
 struct PosteriorLayout {
-    int64_t kst_off[2], mup_off[2], xsc_off, prep_off, pval_off, pidx_off, nan_off, ssp_off, total, nparts_cap;
+    double *kst[2], *mup[2], *xsc;
+    void *prep;   // prefix-bound route (kstar_mfma.hip)
+    double *pval;
+    int64_t *pidx;
+    unsigned long long *nan;
+    double *ssp;
+    int64_t total, nparts_cap;
+    PosteriorLayout(void *work, int64_t Np, int64_t chunk, int64_t M, int split_max = 1) {
+        Carver c(work);
+        const int64_t nchunks = (M + chunk - 1) / chunk;
+        nparts_cap = nchunks * (chunk / BM);
+        for (int b = 0; b < (nchunks > 1 ? 2 : 1); ++b) {
+            kst[b] = c.take<double>(Np * chunk);
+            mup[b] = c.take<double>((Np / GPBO_KS_SLICE) * chunk);
+        }
+        if (nchunks == 1) { kst[1] = kst[0]; mup[1] = mup[0]; }
+        xsc = c.take<double>(Np * GPBO_MAX_D);
+        prep = c.take_bytes(gpbo_kstar_mfma_prep_bytes(Np));
+        pval = c.take<double>(nparts_cap);
+        pidx = c.take<int64_t>(nparts_cap);
+        nan = c.take<unsigned long long>(32);   // 256 bytes
+        ssp = c.take<double>((split_max > 16 ? split_max : 16) * chunk);
+        total = c.total();
+    }
 };
 
 // number of column-split workgroups per candidate tile for a launch of nblk tiles (1 = the plain kernel)
@@ -535,31 +560,6 @@ int split_factor(int64_t nblk, int64_t nJ, int split_max) {
     if (S > split_max) S = split_max;
     return S < 1 ? 1 : (int)S;
 }
-
-PosteriorLayout posterior_layout(int64_t Np, int64_t chunk, int64_t M, int split_max = 1) {
-    PosteriorLayout L;
-    const int64_t nchunks = (M + chunk - 1) / chunk;
-    L.nparts_cap = nchunks * (chunk / BM);
-    int64_t off = 0;
-    // two chunk buffers when there is more than one chunk: K(X*,X) of chunk c+1 is built on a helper
-    // stream while the variance kernel of chunk c runs
-    const int nbuf = nchunks > 1 ? 2 : 1;
-    for (int b = 0; b < 2; ++b) {
-        L.kst_off[b] = off; if (b < nbuf) off += align_up((int64_t)sizeof(double) * Np * chunk, 256);
-        L.mup_off[b] = off; if (b < nbuf) off += align_up((int64_t)sizeof(double) * (Np / GPBO_KS_SLICE) * chunk, 256);
-    }
-    if (nbuf == 1) { L.kst_off[1] = L.kst_off[0]; L.mup_off[1] = L.mup_off[0]; }
-    L.xsc_off = off; off += align_up((int64_t)sizeof(double) * Np * GPBO_MAX_D, 256);
-    L.prep_off = off; off += align_up(gpbo_kstar_mfma_prep_bytes(Np), 256);   // prefix-bound route (kstar_mfma.hip)
-    L.pval_off = off; off += align_up((int64_t)sizeof(double) * L.nparts_cap, 256);
-    L.pidx_off = off; off += align_up((int64_t)sizeof(int64_t) * L.nparts_cap, 256);
-    L.nan_off = off; off += 256;
-    L.ssp_off = off;
-    off += align_up((int64_t)sizeof(double) * (split_max > 16 ? split_max : 16) * chunk, 256);
-    L.total = off;
-    return L;
-}
-
 
 // ================================================================================================
 // q-point Monte-Carlo Expected Improvement (BASELINE config 5; not in the reference).
@@ -686,28 +686,31 @@ __global__ __launch_bounds__(256) void qei_kernel(const double *__restrict__ G, 
 }
 
 struct QeiLayout {
-    int64_t kst_off, mup_off, xsc_off, v_off, mu_off, spv_off, spi_off, pval_off, pidx_off, nan_off, ssp_off, total;
+    double *kst, *mup, *xsc, *v, *mu, *spv;
+    int64_t *spi;
+    double *pval;
+    int64_t *pidx;
+    unsigned long long *nan;
+    double *ssp;
+    int64_t total;
+    QeiLayout(void *work, int64_t Np, int64_t chunk, int64_t M) {
+        Carver c(work);
+        const int64_t nchunks = (M + chunk - 1) / chunk;
+        kst = c.take<double>(Np * chunk);
+        mup = c.take<double>((Np / GPBO_KS_SLICE) * chunk);
+        xsc = c.take<double>(Np * GPBO_MAX_D);
+        v = c.take<double>(64 * (chunk / 8) * 16 * WQ);   // Gram blocks: <= 16 x WQ partials
+        mu = c.take<double>(chunk);
+        spv = c.take<double>(chunk / BM);
+        spi = c.take<int64_t>(chunk / BM);
+        const int64_t nparts = nchunks * ((chunk / QQ + 3) / 4);
+        pval = c.take<double>(nparts);
+        pidx = c.take<int64_t>(nparts);
+        nan = c.take<unsigned long long>(32);   // 256 bytes: the reported count and the single-point pass's scratch count
+        ssp = c.take<double>(16 * chunk);       // column-group partials (large calls)
+        total = c.total();
+    }
 };
-
-QeiLayout qei_layout(int64_t Np, int64_t chunk, int64_t M) {
-    QeiLayout L;
-    const int64_t nchunks = (M + chunk - 1) / chunk;
-    int64_t off = 0;
-    L.kst_off = off; off += align_up((int64_t)sizeof(double) * Np * chunk, 256);
-    L.mup_off = off; off += align_up((int64_t)sizeof(double) * (Np / GPBO_KS_SLICE) * chunk, 256);
-    L.xsc_off = off; off += align_up((int64_t)sizeof(double) * Np * GPBO_MAX_D, 256);
-    L.v_off = off; off += align_up((int64_t)sizeof(double) * 64 * (chunk / 8) * 16 * WQ, 256);   // Gram blocks: <= 16 x WQ partials
-    L.mu_off = off; off += align_up((int64_t)sizeof(double) * chunk, 256);
-    L.spv_off = off; off += align_up((int64_t)sizeof(double) * (chunk / BM), 256);
-    L.spi_off = off; off += align_up((int64_t)sizeof(int64_t) * (chunk / BM), 256);
-    const int64_t nparts = nchunks * ((chunk / QQ + 3) / 4);
-    L.pval_off = off; off += align_up((int64_t)sizeof(double) * nparts, 256);
-    L.pidx_off = off; off += align_up((int64_t)sizeof(int64_t) * nparts, 256);
-    L.nan_off = off; off += 256;
-    L.ssp_off = off; off += align_up((int64_t)sizeof(double) * 16 * chunk, 256);  // column-group partials (large calls)
-    L.total = off;
-    return L;
-}
 
 // One variance launch of the acquisition driver: the kernel's arguments once, whichever variant is launched.
 struct SigmaLaunch {
@@ -832,7 +835,11 @@ extern "C" int gpbo_posterior_prefix_f64(const double *Xs, int64_t M, const doub
 
 int64_t gpbo_posterior_workspace_bytes_split(int64_t Np, int64_t chunk, int64_t M, int split_max) {
     if (!np_ok(Np) || !chunk_ok(chunk) || M < 1) return GPBO_ERR_ARG;
-    return posterior_layout(Np, chunk, M, split_max).total;
+    return PosteriorLayout(nullptr, Np, chunk, M, split_max).total;
+}
+
+const double *gpbo_posterior_chunk_image(const void *work, int64_t Np, int64_t chunk, int64_t M) {
+    return PosteriorLayout(const_cast<void *>(work), Np, chunk, M).kst[0];
 }
 
 // split_max > 1: launches of fewer than 128 candidate tiles are split over the column blocks of V (the re-scoring
@@ -854,17 +861,9 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
     if (!chunk_ok(chunk)) return GPBO_ERR_ARG;
     if (!acq_kind_ok(acq.kind)) return GPBO_ERR_ARG;
     if (!aligned_to(work, 256) || !aligned_to(U, 16)) return GPBO_ERR_ARG;
-    const PosteriorLayout L = posterior_layout(Np, chunk, M, split_max);
+    const PosteriorLayout L(work, Np, chunk, M, split_max);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    double *ss_part = reinterpret_cast<double *>(w + L.ssp_off);
-    double *KsT[2] = {reinterpret_cast<double *>(w + L.kst_off[0]), reinterpret_cast<double *>(w + L.kst_off[1])};
-    double *mu_part[2] = {reinterpret_cast<double *>(w + L.mup_off[0]), reinterpret_cast<double *>(w + L.mup_off[1])};
-    double *Xsc = reinterpret_cast<double *>(w + L.xsc_off);
-    double *part_val = reinterpret_cast<double *>(w + L.pval_off);
-    int64_t *part_idx = reinterpret_cast<int64_t *>(w + L.pidx_off);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
     // prefix-bound route: K(X*,X) with the pair distances on the matrix cores and the mean reported from below by its error
     // bound (kstar_mfma.hip; GPBO_PREFIX_VALU=1: the difference-form kernel instead, for A/B runs)
     static const bool prefix_valu = env_flag("GPBO_PREFIX_VALU");
@@ -874,15 +873,14 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
     const bool anyd = d > GPBO_MAX_D;   // slow path of the fp64 route: no unrolled registers, no pre-scaled copy
     if (anyd && (n_prefix > 0 || d > GPBO_MAX_D_ANY)) return GPBO_ERR_ARG;
     if (anyd) {
-        if (hipMemsetAsync(nan_count, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
+        if (hipMemsetAsync(L.nan, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
     } else {
         // observations / (ls sqrt 2), once per call; the same launch clears the NaN counter
-        int rc0 = gpbo_scale_points_launch(X, N, Np, d, ls_host, Xsc, nan_count, stream);
+        int rc0 = gpbo_scale_points_launch(X, N, Np, d, ls_host, L.xsc, L.nan, stream);
         if (rc0 != GPBO_OK) return rc0;
     }
-    void *prep_buf = w + L.prep_off;
     if (kstar_mfma) {
-        int rc0 = gpbo_kstar_mfma_prep(X, N, Np, d, ls_host, alpha, prep_buf, stream);
+        int rc0 = gpbo_kstar_mfma_prep(X, N, Np, d, ls_host, alpha, L.prep, stream);
         if (rc0 != GPBO_OK) return rc0;
     }
 
@@ -918,19 +916,19 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
             // (unnormalised inputs), is amplified by |U| and would need a data-dependent variance pad; with the plain
             // pass's own entries |v[:J]|^2 is a partial sum of the very squares the plain pass adds up, so the bound
             // holds for any inputs.  Costs n_prefix / N of the fp64-VALU kernel: 6 % at N / 16.
-            rc = gpbo_kstar_mu_mfma(Xs + s * d, Mc, N, Np, d, ls_host, alpha, prep_buf, KsT[b], chunk, mu_part[b], 0, ks);
+            rc = gpbo_kstar_mu_mfma(Xs + s * d, Mc, N, Np, d, ls_host, alpha, L.prep, L.kst[b], chunk, L.mup[b], 0, ks);
             if (rc != GPBO_OK) return rc;
             const int64_t nrow = (N < n_prefix) ? N : n_prefix;
             // (its mean partials - of the first n_prefix observations only - are not wanted: they go to rows of the K*^T
             //  slab that the prefix mode neither writes nor reads, [n_prefix, n_prefix + n_prefix / 64))
-            rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, Xsc, nrow, n_prefix, d, ls_host, GPBO_KERNEL_SE, alpha, 0.0, idx_offset + s,
-                                    KsT[b], chunk, KsT[b] + n_prefix * chunk, n_prefix, ks);
+            rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, L.xsc, nrow, n_prefix, d, ls_host, GPBO_KERNEL_SE, alpha, 0.0, idx_offset + s,
+                                    L.kst[b], chunk, L.kst[b] + n_prefix * chunk, n_prefix, ks);
         } else if (anyd) {
-            rc = gpbo_kstar_mu_anyd(Xs + s * d, Mc, X, N, Np, d, ls_host, alpha, diag_add, idx_offset + s, KsT[b], chunk,
-                                    mu_part[b], ks);
+            rc = gpbo_kstar_mu_anyd(Xs + s * d, Mc, X, N, Np, d, ls_host, alpha, diag_add, idx_offset + s, L.kst[b], chunk,
+                                    L.mup[b], ks);
         } else {
-            rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, Xsc, N, Np, d, ls_host, gp.kernel, alpha, diag_add, idx_offset + s, KsT[b],
-                                    chunk, mu_part[b], n_prefix ? n_prefix : Np, ks);
+            rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, L.xsc, N, Np, d, ls_host, gp.kernel, alpha, diag_add, idx_offset + s, L.kst[b],
+                                    chunk, L.mup[b], n_prefix ? n_prefix : Np, ks);
         }
         if (rc != GPBO_OK) return rc;
         if (hp && hipEventRecord(hp->kdone[b], ks) != hipSuccess) return GPBO_ERR_LAUNCH;
@@ -957,21 +955,21 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
         // same box: 543 -> 509 ms per step with 8 groups (16: 512), the variance launches 32.9 -> 30.7 ms.
         const int xg = (S == 1 && n_prefix == 0) ? f64_column_groups(M, Np) : 1;
         const DenseOut o = out.at(s);
-        SigmaLaunch a = {dim3((unsigned)nblk), KsT[b], chunk, U, (int)Np, mu_part[b], nsl, Mc, gp.prior_var, acq,
-                         idx_offset + s, o, part_val + nparts, part_idx + nparts, nan_count,
+        SigmaLaunch a = {dim3((unsigned)nblk), L.kst[b], chunk, U, (int)Np, L.mup[b], nsl, Mc, gp.prior_var, acq,
+                         idx_offset + s, o, L.pval + nparts, L.pidx + nparts, L.nan,
                          // (the stamps of a stamped variant go to the other chunk buffer, free during the last chunk)
-                         (c == nchunks - 1 && nchunks > 1) ? KsT[(c + 1) & 1] : nullptr, nullptr, 1, (int)nblk,
+                         (c == nchunks - 1 && nchunks > 1) ? L.kst[(c + 1) & 1] : nullptr, nullptr, 1, (int)nblk,
                          (int)(n_prefix / BN)};
-        if (xg > 1 || S > 1) {   // partial sums to ss_part, the epilogue in split_finish_kernel
+        if (xg > 1 || S > 1) {   // partial sums to L.ssp, the epilogue in split_finish_kernel
             a.grid = (xg > 1) ? dim3((unsigned)((nblk + 7) / 8 * 8 * xg)) : dim3((unsigned)nblk, (unsigned)S);
             a.out = {nullptr, nullptr, nullptr, nullptr};
-            a.ss_part = ss_part;
+            a.ss_part = L.ssp;
             a.xg = xg;
             if (xg > 1) launch_sigma_variant(a, st);
             else launch_sigma<0>(a, st);
-            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, xg > 1 ? xg : S, chunk,
-                               mu_part[b], nsl, Mc, gp.prior_var, (int)acq.kind, acq.p0, acq.p1, idx_offset + s, o.mu, o.sigma,
-                               o.acq, (double *)nullptr, part_val + nparts, part_idx + nparts, nan_count,
+            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, L.ssp, xg > 1 ? xg : S, chunk,
+                               L.mup[b], nsl, Mc, gp.prior_var, (int)acq.kind, acq.p0, acq.p1, idx_offset + s, o.mu, o.sigma,
+                               o.acq, (double *)nullptr, L.pval + nparts, L.pidx + nparts, L.nan,
                                n_prefix ? GPBO_BOUND_VAR_PAD : 0.0);
         } else {
             launch_sigma_variant(a, st);
@@ -985,35 +983,48 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
         }
         nparts += nblk;
     }
-    return gpbo_launch_argmax_finish(part_val, part_idx, nparts, nan_count, result, st);
+    return gpbo_launch_argmax_finish(L.pval, L.pidx, nparts, L.nan, result, st);
 }
 
-extern "C" int64_t gpbo_acq_workspace_bytes(void) { return 1024 * 16 + 256; }
+namespace {
+struct AcqLayout {   // partial records of at most 1024 workgroups
+    double *pval;
+    int64_t *pidx;
+    unsigned long long *nan;
+    int64_t total;
+    explicit AcqLayout(void *work) {
+        Carver c(work);
+        pval = c.take<double>(1024);
+        pidx = c.take<int64_t>(1024);
+        nan = c.take<unsigned long long>(32);   // 256 bytes
+        total = c.total();
+    }
+};
+}  // namespace
+
+extern "C" int64_t gpbo_acq_workspace_bytes(void) { return AcqLayout(nullptr).total; }
 
 extern "C" int gpbo_acq_argmax_f64(const double *mu, const double *sigma, int64_t M, int32_t acq_kind, double p0,
                                    double p1, int64_t idx_offset, double *acq_out, gpbo_result *result, void *work,
                                    int64_t work_bytes, void *stream) {
     if (!mu || !sigma || !result || !work || M < 1) return GPBO_ERR_ARG;
     if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
-    if (work_bytes < gpbo_acq_workspace_bytes()) return GPBO_ERR_WORKSPACE;
+    const AcqLayout L(work);
+    if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    double *part_val = reinterpret_cast<double *>(w);
-    int64_t *part_idx = reinterpret_cast<int64_t *>(w + 1024 * 8);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + 1024 * 16);
-    if (hipMemsetAsync(nan_count, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
+    if (hipMemsetAsync(L.nan, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
     int64_t nblk = (M + 255) / 256;
     if (nblk > 1024) nblk = 1024;
     hipLaunchKernelGGL(acq_argmax_kernel, dim3((unsigned)nblk), dim3(256), 0, st, mu, sigma, M, (int)acq_kind, p0, p1,
-                       idx_offset, acq_out, part_val, part_idx, nan_count);
-    hipLaunchKernelGGL(argmax_finish_kernel, dim3(1), dim3(256), 0, st, part_val, part_idx, nblk, nan_count, result);
+                       idx_offset, acq_out, L.pval, L.pidx, L.nan);
+    hipLaunchKernelGGL(argmax_finish_kernel, dim3(1), dim3(256), 0, st, L.pval, L.pidx, nblk, L.nan, result);
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
 }
 
 extern "C" int64_t gpbo_qei_workspace_bytes(int64_t Np, int64_t chunk, int64_t M) {
     if (!np_ok(Np) || !chunk_ok(chunk) || M < 1) return GPBO_ERR_ARG;
-    return qei_layout(Np, chunk, M).total;
+    return QeiLayout(nullptr, Np, chunk, M).total;
 }
 
 extern "C" int gpbo_posterior_qei_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
@@ -1025,29 +1036,15 @@ extern "C" int gpbo_posterior_qei_f64(const double *Xs, int64_t M, const double 
     if (M < QQ || M % QQ || N < 1 || Np != gpbo_padded_n(N) || S < 1 || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
     if (!chunk_ok(chunk)) return GPBO_ERR_ARG;
     if (!aligned_to(work, 256) || !aligned_to(U, 16)) return GPBO_ERR_ARG;
-    const QeiLayout L = qei_layout(Np, chunk, M);
+    const QeiLayout L(work, Np, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     QeiLs ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.il2[k] = 0.0;
-    for (int k = 0; k < d; ++k) {
-        if (!(ls_host[k] > 0.0)) return GPBO_ERR_ARG;
-        ls.il2[k] = 1.0 / (ls_host[k] * ls_host[k]);
-    }
+    if (!length_scale_scalings(ls_host, d, ls.il2, nullptr)) return GPBO_ERR_ARG;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    double *KsT = reinterpret_cast<double *>(w + L.kst_off);
-    double *mu_part = reinterpret_cast<double *>(w + L.mup_off);
-    double *Xsc = reinterpret_cast<double *>(w + L.xsc_off);
-    double *Vb = reinterpret_cast<double *>(w + L.v_off);
-    double *mu = reinterpret_cast<double *>(w + L.mu_off);
-    double *spv = reinterpret_cast<double *>(w + L.spv_off);
-    int64_t *spi = reinterpret_cast<int64_t *>(w + L.spi_off);
-    double *part_val = reinterpret_cast<double *>(w + L.pval_off);
-    int64_t *part_idx = reinterpret_cast<int64_t *>(w + L.pidx_off);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
-    unsigned long long *nan_scratch = nan_count + 8;  // NaN count of the single-point pass (not reported)
-    if (hipMemsetAsync(nan_count, 0, 256, st) != hipSuccess) return GPBO_ERR_LAUNCH;
-    int rc = gpbo_scale_points_f64(X, N, Np, d, ls_host, Xsc, stream);
+    unsigned long long *nan_scratch = L.nan + 8;  // NaN count of the single-point pass (not reported)
+    if (hipMemsetAsync(L.nan, 0, 256, st) != hipSuccess) return GPBO_ERR_LAUNCH;
+    int rc = gpbo_scale_points_f64(X, N, Np, d, ls_host, L.xsc, stream);
     if (rc != GPBO_OK) return rc;
     int64_t nparts = 0;
     ProfileRecorder slots(prof);
@@ -1056,7 +1053,7 @@ extern "C" int gpbo_posterior_qei_f64(const double *Xs, int64_t M, const double 
         // one profile slot per chunk: kbegin | K(X*,X) | begin | variance launch (+ its finish) | end | qEI launch | qend
         // (the qEI launch lies between a slot's end and the next K(X*,X) launch: no chaining)
         if (!slots.kstar(st, false)) return GPBO_ERR_LAUNCH;
-        rc = gpbo_kstar_mu_f64(Xs + s * d, Mc, Xsc, N, Np, d, ls_host, alpha, 0.0, 0, KsT, chunk, mu_part, stream);
+        rc = gpbo_kstar_mu_f64(Xs + s * d, Mc, L.xsc, N, Np, d, ls_host, alpha, 0.0, 0, L.kst, chunk, L.mup, stream);
         if (rc != GPBO_OK) return rc;
         if (!slots.begin(st)) return GPBO_ERR_LAUNCH;
         const int64_t nblk = (Mc + BM - 1) / BM;
@@ -1065,26 +1062,26 @@ extern "C" int gpbo_posterior_qei_f64(const double *Xs, int64_t M, const double 
         // leaves the Gram partials of its column blocks; the mean then comes from split_finish_kernel).
         const int xg = f64_column_groups(M, Np);
         const int gram_parts = xg * WQ;   // partial Gram blocks per batch: one per column group of waves and of workgroups
-        double *ss_part = xg > 1 ? reinterpret_cast<double *>(w + L.ssp_off) : nullptr;
+        double *ss_part = xg > 1 ? L.ssp : nullptr;
         const int64_t grid = xg > 1 ? (nblk + 7) / 8 * 8 * xg : nblk;
-        hipLaunchKernelGGL((sigma_acq_kernel<0, true>), dim3((unsigned)grid), dim3(NW * 64), 0, st, KsT, chunk, U, (int)Np, mu_part,
+        hipLaunchKernelGGL((sigma_acq_kernel<0, true>), dim3((unsigned)grid), dim3(NW * 64), 0, st, L.kst, chunk, U, (int)Np, L.mup,
                            (int)(Np / GPBO_KS_SLICE), Mc, prior_var, (int)GPBO_ACQ_LCB, 0.0, 0.0, (int64_t)0,
-                           xg > 1 ? (double *)nullptr : mu, (double *)nullptr, (double *)nullptr, spv, spi, nan_scratch, Vb,
+                           xg > 1 ? (double *)nullptr : L.mu, (double *)nullptr, (double *)nullptr, L.spv, L.spi, nan_scratch, L.v,
                            ss_part, xg, (int)nblk, 0);
         if (xg > 1)
-            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, xg, chunk, mu_part,
-                               (int)(Np / GPBO_KS_SLICE), Mc, prior_var, (int)GPBO_ACQ_LCB, 0.0, 0.0, (int64_t)0, mu,
-                               (double *)nullptr, (double *)nullptr, (double *)nullptr, spv, spi, nan_scratch, 0.0);
+            hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, st, ss_part, xg, chunk, L.mup,
+                               (int)(Np / GPBO_KS_SLICE), Mc, prior_var, (int)GPBO_ACQ_LCB, 0.0, 0.0, (int64_t)0, L.mu,
+                               (double *)nullptr, (double *)nullptr, (double *)nullptr, L.spv, L.spi, nan_scratch, 0.0);
         GPBO_CHECK_LAUNCH();
         if (!slots.end_open(st)) return GPBO_ERR_LAUNCH;
         const int64_t nbatch = Mc / QQ;
         const int64_t qblk = (nbatch + 3) / 4;
-        hipLaunchKernelGGL(qei_kernel, dim3((unsigned)qblk), dim3(256), 0, st, Vb, gram_parts, chunk / 8, mu, Xs + s * d, (int)d, ls, nbatch,
+        hipLaunchKernelGGL(qei_kernel, dim3((unsigned)qblk), dim3(256), 0, st, L.v, gram_parts, chunk / 8, L.mu, Xs + s * d, (int)d, ls, nbatch,
                            prior_var, f_best, xi, Z, (int)S, batch_offset + s / QQ, qei_out ? qei_out + s / QQ : nullptr,
-                           part_val + nparts, part_idx + nparts, nan_count);
+                           L.pval + nparts, L.pidx + nparts, L.nan);
         GPBO_CHECK_LAUNCH();
         if (!slots.qend(st, Mc)) return GPBO_ERR_LAUNCH;
         nparts += qblk;
     }
-    return gpbo_launch_argmax_finish(part_val, part_idx, nparts, nan_count, result, st);
+    return gpbo_launch_argmax_finish(L.pval, L.pidx, nparts, L.nan, result, st);
 }

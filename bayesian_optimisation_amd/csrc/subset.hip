@@ -434,21 +434,25 @@ __global__ void gather_obs_kernel(const double *__restrict__ X, int d, const int
     out[e] = (r >= 0 && r < n) ? X[r * d + (e % d)] : std::numeric_limits<double>::quiet_NaN();
 }
 
-struct OrderLayout {
-    int64_t mind_off, fps_off, slot_off, total;
-};
 constexpr int FPS_MAXG = 256;  // workgroups of a selection step at most
-
-OrderLayout order_layout(int64_t N) {
-    OrderLayout L;
-    int64_t off = 0;
-    auto take = [&](int64_t bytes) { const int64_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    L.mind_off = take((int64_t)sizeof(double) * N);
-    L.fps_off = take((int64_t)sizeof(FpsState) + (int64_t)FPS_MAXG * (sizeof(double) + sizeof(int64_t)) + 256);
-    L.slot_off = take((int64_t)sizeof(FpsSlot) * 2 * FPS_MAXW);
-    L.total = off;
-    return L;
-}
+struct OrderLayout {
+    double *mind;
+    FpsState *stt;   // the state block: FpsState, then the partial values and indices of the one-launch-per-member route
+    double *pval;
+    int64_t *pidx;
+    FpsSlot *slots;
+    int64_t total;
+    OrderLayout(void *work, int64_t N) {
+        Carver c(work);
+        mind = c.take<double>(N);
+        Carver state(c.take_bytes((int64_t)sizeof(FpsState) + (int64_t)FPS_MAXG * (sizeof(double) + sizeof(int64_t)) + 256));
+        stt = state.take<FpsState>(1);
+        pval = state.take<double>(FPS_MAXG);
+        pidx = state.take<int64_t>(FPS_MAXG);
+        slots = c.take<FpsSlot>(2 * FPS_MAXW);
+        total = c.total();
+    }
+};
 
 __global__ void gather_y_kernel(const double *__restrict__ y, const int64_t *__restrict__ perm, int64_t n, double *__restrict__ out) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -462,7 +466,7 @@ __global__ void gather_y_kernel(const double *__restrict__ y, const int64_t *__r
 
 extern "C" int64_t gpbo_fps_order_workspace_bytes(int64_t N) {
     if (N < 1) return GPBO_ERR_ARG;
-    return order_layout(N).total;
+    return OrderLayout(nullptr, N).total;
 }
 
 // 1 into *fell_back (device int32) when the last gpbo_fps_order_f64 on this workspace gave up its co-operative selection (a
@@ -474,8 +478,7 @@ __global__ void fps_status_kernel(const FpsState *__restrict__ stt, int32_t *__r
 
 extern "C" int gpbo_fps_order_status(const void *work, int64_t N, int32_t *fell_back, void *stream) {
     if (!work || !fell_back || N < 1 || ((uintptr_t)work & 255)) return GPBO_ERR_ARG;
-    const OrderLayout L = order_layout(N);
-    const FpsState *stt = reinterpret_cast<const FpsState *>(reinterpret_cast<const char *>(work) + L.fps_off);
+    const FpsState *stt = OrderLayout(const_cast<void *>(work), N).stt;
     hipLaunchKernelGGL(fps_status_kernel, dim3(1), dim3(1), 0, gpbo_stream(stream), stt, fell_back);
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
@@ -489,7 +492,7 @@ extern "C" int gpbo_fps_order_f64(const double *X, const double *y, int64_t N, i
     if (!X || !ls_host || !perm_out || !work || (yp_out && !y)) return GPBO_ERR_ARG;
     if (N < 1 || d < 1 || d > GPBO_MAX_D || J < 1 || J > N) return GPBO_ERR_ARG;
     if ((uintptr_t)work & 255) return GPBO_ERR_ARG;
-    const OrderLayout L = order_layout(N);
+    const OrderLayout L(work, N);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
     FpsLs ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.isc[k] = 0.0;
@@ -498,9 +501,8 @@ extern "C" int gpbo_fps_order_f64(const double *X, const double *y, int64_t N, i
         ls.isc[k] = 1.0 / ls_host[k];
     }
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    double *mind = reinterpret_cast<double *>(w + L.mind_off);
-    FpsState *stt = reinterpret_cast<FpsState *>(w + L.fps_off);
+    double *mind = L.mind;
+    FpsState *stt = L.stt;
     // Shape of the selection (see fps_coop_kernel): PTS points per thread, as many as 128 registers of coordinates hold
     // (8 up to d = 8, 4 above); one workgroup of 256 threads while it can hold the points, of 512 up to 4,096 (2,048)
     // points.  Beyond, workgroups of 512 threads share the points, EIGHT of them while 8 x 512 x pmax points suffice
@@ -541,7 +543,7 @@ extern "C" int gpbo_fps_order_f64(const double *X, const double *y, int64_t N, i
     const int64_t G = (N + (int64_t)th * pts - 1) / ((int64_t)th * pts);
     bool launched = false;
     if (G <= FPS_MAXW) {
-        FpsSlot *slots = reinterpret_cast<FpsSlot *>(w + L.slot_off);
+        FpsSlot *slots = L.slots;
         if (coop && hipMemsetAsync(slots, 0, sizeof(FpsSlot) * 2 * FPS_MAXW, st) != hipSuccess) return GPBO_ERR_LAUNCH;
         hipLaunchKernelGGL(fps_centroid_kernel, dim3(1), dim3(FT), 0, st, X, N, (int)d, ls, stt);
         const unsigned grid = coop ? (unsigned)(8 * G) : 1u;
@@ -568,9 +570,9 @@ extern "C" int gpbo_fps_order_f64(const double *X, const double *y, int64_t N, i
         hipLaunchKernelGGL(fps_extend_kernel, dim3(1), dim3(FT), 0, st, N, J, N, mind, perm_out);
     }
     if (!launched) {
-        // one launch per member (the state block: FpsState, then the workgroups' partial values and indices)
-        double *pval = reinterpret_cast<double *>(w + L.fps_off + ((sizeof(FpsState) + 255) / 256) * 256);
-        int64_t *pidx = reinterpret_cast<int64_t *>(pval + FPS_MAXG);
+        // one launch per member (the workgroups' partial values and indices follow FpsState in its block)
+        double *pval = L.pval;
+        int64_t *pidx = L.pidx;
         int64_t G = (N + FG - 1) / FG;
         if (G > FPS_MAXG) G = FPS_MAXG;
         hipLaunchKernelGGL(fps_centroid_kernel, dim3(1), dim3(FT), 0, st, X, N, (int)d, ls, stt);

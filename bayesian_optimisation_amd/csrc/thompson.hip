@@ -247,41 +247,39 @@ __global__ __launch_bounds__(256) void thompson_resid_kernel(const double *__res
 }
 
 struct PathsLayout {
-    int64_t Sp, nblk, xsc_off, vt_off, om_off, wt_off, part_val_off, part_idx_off, nan_off, total;
+    double *xsc, *vt, *om, *wt, *part_val;
+    int64_t *part_idx;
+    unsigned long long *nan;
+    int64_t Sp, nblk, total;
+    PathsLayout(void *work, int64_t Np, int64_t M, int32_t F, int32_t S) {
+        Carver c(work);
+        Sp = padded_paths(S);
+        nblk = (M + TS_CANDS - 1) / TS_CANDS;
+        xsc = c.take<double>(Np * GPBO_MAX_D);
+        vt = c.take<double>(Np * Sp);
+        om = c.take<double>((int64_t)F * GPBO_MAX_D);
+        wt = c.take<double>((int64_t)F * Sp);
+        part_val = c.take<double>(Sp * nblk);
+        part_idx = c.take<int64_t>(Sp * nblk);
+        nan = c.take<unsigned long long>(Sp);
+        total = c.total();
+    }
 };
-
-PathsLayout paths_layout(int64_t Np, int64_t M, int32_t F, int32_t S) {
-    PathsLayout L;
-    L.Sp = padded_paths(S);
-    L.nblk = (M + TS_CANDS - 1) / TS_CANDS;
-    int64_t o = 0;
-    L.xsc_off = o;      o += align_up(8 * Np * GPBO_MAX_D, 256);
-    L.vt_off = o;       o += align_up(8 * Np * L.Sp, 256);
-    L.om_off = o;       o += align_up(8 * (int64_t)F * GPBO_MAX_D, 256);
-    L.wt_off = o;       o += align_up(8 * (int64_t)F * L.Sp, 256);
-    L.part_val_off = o; o += align_up(8 * L.Sp * L.nblk, 256);
-    L.part_idx_off = o; o += align_up(8 * L.Sp * L.nblk, 256);
-    L.nan_off = o;      o += align_up(8 * L.Sp, 256);
-    L.total = o;
-    return L;
-}
 
 struct WeightsLayout {
-    int64_t S64, a_off, b_off, out_off, paths_off, paths_bytes, total;
+    double *a, *b;   // G = g_s(X), then T = R U;  R, then V with its rows padded to 64
+    void *paths;     // the workspace of the inner paths call over the Np observations
+    int64_t S64, total;
+    WeightsLayout(void *work, int64_t Np, int32_t F, int32_t S) {
+        Carver c(work);
+        S64 = align_up(S, 64);
+        a = c.take<double>(S64 * Np);
+        b = c.take<double>(S64 * Np);
+        c.take_bytes(3 * align_up(8 * GPBO_TS_MAX_PATHS, 256));   // the arg-max outputs of the inner paths call (unused)
+        paths = c.take_bytes(PathsLayout(nullptr, Np, Np, F, S).total);
+        total = c.total();
+    }
 };
-
-WeightsLayout weights_layout(int64_t Np, int32_t F, int32_t S) {
-    WeightsLayout L;
-    L.S64 = align_up(S, 64);
-    int64_t o = 0;
-    L.a_off = o;     o += align_up(8 * L.S64 * Np, 256);   // G = g_s(X), then T = R U
-    L.b_off = o;     o += align_up(8 * L.S64 * Np, 256);   // R, then V with its rows padded to 64
-    L.out_off = o;   o += 3 * align_up(8 * GPBO_TS_MAX_PATHS, 256);   // the arg-max outputs of the inner paths call (unused)
-    L.paths_off = o; L.paths_bytes = paths_layout(Np, Np, F, S).total;
-    o += L.paths_bytes;
-    L.total = o;
-    return L;
-}
 
 bool draws_ok(int32_t F, int32_t S) { return F >= 1 && F <= GPBO_TS_MAX_FEATURES && S >= 1 && S <= GPBO_TS_MAX_PATHS; }
 bool sizes_ok(int64_t Np, int32_t F, int32_t S) { return np_ok(Np) && Np <= (1 << 20) && draws_ok(F, S); }
@@ -304,16 +302,8 @@ int run_paths(const double *Xs, int64_t M, const double *X, int64_t N, int64_t N
               const double *omega, const double *phase, const double *W, const double *V, int32_t F, int32_t S,
               int64_t idx_offset, double *f_out, int64_t ldf, int64_t *idx_out, double *val_out, int64_t *nan_out,
               bool want_argmax, void *work, void *stream) {
-    const PathsLayout L = paths_layout(Np, M, F, S);
+    const PathsLayout L(work, Np, M, F, S);
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    double *Xsc = reinterpret_cast<double *>(w + L.xsc_off);
-    double *Vt = reinterpret_cast<double *>(w + L.vt_off);
-    double *Om = reinterpret_cast<double *>(w + L.om_off);
-    double *Wt = reinterpret_cast<double *>(w + L.wt_off);
-    double *part_val = reinterpret_cast<double *>(w + L.part_val_off);
-    int64_t *part_idx = reinterpret_cast<int64_t *>(w + L.part_idx_off);
-    unsigned long long *nan_count = reinterpret_cast<unsigned long long *>(w + L.nan_off);
     TsScale sc;
     for (int k = 0; k < GPBO_MAX_D; ++k) sc.isc[k] = sc.tl[k] = 1.0;
     (void)length_scale_scalings(ls_host, d, nullptr, sc.isc);   // (cannot refuse: the arguments have been checked)
@@ -321,25 +311,25 @@ int run_paths(const double *Xs, int64_t M, const double *X, int64_t N, int64_t N
     const int Sp = (int)L.Sp, G = group_of(S);
     const int Nk = V ? (int)N : 0;
     if (V) {
-        int rc = gpbo_scale_points_launch(X, N, Np, d, ls_host, Xsc, nullptr, stream);
+        int rc = gpbo_scale_points_launch(X, N, Np, d, ls_host, L.xsc, nullptr, stream);
         if (rc != GPBO_OK) return rc;
     }
-    if (want_argmax && hipMemsetAsync(nan_count, 0, 8 * (size_t)Sp, st) != hipSuccess) return GPBO_ERR_LAUNCH;
+    if (want_argmax && hipMemsetAsync(L.nan, 0, 8 * (size_t)Sp, st) != hipSuccess) return GPBO_ERR_LAUNCH;
     int64_t prep = (int64_t)F * (Sp > d ? Sp : d);
     if ((int64_t)Nk * Sp > prep) prep = (int64_t)Nk * Sp;
     hipLaunchKernelGGL(thompson_prep_kernel, dim3((unsigned)((prep + 255) / 256)), dim3(256), 0, st, omega, W, V, (int)F, (int)S,
-                       Sp, (int)d, Nk, Np, sc, Om, Wt, Vt);
+                       Sp, (int)d, Nk, Np, sc, L.om, L.wt, L.vt);
     GPBO_CHECK_LAUNCH();
     const dim3 grid((unsigned)L.nblk, (unsigned)(Sp / G));
     const double amp = sqrt(2.0 / (double)F);
-#define CALL(DD)                                                                                                              \
-    launch_paths<DD>(G, grid, st, Xs, M, Xsc, Nk, sc, Vt, Om, phase, Wt, (int)F, (int)S, Sp, amp, idx_offset, f_out, ldf,        \
-                     want_argmax ? part_val : nullptr, part_idx, L.nblk, nan_count)
+#define CALL(DD)                                                                                                                  \
+    launch_paths<DD>(G, grid, st, Xs, M, L.xsc, Nk, sc, L.vt, L.om, phase, L.wt, (int)F, (int)S, Sp, amp, idx_offset, f_out, ldf, \
+                     want_argmax ? L.part_val : nullptr, L.part_idx, L.nblk, L.nan)
     GPBO_FOR_D(d, CALL)
 #undef CALL
     GPBO_CHECK_LAUNCH();
     if (!want_argmax) return GPBO_OK;
-    hipLaunchKernelGGL(thompson_finish_kernel, dim3((unsigned)S), dim3(256), 0, st, part_val, part_idx, L.nblk, nan_count,
+    hipLaunchKernelGGL(thompson_finish_kernel, dim3((unsigned)S), dim3(256), 0, st, L.part_val, L.part_idx, L.nblk, L.nan,
                        idx_out, val_out, nan_out);
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
@@ -355,12 +345,12 @@ bool model_ok(const double *X, int64_t N, int64_t Np, int32_t d, const double *l
 
 extern "C" int64_t gpbo_thompson_paths_workspace_bytes(int64_t Np, int64_t M, int32_t F, int32_t S) {
     if (!sizes_ok(Np, F, S) || M < 1 || M > TS_MAX_M) return GPBO_ERR_ARG;
-    return paths_layout(Np, M, F, S).total;
+    return PathsLayout(nullptr, Np, M, F, S).total;
 }
 
 extern "C" int64_t gpbo_thompson_weights_workspace_bytes(int64_t Np, int32_t F, int32_t S) {
     if (!sizes_ok(Np, F, S)) return GPBO_ERR_ARG;
-    return weights_layout(Np, F, S).total;
+    return WeightsLayout(nullptr, Np, F, S).total;
 }
 
 extern "C" int gpbo_thompson_paths_f64(const double *Xs, int64_t M, const double *X, int64_t N, int64_t Np, int32_t d,
@@ -370,7 +360,7 @@ extern "C" int gpbo_thompson_paths_f64(const double *Xs, int64_t M, const double
                                        void *stream) {
     if (!Xs || !omega || !phase || !W || !idx_out || !val_out || !nan_out || !work) return GPBO_ERR_ARG;
     if (!model_ok(X, N, Np, d, ls_host, F, S) || M < 1 || M > TS_MAX_M || (f_out && ldf < M)) return GPBO_ERR_ARG;
-    if (work_bytes < paths_layout(Np, M, F, S).total || !aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
+    if (work_bytes < PathsLayout(nullptr, Np, M, F, S).total || !aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
     return run_paths(Xs, M, X, N, Np, d, ls_host, omega, phase, W, V, F, S, idx_offset, f_out, ldf, idx_out, val_out, nan_out,
                      true, work, stream);
 }
@@ -384,14 +374,13 @@ extern "C" int gpbo_thompson_weights_f64(const double *X, const double *y, int64
     if (!aligned_to(U, 16)) return GPBO_ERR_ARG;   // the GEMM's B operand; refused here so that nothing is enqueued first
     const double kappa = jitter1 + jitter2;
     if (!(kappa >= 0.0) || !std::isfinite(kappa)) return GPBO_ERR_ARG;
-    const WeightsLayout L = weights_layout(Np, F, S);
+    const WeightsLayout L(work, Np, F, S);
     if (work_bytes < L.total || !aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
     hipStream_t st = gpbo_stream(stream);
-    char *w = reinterpret_cast<char *>(work);
-    double *A = reinterpret_cast<double *>(w + L.a_off), *B = reinterpret_cast<double *>(w + L.b_off);
+    double *A = L.a, *B = L.b;
     // G = g_s(X) [S x Np] (columns n >= N are not written and not read)
     int rc = run_paths(X, N, X, N, Np, d, ls_host, omega, phase, W, nullptr, F, S, 0, A, Np, nullptr, nullptr, nullptr, false,
-                       w + L.paths_off, stream);
+                       L.paths, stream);
     if (rc != GPBO_OK) return rc;
     hipLaunchKernelGGL(thompson_resid_kernel, dim3((unsigned)((L.S64 * Np + 255) / 256)), dim3(256), 0, st, y, A, E, (int)S,
                        L.S64, N, Np, sqrt(kappa), B);

@@ -270,6 +270,54 @@ int main() {
         EXPECT(gpbo_cholinv_tiles_f64(pd, 512, 256, pi, 5, nullptr, 0, 1, 1, nullptr) == GPBO_ERR_ARG);  // pair beyond Np
         EXPECT(gpbo_cholinv_tiles_f64(pd, 512, 256, pi, -1, nullptr, 0, 1, 1, nullptr) == GPBO_ERR_ARG);  // nothing to do
     }
+    // the workspace carves with a null base (csrc/host_driver.h: Carver): every size query over the argument sets of
+    // tests/test_workspace_sizes_cpu.py, refused values included - whole 256-byte granules, or a refusal
+    {
+        const int64_t NP[] = {128, 256, 384, 4096, 32768, 0, 100}, CHUNK[] = {512, 1024, 131072, 0, 500};
+        const int64_t MM[] = {1, 511, 512, 513, 131073, 0}, CAP[] = {1, 4096, 131073, 0};
+        const int32_t QS[] = {1, 2, 16, 64, 0, 65}, FS[] = {1, 1000, 16384, 0, 16385}, DS[] = {1, 8, 16, 0, 17};
+        const int64_t PS[] = {1, 64, 4096, 0, 4097};
+        long queries = 0;
+        auto granules = [&](int64_t b) {
+            EXPECT(b == GPBO_ERR_ARG || (b > 0 && b % 256 == 0));
+            ++queries;
+        };
+        granules(gpbo_acq_workspace_bytes());
+        for (int64_t Np : NP) {
+            granules(gpbo_prepare_i8_bytes(Np));
+            granules(gpbo_loo_workspace_bytes(Np));
+            granules(gpbo_fps_order_workspace_bytes(Np + 2));
+            EXPECT(gpbo_factorise_workspace_bytes(Np) >= 0 && gpbo_append_workspace_bytes(Np) != 0);
+            for (int64_t chunk : CHUNK)
+                for (int64_t M : MM) {
+                    granules(gpbo_posterior_workspace_bytes(Np, chunk, M));
+                    granules(gpbo_qei_workspace_bytes(Np, chunk, M));
+                    granules(gpbo_posterior_workspace_bytes_f32(Np, chunk, M));
+                    granules(gpbo_posterior_workspace_bytes_i8(Np, chunk, M));
+                    granules(gpbo_ensemble_workspace_bytes(Np, chunk, M));
+                    for (int32_t S : QS) granules(gpbo_posterior_nei_workspace_bytes(Np, chunk, M, S));
+                }
+            for (int64_t chunk : CHUNK)
+                for (int64_t cap : CAP) granules(gpbo_rescore_workspace_bytes(Np, cap, chunk));
+            for (int32_t S : QS) {
+                granules(gpbo_nei_fantasies_workspace_bytes(Np, S));
+                for (int64_t M : MM) granules(gpbo_batch_workspace_bytes(Np, M, S));
+                for (int32_t F : FS) {
+                    granules(gpbo_thompson_weights_workspace_bytes(Np, F, S));
+                    for (int64_t M : MM) granules(gpbo_thompson_paths_workspace_bytes(Np, M, F, S));
+                }
+            }
+            for (int64_t P : PS) {
+                granules(gpbo_posterior_grad_workspace_bytes(Np, P));
+                granules(gpbo_refine_workspace_bytes(Np, P));
+            }
+            for (int32_t d : DS) {
+                granules(gpbo_nlml_grad_workspace_bytes(Np, d));
+                granules(gpbo_nlml_hyper_workspace_bytes(Np, d));
+            }
+        }
+        EXPECT(queries == 1 + 7 * 625);
+    }
     // host-pointer entry points: refused before the first HIP call
     gpbo_result res;
     int32_t info_h = 0;
