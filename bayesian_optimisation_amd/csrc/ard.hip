@@ -10,8 +10,7 @@
 // carried N columns deep in LDS: the last row then holds (L^-1 y)^T, the last pivot is -y^T K^-1 y,
 // and log det K = 2 sum log L_ii.  NumPy's det is sign * exp(logdet) (LAPACK getrf), so the reference's
 // underflow of det to 0 (-> -inf cells for N >~ 100) is reproduced by evaluating log(exp(logdet)).
-#include "gpbo_internal.h"
-#include "exp_neg.h"
+#include "cov_entry.h"
 #include "potrf_diag64.h"
 #include <atomic>
 
@@ -50,12 +49,12 @@ __global__ __launch_bounds__(256) void nlml_grid_kernel(const double *__restrict
         double v = 0.0;
         {
             if (r < N) {
-                double acc = 0.0;
+                double acc = 0.0;   // cov_r2 over a run-time d, written out
                 for (int k = 0; k < d; ++k) {
                     const double diff = xs[r * d + k] - xs[q * d + k];
                     acc = fma(diff * diff, il2[k], acc);
                 }
-                v = exp(-0.5 * acc);
+                v = cov_from_r2<GPBO_KERNEL_SE>(acc);
                 if (r == q) v += jitter;
             } else if (q < N) {
                 v = y[q];
@@ -240,7 +239,7 @@ __global__ __launch_bounds__(TH, OCC) void nlml_fused_kernel(const double *__res
     const int nbf = Nf >> 6;
     d2_t *Lf = reinterpret_cast<d2_t *>(scratch) + (int64_t)blockIdx.x * (int64_t)(RTY + 1) * KP * 64;
 
-    if (tid0 < GPBO_EXP_E) S.tab[tid0] = kExp2Tab256[tid0 * (256 / GPBO_EXP_E)];
+    cov_stage_tab(S.tab, tid0);
 
     for (int g = blockIdx.x; g < G; g += gridDim.x) {
         gpbo_syncthreads();   // the previous cell's reductions have been read
@@ -381,13 +380,13 @@ __global__ __launch_bounds__(TH, OCC) void nlml_fused_kernel(const double *__res
 #pragma unroll
                                 for (int r = 0; r < 4; ++r) {
                                     const double *xc = S.Xc + (16 * ct + l4 + 4 * r) * D;
-                                    double a = 0.0;
+                                    double a = 0.0;   // cov_r2<D> of cov_entry.h, written out here and below (see there)
 #pragma unroll
                                     for (int k = 0; k < D; ++k) {
                                         const double diff = xc[k] - xr[k];
                                         a = fma(diff * diff, il2[k], a);
                                     }
-                                    acc[ct][t][r] = exp_neg(0.5 * a, S.tab) - acc[ct][t][r];
+                                    acc[ct][t][r] = cov_from_r2_tab<GPBO_KERNEL_SE>(a, S.tab) - acc[ct][t][r];
                                 }
                                 __builtin_amdgcn_sched_barrier(0);
                             }
@@ -411,7 +410,7 @@ __global__ __launch_bounds__(TH, OCC) void nlml_fused_kernel(const double *__res
                                         const double diff = S.Xc[jc * D + k] - xr[k];
                                         a = fma(diff * diff, il2[k], a);
                                     }
-                                    double v = exp_neg(0.5 * a, S.tab);
+                                    double v = cov_from_r2_tab<GPBO_KERNEL_SE>(a, S.tab);
                                     if (row == col) v += jitter;
                                     if (row >= N || col >= N) v = (row == col) ? 1.0 : 0.0;
                                     acc[ct][t][r] = v - acc[ct][t][r];

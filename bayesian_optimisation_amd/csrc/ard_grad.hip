@@ -21,8 +21,7 @@
 // Other covariance families (gpbo_nlml_grad_kern_f64): dk / dlog l_k = g(r) (x_ik - x_jk)^2 / l_k^2 with g = k for the squared
 // exponential, 3 exp(-a) for Matern 3/2 and 5/3 (1 + a) exp(-a) for Matern 5/2, so only the factor the epilogue regenerates
 // changes; in the scaled coordinates s = r^2 / 2, a = sqrt(6 s) or sqrt(10 s).  Nothing is divided by r.
-#include "gpbo_internal.h"
-#include "exp_neg.h"
+#include "cov_entry.h"
 
 namespace {
 
@@ -78,7 +77,7 @@ __device__ __forceinline__ void nlml_grad_tile(const double *__restrict__ U, con
     }
     if (tid < GT) ar[tid] = alpha[r0 + tid];
     else if (tid < 2 * GT) ac[tid - GT] = alpha[c0 + tid - GT];
-    else if (tid < 2 * GT + GPBO_EXP_E) tab[tid - 2 * GT] = kExp2Tab256[(tid - 2 * GT) * (256 / GPBO_EXP_E)];
+    else if (tid < 2 * GT + GPBO_EXP_E) cov_stage_tab(tab, tid - 2 * GT);
 
     const double *A = U + (int64_t)r0 * Np;
     const double *B = U + (int64_t)c0 * Np;

@@ -17,19 +17,12 @@
 //     batch_downdate_kernel  every candidate: t_j, mu, sigma, acquisition, block arg-max without the members chosen so far
 //     argmax_finish_kernel   the next member (sigma_acq.hip: lowest index on ties, NaN counted)
 //     batch_record_kernel    idx_out / val_out, the guards
-#include "gpbo_internal.h"
+#include "cov_entry.h"
 
 #include <cmath>
 #include <limits>
 
-#include "exp_neg.h"
-
 namespace {
-
-struct BatchLs {
-    double il2[GPBO_MAX_D];  // 1 / ls_k^2 (the arithmetic of kxx_kernel: k_j is a column of K as the factorisation saw it)
-    double isc[GPBO_MAX_D];  // 1 / (ls_k sqrt 2) (the arithmetic of kstar_mu_kernel)
-};
 
 // What one step hands to the next, on the device.
 struct BatchRec {
@@ -46,7 +39,7 @@ struct BatchRec {
 // k_j[n] = k(x_n, x_j) in the factorisation's own order (0 on the padding), the scaled x_j and the scalars of step j.
 // grid ceil(Np / 256), block 256.  A member that does not exist (idx < 0: see batch_record_kernel) gives k_j = 0.
 __global__ __launch_bounds__(256) void batch_pivot_kernel(const double *__restrict__ Xs, int64_t M,
-                                                          const double *__restrict__ X, int N, int Np, int d, BatchLs ls,
+                                                          const double *__restrict__ X, int N, int Np, int d, CovLs ls,
                                                           const double *__restrict__ mu, const double *__restrict__ sigma,
                                                           const double *__restrict__ T, int64_t ldt, int j,
                                                           double kappa_minus_prior, int fantasy, double lie,
@@ -61,12 +54,12 @@ __global__ __launch_bounds__(256) void batch_pivot_kernel(const double *__restri
     if (i < Np) {
         double v = 0.0;
         if (i < N && !none) {
-            double acc = 0.0;
+            double acc = 0.0;   // cov_r2 over a run-time d, written out: k_j is a column of K as the factorisation saw it
             for (int k = 0; k < d; ++k) {
                 const double diff = X[(int64_t)i * d + k] - xj[k];
                 acc = fma(diff * diff, ls.il2[k], acc);
             }
-            v = exp(-0.5 * acc);
+            v = cov_from_r2<GPBO_KERNEL_SE>(acc);
         }
         kj[i] = v;
     }
@@ -93,7 +86,7 @@ __global__ __launch_bounds__(256) void batch_pivot_kernel(const double *__restri
 // No atomics in the sums (the NaN counter is an integer), fixed order everywhere: two calls give the same bits.
 template <int D>
 __global__ __launch_bounds__(256) void batch_downdate_kernel(const double *__restrict__ Xs, int64_t M,
-                                                             const double *__restrict__ Xsc, int N, BatchLs ls,
+                                                             const double *__restrict__ Xsc, int N, CovLs ls,
                                                              const double *__restrict__ beta,
                                                              const BatchRec *__restrict__ rec, int j,
                                                              double *__restrict__ T, int64_t ldt, double *__restrict__ mu,
@@ -112,7 +105,7 @@ __global__ __launch_bounds__(256) void batch_downdate_kernel(const double *__res
         }
         return;
     }
-    if (tid < GPBO_EXP_E) tab[tid] = kExp2Tab256[tid * (256 / GPBO_EXP_E)];
+    cov_stage_tab(tab, tid);
     const int64_t c0 = ((int64_t)blockIdx.x * 256 + tid) * 2;
     const bool va = c0 < M, vb = c0 + 1 < M;
     double xa[D], xb[D];
@@ -127,45 +120,26 @@ __global__ __launch_bounds__(256) void batch_downdate_kernel(const double *__res
     for (; n + 1 < N; n += 2) {
         const double *xo0 = Xsc + (int64_t)n * D;  // wave-uniform rows -> scalar loads
         const double *xo1 = xo0 + D;
-        double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            const double o0 = xo0[k], o1 = xo1[k];
-            const double d00 = xa[k] - o0, d01 = xb[k] - o0, d10 = xa[k] - o1, d11 = xb[k] - o1;
-            s00 = fma(d00, d00, s00);
-            s01 = fma(d01, d01, s01);
-            s10 = fma(d10, d10, s10);
-            s11 = fma(d11, d11, s11);
-        }
+        double s00, s01, s10, s11;
+        cov_s4<D>(xa, xb, xo0, xo1, s00, s01, s10, s11);
         const double b0 = beta[n], b1 = beta[n + 1];
-        ta0 = fma(exp_neg(s00, tab), b0, ta0);
-        tb0 = fma(exp_neg(s01, tab), b0, tb0);
-        ta1 = fma(exp_neg(s10, tab), b1, ta1);
-        tb1 = fma(exp_neg(s11, tab), b1, tb1);
+        ta0 = fma(cov_from_s<GPBO_KERNEL_SE>(s00, tab), b0, ta0);
+        tb0 = fma(cov_from_s<GPBO_KERNEL_SE>(s01, tab), b0, tb0);
+        ta1 = fma(cov_from_s<GPBO_KERNEL_SE>(s10, tab), b1, ta1);
+        tb1 = fma(cov_from_s<GPBO_KERNEL_SE>(s11, tab), b1, tb1);
     }
     if (n < N) {  // odd tail
         const double *xo = Xsc + (int64_t)n * D;
-        double sa = 0.0, sb = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            const double da = xa[k] - xo[k], db = xb[k] - xo[k];
-            sa = fma(da, da, sa);
-            sb = fma(db, db, sb);
-        }
+        double sa, sb;
+        cov_s2<D>(xa, xb, xo, sa, sb);
         const double bn = beta[n];
-        ta0 = fma(exp_neg(sa, tab), bn, ta0);
-        tb0 = fma(exp_neg(sb, tab), bn, tb0);
+        ta0 = fma(cov_from_s<GPBO_KERNEL_SE>(sa, tab), bn, ta0);
+        tb0 = fma(cov_from_s<GPBO_KERNEL_SE>(sb, tab), bn, tb0);
     }
     // t_j = k(c, x_j) - k_c . beta_j - sum_{i<j} t_i(c) r_i
-    double pa = 0.0, pb = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double o = rec->xj[k];
-        const double da = xa[k] - o, db = xb[k] - o;
-        pa = fma(da, da, pa);
-        pb = fma(db, db, pb);
-    }
-    double t_a = exp_neg(pa, tab) - (ta0 + ta1), t_b = exp_neg(pb, tab) - (tb0 + tb1);
+    double pa, pb;
+    cov_s2<D>(xa, xb, rec->xj, pa, pb);
+    double t_a = cov_from_s<GPBO_KERNEL_SE>(pa, tab) - (ta0 + ta1), t_b = cov_from_s<GPBO_KERNEL_SE>(pb, tab) - (tb0 + tb1);
     if (va) {   // (c0 is even and ldt is: 16-byte pieces; column c0 + 1 < ldt exists even when candidate c0 + 1 does not)
         for (int p = 0; p < j; ++p) {
             const d2_t tp = *reinterpret_cast<const d2_t *>(T + (int64_t)p * ldt + c0);
@@ -288,7 +262,7 @@ extern "C" int gpbo_select_batch_f64(const double *Xs, int64_t M, const double *
     const Layout L(work, Np, M, q);
     if (work_bytes < L.total || !aligned_to(work, 256)) return GPBO_ERR_WORKSPACE;
 
-    BatchLs ls;
+    CovLs ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.il2[k] = ls.isc[k] = 0.0;
     (void)length_scale_scalings(ls_host, d, ls.il2, ls.isc);   // (cannot refuse: length_scales_ok above has)
     hipStream_t st = gpbo_stream(stream);

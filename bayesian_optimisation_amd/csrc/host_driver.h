@@ -60,8 +60,8 @@ inline bool length_scales_ok(const double *ls, int d) {
     return true;
 }
 
-// ---- the length scales as the kernels take them: il2[k] = 1 / ls_k^2 (the arithmetic of kxx_kernel), isc[k] = 1 / (ls_k sqrt 2)
-// (the arithmetic of kstar_mu_kernel), k < d; either may be null.  EXACTLY these expressions: the values feed kernels whose
+// ---- the length scales as the kernels take them: il2[k] = 1 / ls_k^2 (cov_r2, cov_entry.h), isc[k] = 1 / (ls_k sqrt 2)
+// (the scoring form of cov_entry.h), k < d; either may be null.  EXACTLY these expressions: the values feed kernels whose
 // outputs are compared bit for bit.  The entries k >= d are the caller's.  false: a length scale that is not positive.
 inline bool length_scale_scalings(const double *ls_host, int d, double *il2, double *isc) {
     for (int k = 0; k < d; ++k) {

@@ -12,26 +12,10 @@
 // Both kernels take the covariance family as a template parameter (GPBO_KERNEL_*, include/gpbo.h): the squared-exponential
 // instances are the code above unchanged, the Matern instances replace the exponential of the accumulated distance by
 // (1 + a) exp(-a) or (1 + a + a^2 / 3) exp(-a), a = sqrt(3) r or sqrt(5) r.
-#include "gpbo_internal.h"
+#include "cov_entry.h"
 
 #include <cstdlib>
 #include <vector>
-
-struct LsArgs {
-    double il2[GPBO_MAX_D];  // 1 / ls_k^2, computed on the host in fp64
-    double isc[GPBO_MAX_D];  // 1 / (ls_k sqrt 2): coordinates scaled by this give exp(-sum diff^2)
-};
-
-template <int D>
-__device__ __forceinline__ double sqdist(const double (&xc)[D], const double *__restrict__ xo, const LsArgs &ls) {
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double diff = xc[k] - xo[k];
-        acc = fma(diff * diff, ls.il2[k], acc);
-    }
-    return acc;
-}
 
 // ---------------------------------------------------------------------------------------------
 // K1: Kp[Np x Np] = k(X, X) with diagonal (1 + j1) + j2; identity on the padding.
@@ -39,7 +23,7 @@ __device__ __forceinline__ double sqdist(const double (&xc)[D], const double *__
 // entry are ~45 dependent fp64 instructions, so parallelism over rows matters more than reuse of xj).
 // ---------------------------------------------------------------------------------------------
 template <int D, int KERN>
-__global__ __launch_bounds__(256) void kxx_kernel(const double *__restrict__ X, int N, LsArgs ls, double j1,
+__global__ __launch_bounds__(256) void kxx_kernel(const double *__restrict__ X, int N, CovLs ls, double j1,
                                                   double j2, double *__restrict__ K, int Np,
                                                   double *__restrict__ K2 /* optional second copy (the one the
                                                   factorisation overwrites), row stride ld2; ld2 >= 2 Np: the stacked
@@ -56,16 +40,7 @@ __global__ __launch_bounds__(256) void kxx_kernel(const double *__restrict__ X, 
     for (int i = i0; i < i0 + 8; ++i) {
         double v;
         if (i < N) {  // wave-uniform
-            const double acc = sqdist<D>(xj, X + (int64_t)i * D, ls);   // r^2: the same bits for (i, j) and (j, i)
-            if constexpr (KERN == GPBO_KERNEL_SE) {
-                v = exp(-0.5 * acc);
-            } else if constexpr (KERN == GPBO_KERNEL_MATERN32) {
-                const double a = sqrt(3.0 * acc);
-                v = (1.0 + a) * exp(-a);
-            } else {
-                const double a = sqrt(5.0 * acc);
-                v = ((1.0 + a) + a * a / 3.0) * exp(-a);
-            }
+            v = cov_from_r2<KERN>(cov_r2<D>(xj, X + (int64_t)i * D, ls.il2));   // r^2: the same bits for (i, j) and (j, i)
             if (i == j) v = (v + j1) + j2;  // reference: kernel_rbf adds 1e-4 (:193), assembly adds 1e-6 (:79)
             if (j >= N) v = 0.0;
         } else {
@@ -78,8 +53,6 @@ __global__ __launch_bounds__(256) void kxx_kernel(const double *__restrict__ X, 
         }
     }
 }
-
-#include "exp_neg.h"
 
 // ---------------------------------------------------------------------------------------------
 // K2+K5: KsT[n][c] = k(x_n, x*_c) for one candidate chunk, plus per-slice partial means.
@@ -110,23 +83,10 @@ __device__ __forceinline__ void store_pair(float *p, double a, double b) {
 // TK = double: the fp64 path.  TK = float (gpbo_kstar_mu_mixed): entries and means are computed exactly as in the
 // fp64 path - the mean partials are the same doubles bit for bit - and only the stored K*^T is rounded to fp32
 // (relative error <= 2^-24 per entry) for the fp32 variance screen.
-// KERN: with the coordinates scaled as above the accumulated s is r^2 / 2, so a = sqrt(6 s) (Matern 3/2) or sqrt(10 s) (5/2, where
-// a^2 / 3 = 10/3 s needs no square).  The HAS_DIAG quirk belongs to the reference's kernel_rbf: squared exponential only.
-template <int KERN>
-__device__ __forceinline__ double matern_entry(double s, const double *tab) {
-    static_assert(KERN == GPBO_KERNEL_MATERN32 || KERN == GPBO_KERNEL_MATERN52, "a Matern family");
-    if constexpr (KERN == GPBO_KERNEL_MATERN32) {
-        const double a = sqrt_nonneg(6.0 * s);
-        return (1.0 + a) * exp_neg(a, tab);
-    } else {
-        const double a = sqrt_nonneg(10.0 * s);
-        return ((1.0 + a) + (10.0 / 3.0) * s) * exp_neg(a, tab);
-    }
-}
-
+// KERN: cov_from_s<KERN> (cov_entry.h).  The HAS_DIAG quirk belongs to the reference's kernel_rbf: squared exponential only.
 template <int D, int VARIANT, bool HAS_DIAG, typename TK, bool NT, int KERN = GPBO_KERNEL_SE>
 __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict__ Xs, int64_t Mc,
-                                                       const double *__restrict__ Xsc, int N, LsArgs ls,
+                                                       const double *__restrict__ Xsc, int N, CovLs ls,
                                                        const double *__restrict__ alpha, double diag_add,
                                                        int64_t cand_base, TK *__restrict__ KsT, int64_t ldk,
                                                        double *__restrict__ mu_part,
@@ -135,10 +95,10 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
                                                                          observations but K*^T of the first few only */) {
     static_assert(KERN == GPBO_KERNEL_SE || (!HAS_DIAG && VARIANT == 0), "the quirk and the timing variants are SE-only");
     __shared__ double tab[GPBO_EXP_E];
-    if (threadIdx.x < GPBO_EXP_E) tab[threadIdx.x] = kExp2Tab256[threadIdx.x * (256 / GPBO_EXP_E)];
+    cov_stage_tab(tab, threadIdx.x);
     const int64_t c0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
     const int n0 = blockIdx.y * KS_SLICE;
-    double xa[D], xb[D];
+    double xa[D], xb[D];   // (the scaled load stays written out: see cov_entry.h)
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         xa[k] = ((c0 < Mc) ? Xs[c0 * D + k] : 0.0) * ls.isc[k];
@@ -162,23 +122,14 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
     for (; n + 1 < nend; n += 2) {
         const double *xo0 = Xsc + (int64_t)n * D;  // wave-uniform rows -> scalar loads
         const double *xo1 = xo0 + D;
-        double s00 = 0.0, s01 = 0.0, s10 = 0.0, s11 = 0.0;
-#pragma unroll
-        for (int k = 0; k < (VARIANT == 3 ? 1 : D); ++k) {
-            const double o0 = xo0[k], o1 = xo1[k];
-            const double d00 = xa[k] - o0, d01 = xb[k] - o0, d10 = xa[k] - o1, d11 = xb[k] - o1;
-            s00 = fma(d00, d00, s00);
-            s01 = fma(d01, d01, s01);
-            s10 = fma(d10, d10, s10);
-            s11 = fma(d11, d11, s11);
-        }
+        double s00, s01, s10, s11;
+        cov_s4<D, (VARIANT == 3 ? 1 : D)>(xa, xb, xo0, xo1, s00, s01, s10, s11);
         double k00, k01, k10, k11;
-        if constexpr (KERN != GPBO_KERNEL_SE) {
-            k00 = matern_entry<KERN>(s00, tab); k01 = matern_entry<KERN>(s01, tab);
-            k10 = matern_entry<KERN>(s10, tab); k11 = matern_entry<KERN>(s11, tab);
-        } else
         if (VARIANT == 3) { k00 = s00; k01 = s01; k10 = s10; k11 = s11; }
-        else { k00 = exp_neg(s00, tab); k01 = exp_neg(s01, tab); k10 = exp_neg(s10, tab); k11 = exp_neg(s11, tab); }
+        else {
+            k00 = cov_from_s<KERN>(s00, tab); k01 = cov_from_s<KERN>(s01, tab);
+            k10 = cov_from_s<KERN>(s10, tab); k11 = cov_from_s<KERN>(s11, tab);
+        }
         if (HAS_DIAG) {  // N == M shape-coincidence quirk (point_selector.py:173,191-193)
             if ((int64_t)n == cand_base + c0) k00 += diag_add;
             if ((int64_t)n == cand_base + c0 + 1) k01 += diag_add;
@@ -203,16 +154,9 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
     }
     if (n < nend) {  // odd tail
         const double *xo = Xsc + (int64_t)n * D;
-        double sa = 0.0, sb = 0.0;
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-            const double da = xa[k] - xo[k], db = xb[k] - xo[k];
-            sa = fma(da, da, sa);
-            sb = fma(db, db, sb);
-        }
-        double ka, kb;
-        if constexpr (KERN != GPBO_KERNEL_SE) { ka = matern_entry<KERN>(sa, tab); kb = matern_entry<KERN>(sb, tab); }
-        else { ka = exp_neg(sa, tab); kb = exp_neg(sb, tab); }
+        double sa, sb;
+        cov_s2<D>(xa, xb, xo, sa, sb);
+        double ka = cov_from_s<KERN>(sa, tab), kb = cov_from_s<KERN>(sb, tab);
         if (HAS_DIAG) {
             if ((int64_t)n == cand_base + c0) ka += diag_add;
             if ((int64_t)n == cand_base + c0 + 1) kb += diag_add;
@@ -234,7 +178,7 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
 
 // Xsc[n][k] = X[n][k] / (ls_k sqrt 2), rows n >= N zero.   One thread per element.
 __global__ __launch_bounds__(256) void scale_points_kernel(const double *__restrict__ X, int64_t N, int64_t Np, int d,
-                                                          LsArgs ls, double *__restrict__ Xsc,
+                                                          CovLs ls, double *__restrict__ Xsc,
                                                           unsigned long long *__restrict__ zero_word /* optional:
                                                           cleared here (the posterior's NaN counter), saving a memset */) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -262,7 +206,7 @@ __global__ __launch_bounds__(256) void kxx_anyd_kernel(const double *__restrict_
     for (int i = i0; i < i0 + 8; ++i) {
         double v;
         if (i < N) {
-            double acc = 0.0;
+            double acc = 0.0;   // cov_r2 / cov_from_r2<SE> of cov_entry.h over a run-time d: the any-d slow path keeps its copy
             if (j < N) {
                 for (int k = 0; k < d; ++k) {
                     const double diff = X[(int64_t)j * d + k] - X[(int64_t)i * d + k];
@@ -345,7 +289,7 @@ int gpbo_kstar_mu_anyd(const double *Xs, int64_t Mc, const double *X, int64_t N,
     return ok ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
-static int make_ls(const double *ls_host, int d, LsArgs *out) {
+static int make_ls(const double *ls_host, int d, CovLs *out) {
     if (!ls_host || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
     for (int k = 0; k < GPBO_MAX_D; ++k) out->il2[k] = out->isc[k] = 0.0;
     return length_scale_scalings(ls_host, d, out->il2, out->isc) ? GPBO_OK : GPBO_ERR_ARG;
@@ -368,7 +312,7 @@ int gpbo_kxx_launch(const double *X, int64_t N, int32_t d, const double *ls_host
         (void)hipFreeAsync(lsd, st);
         return ok ? GPBO_OK : GPBO_ERR_LAUNCH;
     }
-    LsArgs ls;
+    CovLs ls;
     int rc = make_ls(ls_host, d, &ls);
     if (rc != GPBO_OK) return rc;
     dim3 grid((unsigned)((Np + 255) / 256), (unsigned)(Np / 8));
@@ -399,7 +343,7 @@ extern "C" int gpbo_kxx_kern_f64(const double *X, int64_t N, int32_t d, const do
 int gpbo_scale_points_launch(const double *X, int64_t N, int64_t Np, int32_t d, const double *ls_host, double *Xsc,
                              unsigned long long *zero_word, void *stream) {
     if (!X || !Xsc || N < 1 || Np < N) return GPBO_ERR_ARG;
-    LsArgs ls;
+    CovLs ls;
     int rc = make_ls(ls_host, d, &ls);
     if (rc != GPBO_OK) return rc;
     const int64_t tot = Np * d;
@@ -437,7 +381,7 @@ int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t 
     if (store_rows < 0 || store_rows > Np || store_rows % KS_SLICE) return GPBO_ERR_ARG;
     if (Mc < 1 || N < 1 || Np < N || Np % 128 != 0 || ldk % GPBO_CHUNK_GRANULE != 0 || Mc > ldk)
         return GPBO_ERR_ARG;
-    LsArgs ls;
+    CovLs ls;
     int rc = make_ls(ls_host, d, &ls);
     if (rc != GPBO_OK) return rc;
     const int64_t used = round_up_granule(Mc);
@@ -489,7 +433,7 @@ int gpbo_kstar_mu_mixed(const double *Xs, int64_t Mc, const double *Xsc, int64_t
                         int64_t ldk, double *mu_part, void *stream) {
     if (!Xs || !Xsc || !alpha || !KsT || !mu_part) return GPBO_ERR_ARG;
     if (Mc < 1 || N < 1 || Np < N || Np % KS_SLICE != 0 || ldk % GPBO_CHUNK_GRANULE != 0 || Mc > ldk) return GPBO_ERR_ARG;
-    LsArgs ls;
+    CovLs ls;
     int rc = make_ls(ls_host, d, &ls);
     if (rc != GPBO_OK) return rc;
     const int64_t used = round_up_granule(Mc);

@@ -38,8 +38,7 @@
 // the mean of ITS candidate over its rows and the four lanes of a candidate are added once at the end; K*^T rows are
 // stored as 128-byte segments (16 candidates).  mu_part is [Np / slice][ldk] with slice = gpbo_kstar_mfma_slice(Np)
 // observations per workgroup (kstar_mu_kernel's layout with a coarser slice).
-#include "gpbo_internal.h"
-#include "exp_neg.h"
+#include "cov_entry.h"
 
 #include <type_traits>
 
@@ -53,10 +52,6 @@ constexpr double PAD_ROW_NORM = 1e300;     // |b|^2 of padding rows i >= N: t = 
 struct ObsPrep {
     double m[GPBO_MAX_D];   // centre (scaled coordinates)
     double S0, S1;
-};
-
-struct IscArgs {
-    double isc[GPBO_MAX_D];  // 1 / (ls_k sqrt 2)
 };
 
 // 2^(j/256), j = 0 .. 255: kExp2Tab256 of exp_neg.h (one table for every kernel of the library)
@@ -115,7 +110,7 @@ __device__ __forceinline__ double clamp_t(double t) {
 }
 
 // One workgroup: centre, rows (b_1 .. b_d, 1, |b|^2, 0 ..) of the observations, S0, S1.  N x d is small (4096 x 8).
-__global__ __launch_bounds__(1024) void obs_prep_kernel(const double *__restrict__ X, int N, int Np, int d, IscArgs ls,
+__global__ __launch_bounds__(1024) void obs_prep_kernel(const double *__restrict__ X, int N, int Np, int d, CovIsc ls,
                                                         const double *__restrict__ alpha, int KP, double *__restrict__ Bp,
                                                         ObsPrep *__restrict__ prep) {
     __shared__ double red[1024];
@@ -178,7 +173,7 @@ __global__ __launch_bounds__(1024) void obs_prep_kernel(const double *__restrict
 // (MFMA results straight into VGPRs - `-mllvm -amdgpu-mfma-vgpr-form=1`, no v_accvgpr_read per value - was measured too:
 //  13.2-13.4 against 13.3-13.5 ms per 2^21 candidates for the whole route, at 128-130 registers instead of 94: not used.)
 template <int KQ /* ceil(d / 4): MFMAs per 16 x 16 pairs */>
-__global__ __launch_bounds__(256) void kstar_mu_mfma_kernel(const double *__restrict__ Xs, int64_t Mc, int d, IscArgs ls,
+__global__ __launch_bounds__(256) void kstar_mu_mfma_kernel(const double *__restrict__ Xs, int64_t Mc, int d, CovIsc ls,
                                                             const double *__restrict__ Bp, const ObsPrep *__restrict__ prep,
                                                             const double *__restrict__ alpha, int N, double gamma,
                                                             double eps_acc /* rounding of the means' summations */,
@@ -323,7 +318,7 @@ int64_t gpbo_kstar_mfma_prep_bytes(int64_t Np) {
 int gpbo_kstar_mfma_prep(const double *X, int64_t N, int64_t Np, int32_t d, const double *ls_host, const double *alpha,
                          void *prep_buf, void *stream) {
     if (!X || !ls_host || !alpha || !prep_buf || N < 1 || Np < N || d < 1 || d > GPBO_MAX_D) return GPBO_ERR_ARG;
-    IscArgs ls;
+    CovIsc ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.isc[k] = 0.0;
     if (!length_scale_scalings(ls_host, d, nullptr, ls.isc)) return GPBO_ERR_ARG;
     const int KP = (d + 2 + 3) / 4 * 4;
@@ -343,7 +338,7 @@ int gpbo_kstar_mu_mfma(const double *Xs, int64_t Mc, int64_t N, int64_t Np, int3
     if (Mc < 1 || N < 1 || Np < N || Np % 128 || ldk % GPBO_CHUNK_GRANULE || Mc > ldk || d < 1 || d > GPBO_MAX_D)
         return GPBO_ERR_ARG;
     if (store_rows < 0 || store_rows > Np || store_rows % KS) return GPBO_ERR_ARG;
-    IscArgs ls;
+    CovIsc ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.isc[k] = 0.0;
     if (!length_scale_scalings(ls_host, d, nullptr, ls.isc)) return GPBO_ERR_ARG;   // (the prep call has refused it already)
     const int KQ = (d + 3) / 4, KP = (d + 2 + 3) / 4 * 4;

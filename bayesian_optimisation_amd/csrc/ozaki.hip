@@ -52,10 +52,6 @@ constexpr int KS_SLICE = GPBO_KS_SLICE;    // observations per mu_part slice (64
 constexpr double MAGIC = 6755399441055744.0;  // 1.5 2^52: x + MAGIC has rint(x) in its low mantissa bits
 constexpr double TWO38 = 274877906944.0;
 
-struct LsArgsI8 {
-    double isc[GPBO_MAX_D];  // 1 / (ls_k sqrt 2)
-};
-
 __device__ __forceinline__ void glds16b(const char *g, char *l) {
     __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)l, 16, 0, 0);
 }
@@ -68,8 +64,8 @@ __device__ __forceinline__ void glds16b_s(const char *base, unsigned lane_off, u
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(lane_off), "s"(base) : "memory");
 }
 
-// ---- exp(-t), t >= 0: the one definition shared with kernel_build.hip (bit-identical entries and means) --------------
-#include "exp_neg.h"
+// ---- the covariance entry: the one definition shared with kernel_build.hip (bit-identical entries and means) ---------
+#include "cov_entry.h"
 
 // ---- balanced base-256 digits of four fixed-point values at once --------------------------------------------------
 // In: z[q] = x_q 2^46 + MAGIC (q = 0..3).  Out: P[a] (a = 0 most significant) = the a-th digits of the four values,
@@ -180,13 +176,13 @@ __global__ __launch_bounds__(256) void u_slices_kernel(const double *__restrict_
 // for the coarse screen below.
 template <int D, bool NT /* non-temporal stores: slabs far beyond the Infinity Cache (see kernel_build.hip) */, int NA>
 __global__ __launch_bounds__(256) void kstar_slices_kernel(const double *__restrict__ Xs, int64_t Mc,
-                                                           const double *__restrict__ Xsc, int N, LsArgsI8 ls,
+                                                           const double *__restrict__ Xsc, int N, CovIsc ls,
                                                            const double *__restrict__ alpha, char *__restrict__ A8,
                                                            int64_t RT, double *__restrict__ mu_part, int64_t ldk) {
     __shared__ double tab[GPBO_EXP_E];
-    if (threadIdx.x < GPBO_EXP_E) tab[threadIdx.x] = kExp2Tab256[threadIdx.x * (256 / GPBO_EXP_E)];
+    cov_stage_tab(tab, threadIdx.x);
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    double x[D];
+    double x[D];   // (the scaled load stays written out: see cov_entry.h)
     bool nan_c = false;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
@@ -209,13 +205,7 @@ __global__ __launch_bounds__(256) void kstar_slices_kernel(const double *__restr
                 double kv = 0.0;
                 if (n < N) {  // wave-uniform
                     const double *xo = Xsc + (int64_t)n * D;
-                    double s = 0.0;
-#pragma unroll
-                    for (int k = 0; k < D; ++k) {
-                        const double dd = x[k] - xo[k];
-                        s = fma(dd, dd, s);
-                    }
-                    kv = exp_neg(s, tab);
+                    kv = cov_from_s<GPBO_KERNEL_SE>(cov_s<D>(x, xo), tab);
                     mu = fma(kv, alpha[n], mu);
                 }
                 z[q] = fma(kv, TWO38, MAGIC);
@@ -929,7 +919,7 @@ int posterior_i8_impl(bool coarse, const double *Xs, int64_t M, const GpModel &g
     if (!aligned_to(work, 256) || !aligned_to(u8, 256)) return GPBO_ERR_ARG;
     const LayoutI8 L(work, Np, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
-    LsArgsI8 ls;
+    CovIsc ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.isc[k] = 0.0;
     if (!length_scale_scalings(ls_host, d, nullptr, ls.isc)) return GPBO_ERR_ARG;
     hipStream_t st = gpbo_stream(stream);

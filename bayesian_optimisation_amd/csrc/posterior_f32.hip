@@ -32,10 +32,6 @@ constexpr int LDA = BM + 16, LDB = BN + 16;
 constexpr int A_TILE = BK * LDA, B_TILE = BK * LDB, STAGE = A_TILE + B_TILE;  // floats
 constexpr int KS_SLICE = 64;
 
-struct LsArgs32 {
-    double isc[GPBO_MAX_D];  // 1 / (ls_k sqrt 2)
-};
-
 __device__ __forceinline__ void glds16f(const float *g, float *l) {
     __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)l, 16, 0, 0);
 }

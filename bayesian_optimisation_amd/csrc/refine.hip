@@ -26,7 +26,7 @@
 #include <cmath>
 #include <limits>
 
-#include "exp_neg.h"
+#include "cov_entry.h"
 
 namespace {
 
@@ -35,7 +35,7 @@ struct RefineBox {
     double ls[GPBO_MAX_D];   // ls_k
     double l2[GPBO_MAX_D];   // ls_k^2
     double il2[GPBO_MAX_D];  // 1 / ls_k^2
-    double isc[GPBO_MAX_D];  // 1 / (ls_k sqrt 2) (the arithmetic of kstar_mu_kernel)
+    double isc[GPBO_MAX_D];  // 1 / (ls_k sqrt 2): the scoring form of cov_entry.h
 };
 
 // The state of one start, on the device from the first launch of a call to the last.
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void refine_ks_kernel(const double *__restrict
                                                         int N, int Np, RefineBox box, double *__restrict__ Ks) {
     __shared__ double tab[GPBO_EXP_E];
     const int tid = threadIdx.x;
-    if (tid < GPBO_EXP_E) tab[tid] = kExp2Tab256[tid * (256 / GPBO_EXP_E)];
+    cov_stage_tab(tab, tid);
     const int n = blockIdx.x * 256 + tid;
     double xo[D];
 #pragma unroll
@@ -76,13 +76,13 @@ __global__ __launch_bounds__(256) void refine_ks_kernel(const double *__restrict
         double v = 0.0;
         if (p < P && n < N) {
             const double *xp = pts + (int64_t)p * D;   // wave-uniform
-            double s = 0.0;
+            double s = 0.0;   // cov_s of cov_entry.h on a point scaled on the fly, written out (see there)
 #pragma unroll
             for (int k = 0; k < D; ++k) {
                 const double df = xp[k] * box.isc[k] - xo[k];
                 s = fma(df, df, s);
             }
-            v = exp_neg(s, tab);
+            v = cov_from_s<GPBO_KERNEL_SE>(s, tab);
         }
         Ks[(int64_t)p * Np + n] = v;
     }

@@ -18,7 +18,7 @@
 // Waves w and w+4 share a SIMD; they take the even and the odd 16-column tiles of the block, so that on the
 // diagonal (where tiles below U's diagonal are skipped) both always have nearly the same amount of work and
 // keep hiding each other's LDS / branch / DMA-issue latencies.
-#include "gpbo_internal.h"
+#include "cov_entry.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -572,10 +572,6 @@ int split_factor(int64_t nblk, int64_t nJ, int split_max) {
 // ================================================================================================
 constexpr int QQ = 8, QT = QQ * (QQ + 1) / 2;  // 36 lower-triangle entries, index i*(i+1)/2 + j, j <= i
 
-struct QeiLs {
-    double il2[GPBO_MAX_D];
-};
-
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
@@ -583,7 +579,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 __global__ __launch_bounds__(256) void qei_kernel(const double *__restrict__ G, int P, int64_t nb8, const double *__restrict__ mu,
-                                                  const double *__restrict__ Xs, int d, QeiLs ls, int64_t nbatch,
+                                                  const double *__restrict__ Xs, int d, CovIl2 ls, int64_t nbatch,
                                                   double prior_var, double f_best, double xi,
                                                   const double *__restrict__ Z, int S, int64_t batch_base,
                                                   double *__restrict__ qei_out, double *__restrict__ part_val,
@@ -615,12 +611,12 @@ __global__ __launch_bounds__(256) void qei_kernel(const double *__restrict__ G, 
             kmine = prior_var;
         } else {
             const double *xi_ = Xs + (bb * QQ + i) * d, *xj_ = Xs + (bb * QQ + j) * d;
-            double accd = 0.0;
+            double accd = 0.0;   // cov_r2 over a run-time d, written out
             for (int k = 0; k < d; ++k) {
                 const double diff = xi_[k] - xj_[k];
                 accd = fma(diff * diff, ls.il2[k], accd);
             }
-            kmine = exp(-0.5 * accd);
+            kmine = cov_from_r2<GPBO_KERNEL_SE>(accd);
         }
     }
     double L[QT];
@@ -1038,7 +1034,7 @@ extern "C" int gpbo_posterior_qei_f64(const double *Xs, int64_t M, const double 
     if (!aligned_to(work, 256) || !aligned_to(U, 16)) return GPBO_ERR_ARG;
     const QeiLayout L(work, Np, chunk, M);
     if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
-    QeiLs ls;
+    CovIl2 ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.il2[k] = 0.0;
     if (!length_scale_scalings(ls_host, d, ls.il2, nullptr)) return GPBO_ERR_ARG;
     hipStream_t st = gpbo_stream(stream);

@@ -26,12 +26,12 @@
 #include <cmath>
 #include <limits>
 
-#include "exp_neg.h"
+#include "cov_entry.h"
 
 namespace {
 
 struct TsScale {
-    double isc[GPBO_MAX_D];   // 1 / (ls_k sqrt 2) (the arithmetic of kstar_mu_kernel)
+    double isc[GPBO_MAX_D];   // 1 / (ls_k sqrt 2): the scoring form of cov_entry.h
     double tl[GPBO_MAX_D];    // 2 pi ls_k
 };
 
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void thompson_paths_kernel(
     __shared__ double s_val[4][G];
     __shared__ int64_t s_idx[4][G];
     const int tid = threadIdx.x, lane = tid & 63;
-    if (tid < GPBO_EXP_E) tab[tid] = kExp2Tab256[tid * (256 / GPBO_EXP_E)];
+    cov_stage_tab(tab, tid);
     const int g0 = blockIdx.y * G;
     const int64_t c0 = ((int64_t)blockIdx.x * 256 + tid) * 2;
     const bool va = c0 < M, vb = c0 + 1 < M;
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void thompson_paths_kernel(
         for (int n = 0; n < N; ++n) {
             const double *xo = Xsc + (int64_t)n * D;   // wave-uniform -> scalar loads
             const double *v = Vt + (int64_t)n * Sp + g0;
-            double sa = 0.0, sb = 0.0;
+            double sa = 0.0, sb = 0.0;   // cov_s2 of cov_entry.h, written out (see there)
 #pragma unroll
             for (int k = 0; k < D; ++k) {
                 const double o = xo[k];
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void thompson_paths_kernel(
                 sa = fma(da, da, sa);
                 sb = fma(db, db, sb);
             }
-            const double ka = exp_neg(sa, tab), kb = exp_neg(sb, tab);
+            const double ka = cov_from_s<GPBO_KERNEL_SE>(sa, tab), kb = cov_from_s<GPBO_KERNEL_SE>(sb, tab);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 const double vg = v[g];

@@ -7,34 +7,30 @@
 //     U' = L'^-T = [U  -U l / lambda; 0  1 / lambda]
 // so only column N of U is new; alpha' = U' (U'^T y') is recomputed in full (two matrix-vector products,
 // same kernels and summation order as gpbo_alpha_f64, so nothing accumulates over repeated appends).
-// K entries use the arithmetic of kxx_kernel (kernel_build.hip) so that an appended row of K is bit-identical
+// K entries are cov_r2's sum and cov_from_r2 (cov_entry.h), kxx_kernel's own, so that an appended row of K is bit-identical
 // to the row a fresh gpbo_kxx_f64 would build.
-#include "gpbo_internal.h"
+#include "cov_entry.h"
 
 #include <cmath>
 
 namespace {
 
-struct LsInv2 {
-    double il2[GPBO_MAX_D];  // 1 / ls_k^2, host fp64 (as kernel_build.hip's LsArgs::il2)
-};
-
 // kvec_i = k(x_i, x_new) for i < N, 0 on the padding; row N of X and y receive the new observation.
 // grid ceil(Np/256), block 256.
 __global__ __launch_bounds__(256) void append_kvec_kernel(double *__restrict__ X, double *__restrict__ y, int N, int d,
-                                                          LsInv2 ls, const double *__restrict__ x_new,
+                                                          CovIl2 ls, const double *__restrict__ x_new,
                                                           const double *__restrict__ y_new, int Np,
                                                           double *__restrict__ kvec) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Np) return;
     double v = 0.0;
     if (i < N) {
-        double acc = 0.0;
+        double acc = 0.0;   // cov_r2 over a run-time d, written out
         for (int k = 0; k < d; ++k) {
             const double diff = X[(int64_t)i * d + k] - x_new[k];
             acc = fma(diff * diff, ls.il2[k], acc);
         }
-        v = exp(-0.5 * acc);
+        v = cov_from_r2<GPBO_KERNEL_SE>(acc);
     }
     kvec[i] = v;
     if (i == N) {
@@ -106,7 +102,7 @@ extern "C" int gpbo_append_f64(double *X, double *y, int64_t N, int32_t d, const
     if (!X || !y || !ls_host || !x_new || !y_new || !U || !alpha || !info || !work) return GPBO_ERR_ARG;
     if (N < 1 || d < 1 || d > GPBO_MAX_D || Np % GPBO_NB || N + 1 > Np || Np > (1 << 30)) return GPBO_ERR_ARG;
     if (work_bytes < gpbo_append_workspace_bytes(Np)) return GPBO_ERR_WORKSPACE;
-    LsInv2 ls;
+    CovIl2 ls;
     for (int k = 0; k < GPBO_MAX_D; ++k) ls.il2[k] = 0.0;
     if (!length_scale_scalings(ls_host, d, ls.il2, nullptr)) return GPBO_ERR_ARG;
     hipStream_t st = gpbo_stream(stream);

@@ -9,8 +9,7 @@
 // column's z - and in WHICH ORDER it sums - is the kernel's: that order is part of its output bits (eliminate()'s hook).
 // The register allocation of these kernels is fragile; the notes at build_row(), load_rhs() and eliminate() say what was paid.
 #pragma once
-#include "gpbo_internal.h"
-#include "exp_neg.h"
+#include "cov_entry.h"
 #include "potrf_diag64.h"
 
 #include <cmath>
@@ -30,7 +29,7 @@ constexpr int CELLS = 4;   // waves, hence cells, per workgroup of 256
 template <int NMAX, int D>
 __device__ __forceinline__ int stage(double *tab, double *Xs, double *ys, const double *__restrict__ X, const double *__restrict__ y,
                                      int N, int d) {
-    if (threadIdx.x < GPBO_EXP_E) tab[threadIdx.x] = kExp2Tab256[threadIdx.x * (256 / GPBO_EXP_E)];
+    cov_stage_tab(tab, threadIdx.x);
     for (int e = threadIdx.x; e < NMAX * D; e += 256) {
         const int r = e / D, q = e % D;   // (D is a power of two)
         Xs[e] = (r < N && q < d) ? X[r * d + q] : 0.0;
@@ -47,8 +46,8 @@ __device__ __forceinline__ int row_of(int lane) {
 }
 
 // x[k] = (K0(ls) + diag I)[i][k] for the lane's row i = li; ls: the cell's d length scales (wave-uniform).  Column k's coordinates
-// are wave-uniform too (one LDS address for the wave).  The entry formulas are those of kxx_kernel (kernel_build.hip) on the
-// table-driven exp(-t) and the Goldschmidt sqrt of exp_neg.h.
+// are wave-uniform too (one LDS address for the wave).  The entries are cov_r2 / cov_from_r2_tab (cov_entry.h): kxx_kernel's
+// formulas on the table-driven exp(-t) and the Goldschmidt sqrt of exp_neg.h.
 template <int NMAX, int D, int KERN>
 __device__ __forceinline__ void build_row(double (&x)[NMAX], const double *tab, const double *Xs, const double *__restrict__ ls,
                                           double diag, int N, int d, int lane, int li) {
@@ -61,22 +60,7 @@ __device__ __forceinline__ void build_row(double (&x)[NMAX], const double *tab, 
     }
 #pragma unroll
     for (int k = 0; k < NMAX; ++k) {
-        double a = 0.0;
-#pragma unroll
-        for (int q = 0; q < D; ++q) {
-            const double diff = Xs[k * D + q] - xi[q];
-            a = fma(diff * diff, il2[q], a);
-        }
-        double v;
-        if constexpr (KERN == GPBO_KERNEL_SE) {
-            v = exp_neg(0.5 * a, tab);
-        } else if constexpr (KERN == GPBO_KERNEL_MATERN32) {
-            const double t = sqrt_nonneg(3.0 * a);
-            v = (1.0 + t) * exp_neg(t, tab);
-        } else {
-            const double t = sqrt_nonneg(5.0 * a);
-            v = ((1.0 + t) + t * t / 3.0) * exp_neg(t, tab);
-        }
+        double v = cov_from_r2_tab<KERN>(cov_r2<D>(Xs + k * D, xi, il2), tab);
         if (k == lane) v += diag;
         if (lane >= N || k >= N) v = (k == lane) ? 1.0 : 0.0;
         x[k] = v;
