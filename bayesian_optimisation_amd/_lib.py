@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GPBO_LIB=/path/to/variant.so: A/B and timing-only builds (tools/ab*.sh, tools/build_variant.sh) are loaded from where
 # they were built; the installed library is never overwritten by a tool.
@@ -44,7 +46,38 @@ def kernel_id(kernel: str) -> int:
         raise ValueError(f"kernel must be one of {sorted(KERNEL_IDS)}, got {kernel!r}") from None
 
 
-_p = C.c_void_p
+_address = C.c_void_p.from_param   # an integer as a pointer argument (cheaper than a c_void_p object)
+_NO_BYTES = C.c_char * 0
+
+
+class Pointer(C.c_void_p):
+    """A `T *` argument.  Arrays and tensors go in as they are: None (NULL), a C-contiguous numpy.ndarray, anything with
+    data_ptr() / is_contiguous() (a torch tensor: this module does not import torch), and whatever c_void_p takes (a
+    c_void_p, an integer, a ctypes array or pointer, byref(...)).  A view that is not contiguous is refused before the call
+    (ctypes.ArgumentError): the library would read the rows of another matrix."""
+
+    @classmethod
+    def from_param(cls, obj):
+        # (ordered by how often each kind arrives: this runs once per pointer argument of every call)
+        if obj is None or type(obj) is C.c_void_p:
+            return obj
+        try:
+            contiguous = obj.is_contiguous()
+        except AttributeError:
+            if isinstance(obj, np.ndarray):
+                if not obj.flags.c_contiguous:
+                    raise TypeError("an array passed to the library must be C-contiguous") from None
+                try:
+                    return _NO_BYTES.from_buffer(obj)   # (a ctypes array at its address: a fifth of the cost of obj.ctypes)
+                except TypeError:
+                    return C.c_void_p(obj.ctypes.data)  # a read-only array has no writable buffer to take
+            return obj if isinstance(obj, C.c_void_p) else C.c_void_p.from_param(obj)
+        if not contiguous:
+            raise TypeError("a tensor passed to the library must be contiguous")
+        return _address(obj.data_ptr())
+
+
+_p = Pointer
 _i64 = C.c_int64
 _i32 = C.c_int32
 _f64 = C.c_double
@@ -76,7 +109,7 @@ SIGNATURES = {
     "gpbo_posterior_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     "gpbo_posterior_acq_f64": (C.c_int, [_p, _i64, _p, _i64, _i64, _i32, _p, _p, _p, _f64, _i32, _f64, _f64, _f64,
                                          _i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
-    "gpbo_profile_create": (C.c_int, [_i32, C.POINTER(_p)]),
+    "gpbo_profile_create": (C.c_int, [_i32, C.POINTER(C.c_void_p)]),
     "gpbo_profile_reset": (None, [_p]),
     "gpbo_profile_read": (C.c_int, [_p, C.POINTER(_f64), C.POINTER(_i64), C.POINTER(_i64)]),
     "gpbo_profile_read_kstar": (C.c_int, [_p, C.POINTER(_f64), C.POINTER(_i64), C.POINTER(_i64)]),
@@ -269,4 +302,11 @@ def check(status: int, what: str):
     if status != GPBO_OK:
         msg = load().gpbo_strerror(status).decode()
         raise GpboError(f"{what}: {msg} (status {status})")
+
+
+def call(fn, *args):
+    """fn(*args) for a library function that returns a status; GpboError naming the function when it is not GPBO_OK."""
+    status = fn(*args)
+    if status != GPBO_OK:
+        check(status, fn.__name__)
 

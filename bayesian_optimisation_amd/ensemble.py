@@ -9,14 +9,13 @@ distributions, everything in the units of y.  PyTorch is plumbing only, as in gp
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
 
 from . import _lib
-from .gp_device import DEFAULT_CHUNK, _round_up, _torch, acq_params
+from .gp_device import DEFAULT_CHUNK, DeviceSide, acq_params
 
 ENSEMBLE_MAX_BYTES = 8 << 30   # cap on the stacked inverse factors, S * Np^2 * 8 bytes (S = 16 at N = 8192)
 
@@ -31,35 +30,15 @@ class EnsembleResult:
     acq: Optional[object] = None     # the integrated acquisition
 
 
-class DeviceEnsemble:
+class DeviceEnsemble(DeviceSide):
     def __init__(self, device=None, chunk: int = DEFAULT_CHUNK):
-        torch = _torch()
-        self.lib = _lib.load()
-        self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if chunk % _lib.CHUNK_GRANULE:
-            raise ValueError(f"chunk must be a multiple of {_lib.CHUNK_GRANULE}")
-        self.chunk = int(chunk)
-        self.S = self.N = self.Np = self.d = 0
-        self.kernel = "se"
+        super().__init__(device, chunk)
+        self.S = 0
         self.X = self.U = self.alpha = self.info = None
         self.ls_h = self.model_h = None      # host [S x d], [S x 4] = (weight, prior variance, y_mean, y_scale)
         self._K = self._work_fact = self._work = None
-        self._result = torch.zeros(4, dtype=torch.int64, device=self.device)
+        self._result = self.torch.zeros(4, dtype=self.torch.int64, device=self.device)
         self._keep = None
-
-    def _stream(self):
-        return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _dev(self, arr):
-        torch = self.torch
-        if isinstance(arr, torch.Tensor):
-            return arr.to(device=self.device, dtype=torch.float64).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float64)).to(self.device)
-
-    @staticmethod
-    def _ptr(t):
-        return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
     def factorise(self, X, y, models):
         """models: a list of (length scales [d], model.SurrogateModel, weight >= 0), 1 <= S <= 64, one covariance family.
@@ -70,15 +49,8 @@ class DeviceEnsemble:
         S = len(models)
         if not 1 <= S <= _lib.ENSEMBLE_MAX_S:
             raise ValueError(f"an ensemble holds 1 to {_lib.ENSEMBLE_MAX_S} models, got {S}")
-        Xd = self._dev(X)
-        if Xd.dim() != 2:
-            raise ValueError("X must be (N, d)")
-        N, d = int(Xd.shape[0]), int(Xd.shape[1])
-        if d > _lib.MAX_D:
-            raise ValueError(f"an ensemble needs d <= {_lib.MAX_D}, got d = {d}")
-        y_h = np.asarray(y, dtype=np.float64).reshape(-1)
-        if y_h.size != N:
-            raise ValueError("y must have one value per row of X")
+        limit = (_lib.MAX_D, f"an ensemble needs d <= {_lib.MAX_D}, got d = {{d}}")
+        Xd, y_h, N, d, _ = self._problem(X, y, None, [limit], host_y=True)   # (the [S x d] length scales: checked below)
         kernels = {m.kernel for _, m, _ in models}
         if len(kernels) != 1:
             raise ValueError(f"the models of an ensemble share one covariance family, got {sorted(kernels)}")
@@ -104,16 +76,11 @@ class DeviceEnsemble:
                 self._K = torch.empty((Np, Np), **f64)
             self.info = torch.zeros(S, dtype=torch.int32, device=self.device)
             wf = int(self.lib.gpbo_factorise_workspace_bytes(Np))
-            if self._work_fact is None or self._work_fact.numel() * 8 < wf:
-                self._work_fact = torch.empty((wf + 7) // 8, **f64)
+            work = self._workspace("_work_fact", wf)
             ys = self._dev(np.stack([m.to_model(y_h) for _, m, _ in models]))   # [S x N], each in its model's units
             for s, (_, m, _) in enumerate(models):
-                st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(ys[s]), N, d,
-                                                      ls_h[s].ctypes.data_as(C.c_void_p), kid, float(m.jitter1),
-                                                      float(m.jitter2), Np, self._ptr(self._K), self._ptr(self.U[s]),
-                                                      self._ptr(self.alpha[s]), self._ptr(self.info[s:s + 1]),
-                                                      self._ptr(self._work_fact), wf, self._stream())
-                _lib.check(st, "gpbo_factorise_kern_f64")
+                self._factorise_into(Xd, ys[s], N, d, ls_h[s], kid, float(m.jitter1), float(m.jitter2), Np, self._K,
+                                     self.U[s], self.alpha[s], self.info[s:s + 1], work, wf)
             info = self.info.cpu().numpy()   # synchronises
         self.X, self.S, self.N, self.Np, self.d, self.kernel = Xd, S, N, Np, d, kernel
         self.ls_h, self.model_h = ls_h, model_h
@@ -131,28 +98,15 @@ class DeviceEnsemble:
         torch = self.torch
         if self.S < 1:
             raise _lib.GpboError("score() needs a factorised ensemble")
-        Xsd = self._dev(Xs)
-        if Xsd.dim() != 2 or int(Xsd.shape[1]) != self.d:
-            raise ValueError("Xs must be (M, d) with the same d as X")
-        M = int(Xsd.shape[0])
+        Xsd, M = self._candidates(Xs)
         kind, p0, p1 = acq_params(acquisition, explore, f_best, xi)
-        chunk = _round_up(min(self.chunk, _round_up(M)))
+        chunk = self._chunk_for(M)
         with torch.cuda.device(self.device):
             need = int(self.lib.gpbo_ensemble_workspace_bytes(self.Np, chunk, M))
-            if need < 0:
-                raise _lib.GpboError("gpbo_ensemble_workspace_bytes: invalid sizes")
-            if self._work is None or self._work.numel() * 8 < need:
-                self._work = None
-                self._work = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
-            mean = sd = acq = None
-            if dense:
-                mean, sd, acq = (torch.empty(M, dtype=torch.float64, device=self.device) for _ in range(3))
-            st = self.lib.gpbo_ensemble_acq_f64(self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.S,
-                                                self.ls_h.ctypes.data_as(C.c_void_p), _lib.KERNEL_IDS[self.kernel],
-                                                self._ptr(self.U), self._ptr(self.alpha),
-                                                self.model_h.ctypes.data_as(C.c_void_p), kind, p0, p1, int(idx_offset), chunk,
-                                                self._ptr(mean), self._ptr(sd), self._ptr(acq), self._ptr(self._result),
-                                                self._ptr(self._work), need, self._stream())
-            _lib.check(st, "gpbo_ensemble_acq_f64")
-            r = self._result.cpu()   # synchronises
-        return EnsembleResult(float(r[:1].view(torch.float64)[0]), int(r[1]), int(r[2]), mean, sd, acq)
+            work = self._workspace("_work", need, free_first=True)
+            mean, sd, acq = self._dense(M, dense)
+            _lib.call(self.lib.gpbo_ensemble_acq_f64, Xsd, M, self.X, self.N, self.Np, self.d, self.S, self.ls_h, self._kid(),
+                      self.U, self.alpha, self.model_h, kind, p0, p1, int(idx_offset), chunk, mean, sd, acq, self._result,
+                      work, need, self._stream())
+            v, i, n = self.read_result(self._result)   # synchronises
+        return EnsembleResult(v, i, n, mean, sd, acq)

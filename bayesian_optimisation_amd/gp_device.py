@@ -215,8 +215,10 @@ class LikelihoodFits:
                                                ls0, ls_lower, ls_upper, noise0, noise_lower, noise_upper, **opts)
 
 
-class DeviceGP(LikelihoodFits):
-    """One BO step's surrogate on one GPU: factorise once, then score any number of candidates."""
+class DeviceSide:
+    """What DeviceGP and ensemble.DeviceEnsemble share: the device and the chunk, uploads, the grow-only workspaces, the input
+    checks and the pieces of an argument list that recur.  Tensors and arrays go into a library call as they are
+    (_lib.Pointer); a call that returns a status goes through _lib.call."""
 
     def __init__(self, device=None, chunk: int = DEFAULT_CHUNK):
         torch = _torch()
@@ -227,61 +229,8 @@ class DeviceGP(LikelihoodFits):
             raise ValueError(f"chunk must be a multiple of {_lib.CHUNK_GRANULE}")
         self.chunk = int(chunk)
         self.N = self.Np = self.d = 0
-        self.X = self.y = self.ls_h = None   # the observations and length scales of the last factorise() / load_state_dict()
-        self.jitter1 = self.jitter2 = 0.0
         self.kernel = "se"           # covariance family of the held factorisation (_lib.KERNEL_IDS)
-        self.n_appended = 0
-        self._owns_xy = False
-        self.K = self.U = self.alpha = None
-        # workspaces, kept from call to call and only ever grown (_workspace)
-        self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
-        self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = self._work_loo = None
-        self._work_nei = None
-        self._epoch = 0              # counts factorise() / append() / load_state_dict(): ThompsonPaths belong to one of them
-        self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
-        self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
-        self.U8, self._u8_valid = None, False                   # prepare_i8()
-        self._screen_mu = self._screen_var = self._bound_ub = None
-        self._fit_bufs = None
-        self._keep = self._keep_ard = None   # inputs of the last enqueued call, alive until the stream has consumed them
-        self.last_screen = None      # statistics of the last screened call (dict)
-        self.perm = None             # factorise(order="fps"): device int64 [N], row of the factorisation -> the caller's row
-        # the 32-byte result record and the factorisation's info word share one small buffer, so that a step can read
-        # both back with a single device-to-host copy (each copy is a host synchronisation)
-        self._status = torch.zeros(5, dtype=torch.int64, device=self.device)
-        self._result = self._status[:4]
-        self.info = self._status[4:5].view(torch.int32)[:1]
-        self._profile = C.c_void_p(0)
-        self.screen_cap = None       # fp32 screen: most survivors re-scored in fp64 before the plain fp64 pass takes over
-        self.profile_active = True   # False: the next scoring calls record no events (bench.py samples every k-th step)
 
-    # -- per-launch timing of the dominant kernel (bench.py) -----------------------------------------
-    def enable_profile(self, capacity: int = 4096):
-        p = C.c_void_p(0)
-        _lib.check(self.lib.gpbo_profile_create(int(capacity), C.byref(p)), "gpbo_profile_create")
-        self._profile = p
-
-    def reset_profile(self):
-        self.lib.gpbo_profile_reset(self._profile)
-
-    def _read_profile(self, name):
-        ms, n, c = C.c_double(0), C.c_int64(0), C.c_int64(0)
-        _lib.check(getattr(self.lib, name)(self._profile, C.byref(ms), C.byref(n), C.byref(c)), name)
-        return ms.value, n.value, c.value
-
-    def read_profile(self):
-        """(total ms, launches, candidates) summed over the recorded sigma/acquisition launches."""
-        return self._read_profile("gpbo_profile_read")
-
-    def read_profile_kstar(self):
-        """(total ms, launches, candidates) of the K(X*,X) launches recorded beside the variance launches."""
-        return self._read_profile("gpbo_profile_read_kstar")
-
-    def read_profile_qei(self):
-        """(total ms, launches, candidates) of the qEI launches recorded by score_qei()."""
-        return self._read_profile("gpbo_profile_read_qei")
-
-    # -- helpers -------------------------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -294,6 +243,7 @@ class DeviceGP(LikelihoodFits):
 
     @staticmethod
     def _ptr(t):
+        """The address of a tensor as a c_void_p (tests and tools; the calls of this package pass the tensor itself)."""
         return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
     def _candidates(self, Xs):
@@ -325,6 +275,119 @@ class DeviceGP(LikelihoodFits):
     def _kid(self) -> int:
         return _lib.KERNEL_IDS[self.kernel]
 
+    def _dense(self, M: int, dense: bool = True) -> tuple:
+        """The three dense fp64 outputs [M] of a scoring call, or three times None."""
+        if not dense:
+            return None, None, None
+        return tuple(self.torch.empty(M, dtype=self.torch.float64, device=self.device) for _ in range(3))
+
+    def _problem(self, X, y, ls, d_limits, positive: bool = False, host_y: bool = False) -> tuple:
+        """The one check of (X, y, length scales): (X on the device, y flat - on the device, or a host array with host_y -,
+        N, d, the length scales as a contiguous host array or None when ls is None).  d_limits: (largest d, message with
+        {d}) pairs, refused in that order; positive: the length scales must be positive."""
+        Xd = self._dev(X)
+        if Xd.dim() != 2:
+            raise ValueError("X must be (N, d)")
+        N, d = int(Xd.shape[0]), int(Xd.shape[1])
+        for max_d, message in d_limits:
+            if d > max_d:
+                raise ValueError(message.format(d=d))
+        if host_y:
+            # (a tensor is what nlml_hyper_cells_fn has always taken; no copy of an array that is fp64 already)
+            y = np.asarray(y.detach().cpu().numpy() if isinstance(y, self.torch.Tensor) else y, dtype=np.float64).reshape(-1)
+        else:
+            y = self._dev(y).reshape(-1)
+        if (y.size if host_y else y.numel()) != N:
+            raise ValueError("y must have one value per row of X")
+        if ls is None:
+            return Xd, y, N, d, None
+        ls_h = np.ascontiguousarray(np.asarray(ls, dtype=np.float64).reshape(-1))
+        if ls_h.size != d:
+            raise ValueError(f"length scales: expected {d} values, got {ls_h.size}")
+        if positive and not np.all(ls_h > 0):
+            raise ValueError("length scales must be positive")
+        return Xd, y, N, d, ls_h
+
+    def _factorise_into(self, Xd, yd, N, d, ls_h, kid, jitter1, jitter2, Np, K, U, alpha, info, work=None, wbytes=None):
+        """Enqueue gpbo_factorise_kern_f64 of (Xd, yd, ls_h) into K / U / alpha / info.  work: a workspace of wbytes as
+        gpbo_factorise_workspace_bytes(Np) reports them, or None for this object's own grow-only slot _work_fact."""
+        if work is None:
+            wbytes = int(self.lib.gpbo_factorise_workspace_bytes(Np))
+            work = self._workspace("_work_fact", wbytes)
+        _lib.call(self.lib.gpbo_factorise_kern_f64, Xd, yd, N, d, ls_h, kid, jitter1, jitter2, Np, K, U, alpha, info, work,
+                  wbytes, self._stream())
+
+    def read_result(self, result_tensor) -> tuple:
+        """(best value, best index, NaN count) of a gpbo_result record on the device (synchronises)."""
+        r = result_tensor.cpu()
+        best_val = float(r[:1].view(self.torch.float64)[0])
+        return best_val, int(r[1]), int(r[2])
+
+
+class DeviceGP(DeviceSide, LikelihoodFits):
+    """One BO step's surrogate on one GPU: factorise once, then score any number of candidates."""
+
+    def __init__(self, device=None, chunk: int = DEFAULT_CHUNK):
+        super().__init__(device, chunk)
+        torch = self.torch
+        self.X = self.y = self.ls_h = None   # the observations and length scales of the last factorise() / load_state_dict()
+        self.jitter1 = self.jitter2 = 0.0
+        self.n_appended = 0
+        self._owns_xy = False
+        self.K = self.U = self.alpha = None
+        # workspaces, kept from call to call and only ever grown (_workspace)
+        self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
+        self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = self._work_loo = None
+        self._work_nei = None
+        self._epoch = 0              # counts factorise() / append() / load_state_dict(): ThompsonPaths belong to one of them
+        self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
+        self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
+        self.U8, self._u8_valid = None, False                   # prepare_i8()
+        self._screen_mu = self._screen_var = self._bound_ub = None
+        self._fit_bufs = None
+        self._keep = self._keep_ard = None   # inputs of the last enqueued call, alive until the stream has consumed them
+        self.last_screen = None      # statistics of the last screened call (dict)
+        self.perm = None             # factorise(order="fps"): device int64 [N], row of the factorisation -> the caller's row
+        # the 32-byte result record and the factorisation's info word share one small buffer, so that a step can read
+        # both back with a single device-to-host copy (each copy is a host synchronisation)
+        self._status = torch.zeros(5, dtype=torch.int64, device=self.device)
+        self._result = self._status[:4]
+        self.info = self._status[4:5].view(torch.int32)[:1]
+        self._profile = C.c_void_p(0)
+        self.screen_cap = None       # fp32 screen: most survivors re-scored in fp64 before the plain fp64 pass takes over
+        self.profile_active = True   # False: the next scoring calls record no events (bench.py samples every k-th step)
+
+    # -- per-launch timing of the dominant kernel (bench.py) -----------------------------------------
+    def enable_profile(self, capacity: int = 4096):
+        p = C.c_void_p(0)
+        _lib.call(self.lib.gpbo_profile_create, int(capacity), C.byref(p))
+        self._profile = p
+
+    def reset_profile(self):
+        self.lib.gpbo_profile_reset(self._profile)
+
+    def _read_profile(self, name):
+        ms, n, c = C.c_double(0), C.c_int64(0), C.c_int64(0)
+        _lib.call(getattr(self.lib, name), self._profile, C.byref(ms), C.byref(n), C.byref(c))
+        return ms.value, n.value, c.value
+
+    def read_profile(self):
+        """(total ms, launches, candidates) summed over the recorded sigma/acquisition launches."""
+        return self._read_profile("gpbo_profile_read")
+
+    def read_profile_kstar(self):
+        """(total ms, launches, candidates) of the K(X*,X) launches recorded beside the variance launches."""
+        return self._read_profile("gpbo_profile_read_kstar")
+
+    def read_profile_qei(self):
+        """(total ms, launches, candidates) of the qEI launches recorded by score_qei()."""
+        return self._read_profile("gpbo_profile_read_qei")
+
+    # -- helpers -------------------------------------------------------------------------------
+    def _head(self) -> tuple:
+        """(X, N, Np, d, ls): the observations' run that opens the argument list of the calls on the held factorisation."""
+        return self.X, self.N, self.Np, self.d, self.ls_h
+
     def _read(self, res_tuple) -> ScoreResult:
         """The synchronous form of what a score_async* call returned (reads the result record: synchronises)."""
         res, mu, sigma, acq = res_tuple
@@ -352,20 +415,11 @@ class DeviceGP(LikelihoodFits):
         kid = _lib.kernel_id(kernel)
         if kernel != "se" and order != "arrival":
             raise ValueError(f"order='fps' serves score_bound(), which is not available with kernel={kernel!r}")
-        Xd = self._dev(X)
-        if Xd.dim() != 2:
-            raise ValueError("X must be (N, d)")
-        N, d = int(Xd.shape[0]), int(Xd.shape[1])
-        if d > _lib.MAX_D_ANY:
-            raise ValueError(f"d = {d} > {_lib.MAX_D_ANY} is not supported")
-        if kernel != "se" and d > _lib.MAX_D:
-            raise ValueError(f"kernel={kernel!r} needs d <= {_lib.MAX_D} (d = {d}): the any-d slow path is kernel='se' only")
-        yd = self._dev(y).reshape(-1)
-        if yd.numel() != N:
-            raise ValueError("y must have one value per row of X")
-        ls_h = np.ascontiguousarray(np.asarray(ls, dtype=np.float64).reshape(-1))
-        if ls_h.size != d:
-            raise ValueError(f"length scales: expected {d} values, got {ls_h.size}")
+        limits = [(_lib.MAX_D_ANY, f"d = {{d}} > {_lib.MAX_D_ANY} is not supported")]
+        if kernel != "se":
+            limits.append((_lib.MAX_D, f"kernel={kernel!r} needs d <= {_lib.MAX_D} (d = {{d}}): the any-d slow path is "
+                                       "kernel='se' only"))
+        Xd, yd, N, d, ls_h = self._problem(X, y, ls, limits)
         Np = int(self.lib.gpbo_padded_n(N))
         with torch.cuda.device(self.device):
             self.perm = None
@@ -376,16 +430,13 @@ class DeviceGP(LikelihoodFits):
                 self._workspace("_work_order", wob)
                 perm = torch.empty(N, dtype=torch.int64, device=self.device)
                 Xp, yp = torch.empty_like(Xd), torch.empty_like(yd)
-                st = self.lib.gpbo_fps_order_f64(self._ptr(Xd), self._ptr(yd), N, d, ls_h.ctypes.data_as(C.c_void_p), J,
-                                                 self._ptr(perm), self._ptr(Xp), self._ptr(yp), self._ptr(self._work_order),
-                                                 wob, self._stream())
-                _lib.check(st, "gpbo_fps_order_f64")
+                _lib.call(self.lib.gpbo_fps_order_f64, Xd, yd, N, d, ls_h, J, perm, Xp, yp, self._work_order, wob,
+                          self._stream())
                 # did the co-operative selection give up (a workgroup never scheduled) and install the arrival order?  The
                 # flag stays on the device until somebody asks (order_fell_back(), last_screen): no synchronisation here
                 if self._order_flag is None:
                     self._order_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-                _lib.check(self.lib.gpbo_fps_order_status(self._ptr(self._work_order), N, self._ptr(self._order_flag),
-                                                          self._stream()), "gpbo_fps_order_status")
+                _lib.call(self.lib.gpbo_fps_order_status, self._work_order, N, self._order_flag, self._stream())
                 Xd, yd, self.perm = Xp, yp, perm
             self.X, self.y, self.ls_h = Xd, yd, ls_h
             self.N, self.Np, self.d = N, Np, d
@@ -403,13 +454,7 @@ class DeviceGP(LikelihoodFits):
                 self._work_fact = None
             self._u32_valid = False
             self._u8_valid = False
-            wbytes = int(self.lib.gpbo_factorise_workspace_bytes(Np))
-            work = self._workspace("_work_fact", wbytes)
-            st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(yd), N, d, ls_h.ctypes.data_as(C.c_void_p), kid,
-                                                  jitter1, jitter2, Np, self._ptr(self.K), self._ptr(self.U),
-                                                  self._ptr(self.alpha), self._ptr(self.info), self._ptr(work), wbytes,
-                                                  self._stream())
-            _lib.check(st, "gpbo_factorise_kern_f64")
+            self._factorise_into(Xd, yd, N, d, ls_h, kid, jitter1, jitter2, Np, self.K, self.U, self.alpha, self.info)
             if check:
                 info = int(self.info.item())  # synchronises
                 if info != 0:
@@ -508,12 +553,8 @@ class DeviceGP(LikelihoodFits):
                 self.X, self.y, self._owns_xy = Xb, yb, True
             wbytes = int(self.lib.gpbo_append_workspace_bytes(self.Np))
             work = torch.empty(wbytes // 8, dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_append_f64(self._ptr(self.X), self._ptr(self.y), N, self.d,
-                                          self.ls_h.ctypes.data_as(C.c_void_p), self.jitter1, self.jitter2, self.Np,
-                                          self._ptr(xn), self._ptr(yn), self._ptr(self.K), self._ptr(self.U),
-                                          self._ptr(self.alpha), self._ptr(self.info), self._ptr(work), wbytes,
-                                          self._stream())
-            _lib.check(st, "gpbo_append_f64")
+            _lib.call(self.lib.gpbo_append_f64, self.X, self.y, N, self.d, self.ls_h, self.jitter1, self.jitter2, self.Np,
+                      xn, yn, self.K, self.U, self.alpha, self.info, work, wbytes, self._stream())
             self._u32_valid = False
             self._u8_valid = False
             if check:
@@ -636,19 +677,10 @@ class DeviceGP(LikelihoodFits):
                              f"kernel={self.kernel!r}")
         with torch.cuda.device(self.device):
             chunk, wbytes = self._ensure_post_workspace(M)
-            mu = sigma = acq = None
-            if dense:
-                mu = torch.empty(M, dtype=torch.float64, device=self.device)
-                sigma = torch.empty(M, dtype=torch.float64, device=self.device)
-                acq = torch.empty(M, dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_posterior_acq_kern_f64(
-                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d,
-                self.ls_h.ctypes.data_as(C.c_void_p), self._kid(), self._ptr(self.U), self._ptr(self.alpha), prior_var,
-                kind, p0, p1, float(diag_add), int(idx_offset), chunk, self._ptr(mu), self._ptr(sigma),
-                self._ptr(acq), self._ptr(self._result), self._ptr(self._work_post), wbytes,
-                self._profile if self.profile_active else None,
-                self._stream())
-            _lib.check(st, "gpbo_posterior_acq_kern_f64")
+            mu, sigma, acq = self._dense(M, dense)
+            _lib.call(self.lib.gpbo_posterior_acq_kern_f64, Xsd, M, *self._head(), self._kid(), self.U, self.alpha,
+                      prior_var, kind, p0, p1, float(diag_add), int(idx_offset), chunk, mu, sigma, acq, self._result,
+                      self._work_post, wbytes, self._profile if self.profile_active else None, self._stream())
         self._keep = Xsd  # keep the candidate tensor alive until the stream has consumed it
         return self._result, mu, sigma, acq
 
@@ -664,9 +696,7 @@ class DeviceGP(LikelihoodFits):
         with torch.cuda.device(self.device):
             if self.U32 is None or self.U32.shape[0] != Np32:
                 self.U32 = torch.empty((Np32, Np32), dtype=torch.float32, device=self.device)
-            st = self.lib.gpbo_prepare_f32(self._ptr(self.U), None, self.Np, self._ptr(self.U32), None, Np32,
-                                           self._stream())
-            _lib.check(st, "gpbo_prepare_f32")
+            _lib.call(self.lib.gpbo_prepare_f32, self.U, None, self.Np, self.U32, None, Np32, self._stream())
         self.Np32 = Np32
         self._u32_valid = True
         return self
@@ -682,8 +712,7 @@ class DeviceGP(LikelihoodFits):
                 raise _lib.GpboError("gpbo_prepare_i8_bytes: invalid size")
             if self.U8 is None or self.U8.numel() < need:
                 self.U8 = torch.empty(need, dtype=torch.uint8, device=self.device)
-            st = self.lib.gpbo_prepare_i8(self._ptr(self.U), self.Np, self._ptr(self.U8), need, self._stream())
-            _lib.check(st, "gpbo_prepare_i8")
+            _lib.call(self.lib.gpbo_prepare_i8, self.U, self.Np, self.U8, need, self._stream())
         self._u8_valid = True
         return self
 
@@ -713,12 +742,9 @@ class DeviceGP(LikelihoodFits):
             if self._screen_mu is None or self._screen_mu.numel() < M:
                 self._screen_mu = torch.empty(M, dtype=torch.float64, device=self.device)
                 self._screen_var = torch.empty(M, dtype=torch.float64, device=self.device)
-            mu = sigma = acq = None
-            if dense:
-                mu, sigma, acq = (torch.empty(M, dtype=torch.float64, device=self.device) for _ in range(3))
+            mu, sigma, acq = self._dense(M, dense)
             mu_w = mu if dense else self._screen_mu
             prof = self._profile if self.profile_active else None
-            lsp = self.ls_h.ctypes.data_as(C.c_void_p)
             if mode == "f32":
                 chunk = self._chunk_for(M, 1024)
                 need = int(self.lib.gpbo_posterior_workspace_bytes_f32(self.Np32, chunk, M))
@@ -727,21 +753,14 @@ class DeviceGP(LikelihoodFits):
                 need = int(self.lib.gpbo_posterior_workspace_bytes_i8(self.Np, chunk, M))
             self._workspace("_work_screen", need, free_first=True)
             if mode == "f32":
-                st = self.lib.gpbo_posterior_acq_f32(
-                    self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np32, self.d, lsp, self._ptr(self.U32),
-                    self._ptr(self.alpha), prior_var, kind, p0, p1, 0.0, int(idx_offset), chunk, self._ptr(mu_w),
-                    self._ptr(sigma), self._ptr(acq), self._ptr(self._screen_var), self._ptr(self._result),
-                    self._ptr(self._work_screen), need, prof, self._stream())
-                _lib.check(st, "gpbo_posterior_acq_f32")
+                _lib.call(self.lib.gpbo_posterior_acq_f32, Xsd, M, self.X, self.N, self.Np32, self.d, self.ls_h, self.U32,
+                          self.alpha, prior_var, kind, p0, p1, 0.0, int(idx_offset), chunk, mu_w, sigma, acq,
+                          self._screen_var, self._result, self._work_screen, need, prof, self._stream())
                 tau0 = float(self.SCREEN_TAU0)
             else:
                 fn = self.lib.gpbo_posterior_acq_i8c if mode == "i8c" else self.lib.gpbo_posterior_acq_i8
-                st = fn(
-                    self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, lsp, self._ptr(self.U8),
-                    self._ptr(self.alpha), prior_var, kind, p0, p1, int(idx_offset), chunk, self._ptr(mu_w),
-                    self._ptr(sigma), self._ptr(acq), self._ptr(self._screen_var), self._ptr(self._result),
-                    self._ptr(self._work_screen), need, prof, self._stream())
-                _lib.check(st, "gpbo_posterior_acq_" + mode)
+                _lib.call(fn, Xsd, M, *self._head(), self.U8, self.alpha, prior_var, kind, p0, p1, int(idx_offset), chunk,
+                          mu_w, sigma, acq, self._screen_var, self._result, self._work_screen, need, prof, self._stream())
                 tau0 = float(self.SCREEN_TAU0_I8C if mode == "i8c" else self.SCREEN_TAU0_I8)
             cap = self.screen_cap if self.screen_cap else max(4096, min(M, max(M // 16, 1 << 16)))
             chunk64 = self.SCREEN_CHUNK64
@@ -749,12 +768,9 @@ class DeviceGP(LikelihoodFits):
             self._workspace("_work_rescore", rbytes)
             stats = _lib.ScreenStats()
             stride = max(1, M // self.SCREEN_SAMPLE)
-            st = self.lib.gpbo_rescore_f64(
-                self._ptr(Xsd), M, self._ptr(mu_w), self._ptr(self._screen_var), self._ptr(self.X), self.N, self.Np,
-                self.d, lsp, self._ptr(self.U), self._ptr(self.alpha), prior_var, kind,
-                p0, p1, int(idx_offset), tau0, stride, cap, chunk64, self._ptr(self._result),
-                C.byref(stats), self._ptr(self._work_rescore), rbytes, self._stream())
-            _lib.check(st, "gpbo_rescore_f64")
+            _lib.call(self.lib.gpbo_rescore_f64, Xsd, M, mu_w, self._screen_var, *self._head(), self.U, self.alpha,
+                      prior_var, kind, p0, p1, int(idx_offset), tau0, stride, cap, chunk64, self._result, C.byref(stats),
+                      self._work_rescore, rbytes, self._stream())
             self.last_screen = dict(mode=mode, survivors=int(stats.survivors), rescored=int(stats.rescored),
                                     rounds=int(stats.rounds), fallback=bool(stats.fallback), tau=float(stats.tau),
                                     err_max=float(stats.err_max), candidates=M)
@@ -843,13 +859,9 @@ class DeviceGP(LikelihoodFits):
             chunk, wbytes = self._ensure_post_workspace(M)
             if self._bound_ub is None or self._bound_ub.numel() < M:
                 self._bound_ub = torch.empty(M, dtype=torch.float64, device=self.device)
-            lsp = self.ls_h.ctypes.data_as(C.c_void_p)
-            st = self.lib.gpbo_posterior_prefix_f64(
-                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, lsp, self._ptr(self.U),
-                self._ptr(self.alpha), prior_var, kind, p0, p1, int(idx_offset), chunk, J, None, None,
-                self._ptr(self._bound_ub), self._ptr(self._result), self._ptr(self._work_post), wbytes,
-                self._profile if self.profile_active else None, self._stream())
-            _lib.check(st, "gpbo_posterior_prefix_f64")
+            _lib.call(self.lib.gpbo_posterior_prefix_f64, Xsd, M, *self._head(), self.U, self.alpha, prior_var, kind, p0, p1,
+                      int(idx_offset), chunk, J, None, None, self._bound_ub, self._result, self._work_post, wbytes,
+                      self._profile if self.profile_active else None, self._stream())
             # every first-level survivor may go on to the second-level bound (N/4 rows: 1/16 of a plain pass per candidate -
             # cheaper than falling back even if ALL of them survive); LCB(explore=10) on the headline workload leaves 256k
             # of 2^21: 24 ms through the second level against 518 ms through the plain pass (tools/bound_cap_probe.py)
@@ -859,12 +871,9 @@ class DeviceGP(LikelihoodFits):
             self._workspace("_work_rescore", rbytes)
             stats = _lib.ScreenStats()
             stride = max(1, M // self.SCREEN_SAMPLE)
-            st = self.lib.gpbo_bound_select_f64(
-                self._ptr(Xsd), M, self._ptr(self._bound_ub), self._ptr(self.X), self.N, self.Np, self.d, lsp,
-                self._ptr(self.U), self._ptr(self.alpha), prior_var, kind, p0, p1, int(idx_offset), stride, cap,
-                chunk64, J2, self._ptr(self._result), C.byref(stats), self._ptr(self._work_rescore), rbytes,
-                self._stream())
-            _lib.check(st, "gpbo_bound_select_f64")
+            _lib.call(self.lib.gpbo_bound_select_f64, Xsd, M, self._bound_ub, *self._head(), self.U, self.alpha, prior_var,
+                      kind, p0, p1, int(idx_offset), stride, cap, chunk64, J2, self._result, C.byref(stats),
+                      self._work_rescore, rbytes, self._stream())
             self.last_screen = dict(mode="bound", order="arrival (fps fell back)" if self.order_fell_back() else self.order, prefix=J, prefix2=J2, survivors=int(stats.survivors),
                                     rescored=int(stats.rescored), rounds=int(stats.rounds), fallback=bool(stats.fallback),
                                     threshold=float(stats.tau), candidates=M)
@@ -897,12 +906,9 @@ class DeviceGP(LikelihoodFits):
             need = int(self.lib.gpbo_qei_workspace_bytes(self.Np, chunk, M))
             self._workspace("_work_qei", need)
             qei = torch.empty(M // 8, dtype=torch.float64, device=self.device) if dense else None
-            st = self.lib.gpbo_posterior_qei_f64(
-                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
-                self._ptr(self.U), self._ptr(self.alpha), prior_var, float(f_best), float(xi), self._ptr(Zd), S,
-                int(batch_offset), chunk, self._ptr(qei), self._ptr(self._result), self._ptr(self._work_qei), need,
-                self._profile if self.profile_active else None, self._stream())
-            _lib.check(st, "gpbo_posterior_qei_f64")
+            _lib.call(self.lib.gpbo_posterior_qei_f64, Xsd, M, *self._head(), self.U, self.alpha, prior_var, float(f_best),
+                      float(xi), Zd, S, int(batch_offset), chunk, qei, self._result, self._work_qei, need,
+                      self._profile if self.profile_active else None, self._stream())
         self._keep = (Xsd, Zd)
         return self._result, qei
 
@@ -945,12 +951,9 @@ class DeviceGP(LikelihoodFits):
             # members, values, the result record and the info word in one buffer: one device-to-host copy
             out = torch.zeros(2 * q + 5, dtype=torch.int64, device=self.device)
             idx, val, res, info = out[:q], out[q: 2 * q], out[2 * q: 2 * q + 4], out[2 * q + 4:]
-            st = self.lib.gpbo_select_batch_f64(
-                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
-                self._ptr(self.U), self._ptr(self.alpha), self.jitter1, self.jitter2, float(prior_var), kind, p0, p1, q,
-                fkind, fl, self._ptr(mu), self._ptr(sigma), int(idx_offset), self._ptr(idx), self._ptr(val),
-                self._ptr(res), self._ptr(info), self._ptr(work), need, self._stream())
-            _lib.check(st, "gpbo_select_batch_f64")
+            _lib.call(self.lib.gpbo_select_batch_f64, Xsd, M, *self._head(), self.U, self.alpha, self.jitter1, self.jitter2,
+                      float(prior_var), kind, p0, p1, q, fkind, fl, mu, sigma, int(idx_offset), idx, val, res, info, work,
+                      need, self._stream())
             h = out.cpu()   # synchronises: Xsd has been consumed
         return BatchResult(indices=h[:q].numpy().copy(), values=h[q: 2 * q].view(torch.float64).numpy().copy(),
                            nan_count=int(h[2 * q + 2]), info=int(h[2 * q + 4:].view(torch.int32)[0]), mu=mu, sigma=sigma)
@@ -1001,11 +1004,8 @@ class DeviceGP(LikelihoodFits):
             V = torch.empty((n_paths, self.Np), dtype=torch.float64, device=self.device)
             need = int(self.lib.gpbo_thompson_weights_workspace_bytes(self.Np, n_features, n_paths))
             work = self._workspace("_work_thompson", need)
-            st = self.lib.gpbo_thompson_weights_f64(
-                self._ptr(self.X), self._ptr(self.y), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
-                self._ptr(self.U), self.jitter1, self.jitter2, self._ptr(om), self._ptr(ph), self._ptr(Wd), self._ptr(Ed),
-                n_features, n_paths, self._ptr(V), self._ptr(work), need, self._stream())
-            _lib.check(st, "gpbo_thompson_weights_f64")
+            _lib.call(self.lib.gpbo_thompson_weights_f64, self.X, self.y, self.N, self.Np, self.d, self.ls_h, self.U,
+                      self.jitter1, self.jitter2, om, ph, Wd, Ed, n_features, n_paths, V, work, need, self._stream())
         self._keep = Ed   # alive until the stream has consumed it
         return ThompsonPaths(om, ph, Wd, V, n_paths, n_features, seed, (id(self), self._epoch))
 
@@ -1027,12 +1027,8 @@ class DeviceGP(LikelihoodFits):
             work = self._workspace("_work_thompson", need)
             f = torch.empty((S, M), dtype=torch.float64, device=self.device) if dense else None
             out = torch.zeros(3 * S, dtype=torch.int64, device=self.device)   # indices | values | NaN counts: one copy
-            st = self.lib.gpbo_thompson_paths_f64(
-                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
-                self._ptr(paths.omega), self._ptr(paths.phase), self._ptr(paths.W), self._ptr(paths.V), F, S, int(idx_offset),
-                self._ptr(f), M, self._ptr(out[:S]), self._ptr(out[S: 2 * S]), self._ptr(out[2 * S:]), self._ptr(work), need,
-                self._stream())
-            _lib.check(st, "gpbo_thompson_paths_f64")
+            _lib.call(self.lib.gpbo_thompson_paths_f64, Xsd, M, *self._head(), paths.omega, paths.phase, paths.W, paths.V, F,
+                      S, int(idx_offset), f, M, out[:S], out[S: 2 * S], out[2 * S:], work, need, self._stream())
             h = out.cpu()   # synchronises: Xsd has been consumed
         res = ThompsonResult(indices=h[:S].numpy().copy(), values=h[S: 2 * S].view(torch.float64).numpy().copy(),
                              nan_counts=h[2 * S:].numpy().copy(), f=f)
@@ -1081,13 +1077,7 @@ class DeviceGP(LikelihoodFits):
             U0 = torch.empty((Np, Np), dtype=torch.float64, device=self.device)
             alpha0 = torch.empty(Np, dtype=torch.float64, device=self.device)
             info0 = torch.zeros(1, dtype=torch.int32, device=self.device)
-            wbytes = int(self.lib.gpbo_factorise_workspace_bytes(Np))
-            work = self._workspace("_work_fact", wbytes)
-            st = self.lib.gpbo_factorise_kern_f64(self._ptr(self.X), self._ptr(self.y), N, self.d,
-                                                  self.ls_h.ctypes.data_as(C.c_void_p), self._kid(), delta, 0.0, Np,
-                                                  self._ptr(K0d), self._ptr(U0), self._ptr(alpha0), self._ptr(info0),
-                                                  self._ptr(work), wbytes, self._stream())
-            _lib.check(st, "gpbo_factorise_kern_f64")
+            self._factorise_into(self.X, self.y, N, self.d, self.ls_h, self._kid(), delta, 0.0, Np, K0d, U0, alpha0, info0)
             Zd, Ed = self._dev(Z), self._dev(E)
             A = torch.empty((S, Np), dtype=torch.float64, device=self.device)
             F = torch.empty((S, Np), dtype=torch.float64, device=self.device)
@@ -1095,10 +1085,8 @@ class DeviceGP(LikelihoodFits):
             need = int(self.lib.gpbo_nei_fantasies_workspace_bytes(Np, S))
             wn = self._workspace("_work_nei", need)
             noise_sd = float(np.sqrt(max((self.jitter1 + self.jitter2) - delta, 0.0)))
-            st = self.lib.gpbo_nei_fantasies_f64(self._ptr(K0d), self._ptr(U0), self._ptr(self.U), self._ptr(self.y), N, Np,
-                                                 self._ptr(Zd), self._ptr(Ed), noise_sd, S, self._ptr(A), self._ptr(F),
-                                                 self._ptr(best), self._ptr(wn), need, self._stream())
-            _lib.check(st, "gpbo_nei_fantasies_f64")
+            _lib.call(self.lib.gpbo_nei_fantasies_f64, K0d, U0, self.U, self.y, N, Np, Zd, Ed, noise_sd, S, A, F, best, wn,
+                      need, self._stream())
             info = int(info0.item())   # synchronises: Zd and Ed have been consumed
         if info != 0:
             raise np.linalg.LinAlgError(f"the noise-free twin (k(X,X) + {delta!r} I) is not positive definite (pivot {info} of "
@@ -1133,12 +1121,9 @@ class DeviceGP(LikelihoodFits):
                 acq = torch.empty(M, dtype=torch.float64, device=self.device)
                 sigma = torch.empty(M, dtype=torch.float64, device=self.device)
                 mu = torch.empty((S, M), dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_posterior_nei_kern_f64(
-                self._ptr(Xsd), M, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
-                self._kid(), self._ptr(fantasies.U0), self._ptr(fantasies.A), self._ptr(bd), S, 1.0 + fantasies.delta, xi,
-                int(idx_offset), chunk, self._ptr(mu), M, self._ptr(sigma), self._ptr(acq), self._ptr(self._result),
-                self._ptr(work), need, self._stream())
-            _lib.check(st, "gpbo_posterior_nei_kern_f64")
+            _lib.call(self.lib.gpbo_posterior_nei_kern_f64, Xsd, M, *self._head(), self._kid(), fantasies.U0, fantasies.A, bd,
+                      S, 1.0 + fantasies.delta, xi, int(idx_offset), chunk, mu, M, sigma, acq, self._result, work, need,
+                      self._stream())
             v, i, n = self.read_result(self._result)   # synchronises: Xsd has been consumed
         if check and not int(idx_offset) <= i < int(idx_offset) + M:
             raise IndexError(NAN_ACQUISITION)
@@ -1180,12 +1165,8 @@ class DeviceGP(LikelihoodFits):
             work = self._workspace("_work_refine", need)
             vals = torch.empty((3, P), dtype=torch.float64, device=self.device)
             grads = torch.empty((3, P, self.d), dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_posterior_grad_f64(
-                self._ptr(Xd), P, self._ptr(self.X), self.N, self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p),
-                self._ptr(self.U), self._ptr(self.alpha), float(prior_var), kind, p0, p1, self._ptr(vals[0]),
-                self._ptr(vals[1]), self._ptr(vals[2]), self._ptr(grads[0]), self._ptr(grads[1]), self._ptr(grads[2]),
-                self._ptr(work), need, self._stream())
-            _lib.check(st, "gpbo_posterior_grad_f64")
+            _lib.call(self.lib.gpbo_posterior_grad_f64, Xd, P, *self._head(), self.U, self.alpha, float(prior_var), kind, p0,
+                      p1, vals[0], vals[1], vals[2], grads[0], grads[1], grads[2], work, need, self._stream())
         self._keep = Xd
         return GradResult(vals[0], vals[1], vals[2], grads[0], grads[1], grads[2])
 
@@ -1209,12 +1190,8 @@ class DeviceGP(LikelihoodFits):
             vals = torch.empty((3, P), dtype=torch.float64, device=self.device)
             accepted = torch.empty(P, dtype=torch.int32, device=self.device)
             res = torch.zeros(4, dtype=torch.int64, device=self.device)
-            st = self.lib.gpbo_refine_f64(
-                self._ptr(x), P, lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), self._ptr(self.X), self.N,
-                self.Np, self.d, self.ls_h.ctypes.data_as(C.c_void_p), self._ptr(self.U), self._ptr(self.alpha),
-                float(prior_var), kind, p0, p1, iters, step0, self._ptr(vals[0]), self._ptr(vals[1]), self._ptr(accepted),
-                self._ptr(vals[2]), self._ptr(res), self._ptr(work), need, self._stream())
-            _lib.check(st, "gpbo_refine_f64")
+            _lib.call(self.lib.gpbo_refine_f64, x, P, lo, hi, *self._head(), self.U, self.alpha, float(prior_var), kind, p0,
+                      p1, iters, step0, vals[0], vals[1], accepted, vals[2], res, work, need, self._stream())
             v, i, n = self.read_result(res)   # synchronises
         return RefineResult(x=x, acq=vals[0], acq0=vals[1], accepted=accepted, pg=vals[2], best=i, best_val=v, nan_count=n)
 
@@ -1258,11 +1235,6 @@ class DeviceGP(LikelihoodFits):
         best_val = float(r[:1].view(self.torch.float64)[0])
         return best_val, int(r[1]), int(r[2]), int(r[4:5].view(self.torch.int32)[0])
 
-    def read_result(self, result_tensor) -> tuple:
-        r = result_tensor.cpu()  # synchronises
-        best_val = float(r[:1].view(self.torch.float64)[0])
-        return best_val, int(r[1]), int(r[2])
-
     def score(self, Xs, **kw) -> ScoreResult:
         return self._read(self.score_async(Xs, **kw))
 
@@ -1276,10 +1248,8 @@ class DeviceGP(LikelihoodFits):
             acq = torch.empty(M, dtype=torch.float64, device=self.device)
             wbytes = int(self.lib.gpbo_acq_workspace_bytes())
             work = torch.empty(wbytes // 8 + 32, dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_acq_argmax_f64(self._ptr(mu), self._ptr(sigma), M, kind, p0, p1, int(idx_offset),
-                                              self._ptr(acq), self._ptr(self._result), self._ptr(work), wbytes,
-                                              self._stream())
-            _lib.check(st, "gpbo_acq_argmax_f64")
+            _lib.call(self.lib.gpbo_acq_argmax_f64, mu, sigma, M, kind, p0, p1, int(idx_offset), acq, self._result, work,
+                      wbytes, self._stream())
             v, i, n = self.read_result(self._result)
         return ScoreResult(v, i, n, mu, sigma, acq)
 
@@ -1323,22 +1293,17 @@ class DeviceGP(LikelihoodFits):
                 # pinned against the reference's float32 ties (golden g4_ard_n2) like the in-LDS kernel it replaced
                 out = torch.empty(G, dtype=torch.float64 if logdet else torch.float32, device=self.device)
                 fn = self.lib.gpbo_nlml_grid_wave_logdet_f64 if logdet else self.lib.gpbo_nlml_grid_wave_f64
-                st = fn(self._ptr(Xd), self._ptr(yd), N, d, self._ptr(cells), G, float(jitter), self._ptr(out), self._stream())
-                _lib.check(st, "gpbo_nlml_grid_wave_logdet_f64" if logdet else "gpbo_nlml_grid_wave_f64")
+                _lib.call(fn, Xd, yd, N, d, cells, G, float(jitter), out, self._stream())
             elif N > self.ARD_LDS_MAX_N or logdet:
                 # one persistent workgroup per cell, the whole factorisation in one launch (csrc/ard.hip, round 5)
                 out = torch.empty(G, dtype=torch.float64 if logdet else torch.float32, device=self.device)
                 need = int(self.lib.gpbo_nlml_grid_batched_workspace_bytes(N, G))
                 self._workspace("_work_ard", need, free_first=True)
                 fn = self.lib.gpbo_nlml_grid_batched_logdet_f64 if logdet else self.lib.gpbo_nlml_grid_batched_f64
-                st = fn(self._ptr(Xd), self._ptr(yd), N, d, self._ptr(cells), G, float(jitter), self._ptr(out),
-                        self._ptr(self._work_ard), need, self._stream())
-                _lib.check(st, "gpbo_nlml_grid_batched_logdet_f64" if logdet else "gpbo_nlml_grid_batched_f64")
+                _lib.call(fn, Xd, yd, N, d, cells, G, float(jitter), out, self._work_ard, need, self._stream())
             else:
                 out = torch.empty(G, dtype=torch.float32, device=self.device)
-                st = self.lib.gpbo_nlml_grid_f64(self._ptr(Xd), self._ptr(yd), N, d, self._ptr(cells), G, float(jitter),
-                                                 self._ptr(out), self._stream())
-                _lib.check(st, "gpbo_nlml_grid_f64")
+                _lib.call(self.lib.gpbo_nlml_grid_f64, Xd, yd, N, d, cells, G, float(jitter), out, self._stream())
             self._keep_ard = (Xd, yd, cells)   # alive until the stream has consumed them
         return out
 
@@ -1368,32 +1333,17 @@ class DeviceGP(LikelihoodFits):
     def _fit_problem(self, X, y, ls, kernel):
         """The input check of the two likelihood calls: (kernel id, X and y on the device, N, d, length scales on the host)."""
         kid = _lib.kernel_id(kernel)
-        Xd, yd = self._dev(X), self._dev(y).reshape(-1)
-        if Xd.dim() != 2:
-            raise ValueError("X must be (N, d)")
-        N, d = int(Xd.shape[0]), int(Xd.shape[1])
-        if d > _lib.MAX_D:
-            raise ValueError(f"the likelihood gradient supports d <= {_lib.MAX_D}, got {d}")
-        if yd.numel() != N:
-            raise ValueError("y must have one value per row of X")
-        ls_h = np.ascontiguousarray(np.asarray(ls, dtype=np.float64).reshape(-1))
-        if ls_h.size != d:
-            raise ValueError(f"length scales: expected {d} values, got {ls_h.size}")
-        if not np.all(ls_h > 0):
-            raise ValueError("length scales must be positive")
-        return kid, Xd, yd, N, d, ls_h
+        limit = (_lib.MAX_D, f"the likelihood gradient supports d <= {_lib.MAX_D}, got {{d}}")
+        return (kid, *self._problem(X, y, ls, [limit], positive=True))
 
     def _fit_factorise(self, kid, Xd, yd, N, d, ls_h, jitter):
         """K = k(X,X) + jitter I factorised into the fit's own buffers (enqueued; inside torch.cuda.device(self.device)).
-        Returns (buffers, padded N, pointer to the length scales)."""
+        Returns (buffers, padded N)."""
         Np = int(self.lib.gpbo_padded_n(N))
         fb = self._fit_buffers(Np, d)
-        lsp = ls_h.ctypes.data_as(C.c_void_p)
-        st = self.lib.gpbo_factorise_kern_f64(self._ptr(Xd), self._ptr(yd), N, d, lsp, kid, float(jitter), 0.0, Np,
-                                              self._ptr(fb["K"]), self._ptr(fb["U"]), self._ptr(fb["alpha"]),
-                                              self._ptr(fb["info"]), self._ptr(fb["work_fact"]), fb["wf"], self._stream())
-        _lib.check(st, "gpbo_factorise_kern_f64")
-        return fb, Np, lsp
+        self._factorise_into(Xd, yd, N, d, ls_h, kid, float(jitter), 0.0, Np, fb["K"], fb["U"], fb["alpha"], fb["info"],
+                             fb["work_fact"], fb["wf"])
+        return fb, Np
 
     def nlml_and_grad(self, X, y, ls, jitter: float = JITTER_KERNEL, kernel: str = "se"):
         """(NLML, d NLML / d log ls [d]) of K = k(X,X) + jitter I - the "logdet" likelihood and its gradient - from a
@@ -1401,11 +1351,9 @@ class DeviceGP(LikelihoodFits):
         output when K is not positive definite.  d <= 16.  kernel: the covariance family k (factorise())."""
         kid, Xd, yd, N, d, ls_h = self._fit_problem(X, y, ls, kernel)
         with self.torch.cuda.device(self.device):
-            fb, Np, lsp = self._fit_factorise(kid, Xd, yd, N, d, ls_h, jitter)
-            st = self.lib.gpbo_nlml_grad_kern_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N,
-                                                  Np, d, lsp, kid, self._ptr(fb["info"]), self._ptr(fb["out"]),
-                                                  self._ptr(fb["work_grad"]), fb["wg"], self._stream())
-            _lib.check(st, "gpbo_nlml_grad_kern_f64")
+            fb, Np = self._fit_factorise(kid, Xd, yd, N, d, ls_h, jitter)
+            _lib.call(self.lib.gpbo_nlml_grad_kern_f64, fb["U"], fb["alpha"], yd, Xd, N, Np, d, ls_h, kid, fb["info"],
+                      fb["out"], fb["work_grad"], fb["wg"], self._stream())
             out = fb["out"][: 1 + d].cpu().numpy()   # synchronises
         return float(out[0]), out[1:].copy()
 
@@ -1434,7 +1382,7 @@ class DeviceGP(LikelihoodFits):
             raise ValueError(f"noise must be positive and finite, got {noise!r}")
         flags = (_lib.HYPER_MEAN if fit_mean else 0) | (_lib.HYPER_SCALE if fit_scale else 0)
         with torch.cuda.device(self.device):
-            fb, Np, lsp = self._fit_factorise(kid, Xd, yd, N, d, ls_h, noise)
+            fb, Np = self._fit_factorise(kid, Xd, yd, N, d, ls_h, noise)
             if "work_hyper" not in fb:
                 wh = int(self.lib.gpbo_nlml_hyper_workspace_bytes(Np, fb["d"]))
                 if wh < 0:
@@ -1442,11 +1390,8 @@ class DeviceGP(LikelihoodFits):
                 fb["work_hyper"] = torch.empty((wh + 7) // 8, dtype=torch.float64, device=self.device)
                 fb["wh"] = wh
                 fb["out_hyper"] = torch.empty(4 + fb["d"], dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_nlml_hyper_kern_f64(self._ptr(fb["U"]), self._ptr(fb["alpha"]), self._ptr(yd), self._ptr(Xd), N,
-                                                   Np, d, lsp, kid, noise, flags, self._ptr(fb["info"]),
-                                                   self._ptr(fb["out_hyper"]), None, self._ptr(fb["work_hyper"]), fb["wh"],
-                                                   self._stream())
-            _lib.check(st, "gpbo_nlml_hyper_kern_f64")
+            _lib.call(self.lib.gpbo_nlml_hyper_kern_f64, fb["U"], fb["alpha"], yd, Xd, N, Np, d, ls_h, kid, noise, flags,
+                      fb["info"], fb["out_hyper"], None, fb["work_hyper"], fb["wh"], self._stream())
             out = fb["out_hyper"][: 4 + d].cpu().numpy()   # synchronises
         return float(out[0]), out[1: 2 + d].copy(), float(out[2 + d]), float(out[3 + d])
 
@@ -1463,15 +1408,8 @@ class DeviceGP(LikelihoodFits):
         describes the values).  route: None (hyper_cells_route), "wave" or "loop"."""
         torch = self.torch
         kid = _lib.kernel_id(kernel)
-        Xd = self._dev(X)
-        if Xd.dim() != 2:
-            raise ValueError("X must be (N, d)")
-        N, d = int(Xd.shape[0]), int(Xd.shape[1])
-        if d > _lib.MAX_D:
-            raise ValueError(f"the likelihood of hyperparameter cells supports d <= {_lib.MAX_D}, got {d}")
-        y_h = (y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)).astype(np.float64).reshape(-1)
-        if y_h.size != N:
-            raise ValueError("y must have one value per row of X")
+        limit = (_lib.MAX_D, f"the likelihood of hyperparameter cells supports d <= {_lib.MAX_D}, got {{d}}")
+        Xd, y_h, N, d, _ = self._problem(X, y, None, [limit], host_y=True)
         route = self.hyper_cells_route(N, kernel) if route is None else route
         if route not in ("wave", "loop") or (route == "wave" and self.hyper_cells_route(N, kernel) != "wave"):
             raise ValueError(f"route {route!r} is not available for N = {N}, kernel={kernel!r}")
@@ -1494,9 +1432,7 @@ class DeviceGP(LikelihoodFits):
             with torch.cuda.device(self.device):
                 cd = torch.from_numpy(c).to(self.device)
                 out = torch.empty((len(c), 3), dtype=torch.float64, device=self.device)
-                st = self.lib.gpbo_nlml_hyper_cells_f64(self._ptr(Xd), self._ptr(yd), N, d, self._ptr(cd), len(c), kid, flags,
-                                                        self._ptr(out), self._stream())
-                _lib.check(st, "gpbo_nlml_hyper_cells_f64")
+                _lib.call(self.lib.gpbo_nlml_hyper_cells_f64, Xd, yd, N, d, cd, len(c), kid, flags, out, self._stream())
                 res = out.cpu().numpy()   # synchronises: the one read-back
             res[:, 1] += shift
             return res
@@ -1536,10 +1472,8 @@ class DeviceGP(LikelihoodFits):
             need = int(self.lib.gpbo_loo_workspace_bytes(self.Np))
             work = self._workspace("_work_loo", need)
             out = torch.empty((3, self.N), dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_loo_f64(self._ptr(self.U), self._ptr(self.alpha), self._ptr(self.y), self.N, self.Np, scale2,
-                                       self._ptr(out[0]), self._ptr(out[1]), self._ptr(out[2]), self._ptr(work), need,
-                                       self._stream())
-            _lib.check(st, "gpbo_loo_f64")
+            _lib.call(self.lib.gpbo_loo_f64, self.U, self.alpha, self.y, self.N, self.Np, scale2, out[0], out[1], out[2], work,
+                      need, self._stream())
             if self.perm is not None:   # row i of the factorisation is the caller's row perm[i]
                 back = torch.empty_like(out)
                 back[:, self.perm[: self.N]] = out
@@ -1567,9 +1501,7 @@ class DeviceGP(LikelihoodFits):
         ls_h = np.ascontiguousarray(np.asarray(ls, dtype=np.float64).reshape(-1))
         with torch.cuda.device(self.device):
             Kp = torch.empty((npad, npad), dtype=torch.float64, device=self.device)
-            st = self.lib.gpbo_kxx_kern_f64(self._ptr(Pd), n, d, ls_h.ctypes.data_as(C.c_void_p), self._kid(), jitter1, jitter2,
-                                            self._ptr(Kp), npad, self._stream())
-            _lib.check(st, "gpbo_kxx_kern_f64")
+            _lib.call(self.lib.gpbo_kxx_kern_f64, Pd, n, d, ls_h, self._kid(), jitter1, jitter2, Kp, npad, self._stream())
             return Kp[:n, :n].cpu().numpy()
 
     def cov_meas_pred_host(self, Xs, diag_add: float = 0.0) -> np.ndarray:
@@ -1582,13 +1514,9 @@ class DeviceGP(LikelihoodFits):
             kst = torch.empty((self.Np, ldk), dtype=torch.float64, device=self.device)
             mup = torch.empty((self.Np // 64, ldk), dtype=torch.float64, device=self.device)
             xsc = torch.empty((self.Np, self.d), dtype=torch.float64, device=self.device)
-            lsp = self.ls_h.ctypes.data_as(C.c_void_p)
-            _lib.check(self.lib.gpbo_scale_points_f64(self._ptr(self.X), self.N, self.Np, self.d, lsp, self._ptr(xsc),
-                                                      self._stream()), "gpbo_scale_points_f64")
-            st = self.lib.gpbo_kstar_mu_kern_f64(self._ptr(Xsd), M, self._ptr(xsc), self.N, self.Np, self.d, lsp, self._kid(),
-                                                 self._ptr(self.alpha), float(diag_add), 0, self._ptr(kst), ldk,
-                                                 self._ptr(mup), self._stream())
-            _lib.check(st, "gpbo_kstar_mu_kern_f64")
+            _lib.call(self.lib.gpbo_scale_points_f64, *self._head(), xsc, self._stream())
+            _lib.call(self.lib.gpbo_kstar_mu_kern_f64, Xsd, M, xsc, self.N, self.Np, self.d, self.ls_h, self._kid(),
+                      self.alpha, float(diag_add), 0, kst, ldk, mup, self._stream())
             Kf = kst[: self.N, :M].t().contiguous().cpu().numpy()
         p = self._perm_host()
         if p is None:

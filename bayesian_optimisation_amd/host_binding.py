@@ -31,10 +31,6 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else C.c_void_p(0)
-
-
 def _problem(X, y, ls, Xs=None):
     """(X, y, ls, N, d) - with candidates (X, y, ls, Xs, N, d, M) - as contiguous fp64 arrays: the one shape check of the
     binding, made before anything touches the device."""
@@ -51,14 +47,13 @@ class _Result:
     """The gpbo_result record and the info word a host entry writes, and their decoding."""
 
     def __init__(self):
-        self._res = (C.c_int64 * 4)()
-        self._info = C.c_int32(0)
-        self.res_ptr = C.cast(self._res, C.c_void_p)
-        self.info_ptr = C.cast(C.pointer(self._info), C.c_void_p)
+        self.res = (C.c_int64 * 4)()
+        self.info = C.c_int32(0)
+        self.info_ptr = C.byref(self.info)
 
     def decode(self) -> dict:
-        best_val = float(np.frombuffer(self._res, dtype=np.float64, count=1)[0])
-        return dict(best_val=best_val, best_idx=int(self._res[1]), nan_count=int(self._res[2]), info=int(self._info.value))
+        best_val = float(np.frombuffer(self.res, dtype=np.float64, count=1)[0])
+        return dict(best_val=best_val, best_idx=int(self.res[1]), nan_count=int(self.res[2]), info=int(self.info.value))
 
 
 def nlml_grid(X, y, ls_cells, jitter: float = JITTER_KERNEL, lib=None, likelihood: str = "reference") -> np.ndarray:
@@ -74,8 +69,7 @@ def nlml_grid(X, y, ls_cells, jitter: float = JITTER_KERNEL, lib=None, likelihoo
     out = np.empty(len(cells), dtype=np.float64 if logdet else np.float32)
     _lib.note_hip_use()
     fn = lib.gpbo_nlml_grid_logdet_host_f64 if logdet else lib.gpbo_nlml_grid_host_f64
-    _lib.check(fn(_ptr(X), _ptr(y), N, d, _ptr(cells), len(cells), float(jitter), _ptr(out)),
-               "gpbo_nlml_grid_logdet_host_f64" if logdet else "gpbo_nlml_grid_host_f64")
+    _lib.call(fn, X, y, N, d, cells, len(cells), float(jitter), out)
     return out
 
 
@@ -88,8 +82,7 @@ def nlml_and_grad(X, y, ls, jitter: float = JITTER_KERNEL, lib=None, kernel: str
     X, y, ls, N, d = _problem(X, y, ls)
     out = np.empty(1 + d)
     _lib.note_hip_use()
-    _lib.check(lib.gpbo_nlml_grad_host_kern_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(jitter), _ptr(out)),
-               "gpbo_nlml_grad_host_kern_f64")
+    _lib.call(lib.gpbo_nlml_grad_host_kern_f64, X, y, N, d, ls, kid, float(jitter), out)
     return float(out[0]), out[1:].copy()
 
 
@@ -106,8 +99,7 @@ def nlml_hyper(X, y, ls, noise: float, fit_mean: bool = True, fit_scale: bool = 
     flags = (_lib.HYPER_MEAN if fit_mean else 0) | (_lib.HYPER_SCALE if fit_scale else 0)
     out = np.empty(4 + d)
     _lib.note_hip_use()
-    _lib.check(lib.gpbo_nlml_hyper_host_kern_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(noise), flags, _ptr(out)),
-               "gpbo_nlml_hyper_host_kern_f64")
+    _lib.call(lib.gpbo_nlml_hyper_host_kern_f64, X, y, N, d, ls, kid, float(noise), flags, out)
     return float(out[0]), out[1: 2 + d].copy(), float(out[2 + d]), float(out[3 + d])
 
 
@@ -128,10 +120,8 @@ def select_next(X, y, ls, Xs, acquisition: str = "lcb", explore: float = 4.0, f_
     if diag_add is None:
         diag_add = SurrogateModel(kernel, jitter1, jitter2).diag_add(Xs.shape, X.shape)   # point_selector.py:173 shape quirk
     _lib.note_hip_use()
-    st = lib.gpbo_select_next_host_kern_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(jitter1), float(jitter2), _ptr(Xs), M,
-                                            kind, p0, p1, float(diag_add), int(chunk), _ptr(mu), _ptr(sigma), _ptr(acq),
-                                            _ptr(cov), out.res_ptr, out.info_ptr)
-    _lib.check(st, "gpbo_select_next_host_kern_f64")
+    _lib.call(lib.gpbo_select_next_host_kern_f64, X, y, N, d, ls, kid, float(jitter1), float(jitter2), Xs, M, kind, p0, p1,
+              float(diag_add), int(chunk), mu, sigma, acq, cov, out.res, out.info_ptr)
     return dict(out.decode(), mu=mu, sigma=sigma, acq=acq, cov_meas=cov)
 
 
@@ -145,10 +135,8 @@ def select_qei(X, y, ls, Xs, Z, f_best: float, xi: float = 0.0, chunk: int = 0, 
     qei = np.empty(M // 8)
     out = _Result()
     _lib.note_hip_use()
-    st = lib.gpbo_select_qei_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M,
-                                      float(f_best), float(xi), _ptr(Z), len(Z), int(chunk), _ptr(qei), out.res_ptr,
-                                      out.info_ptr)
-    _lib.check(st, "gpbo_select_qei_host_f64")
+    _lib.call(lib.gpbo_select_qei_host_f64, X, y, N, d, ls, JITTER_KERNEL, JITTER_ASSEMBLY, Xs, M, float(f_best), float(xi), Z,
+              len(Z), int(chunk), qei, out.res, out.info_ptr)
     return dict(out.decode(), qei=qei)
 
 
@@ -167,10 +155,8 @@ def select_batch(X, y, ls, Xs, q: int, acquisition: str = "lcb", explore: float 
     mu, sigma = (np.empty(M) if dense else None for _ in range(2))
     out = _Result()
     _lib.note_hip_use()
-    st = lib.gpbo_select_batch_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M, kind,
-                                        p0, p1, int(chunk), q, fkind, fl, _ptr(idx), _ptr(val), _ptr(mu), _ptr(sigma),
-                                        out.res_ptr, out.info_ptr)
-    _lib.check(st, "gpbo_select_batch_host_f64")
+    _lib.call(lib.gpbo_select_batch_host_f64, X, y, N, d, ls, JITTER_KERNEL, JITTER_ASSEMBLY, Xs, M, kind, p0, p1, int(chunk),
+              q, fkind, fl, idx, val, mu, sigma, out.res, out.info_ptr)
     r = out.decode()
     return dict(indices=idx, values=val, nan_count=r["nan_count"], info=r["info"], mu=mu, sigma=sigma)
 
@@ -191,10 +177,8 @@ def select_thompson(X, y, ls, Xs, q: int, n_paths=None, n_features: int = 2048, 
     f = np.empty((S, M)) if dense else None
     out = _Result()
     _lib.note_hip_use()
-    st = lib.gpbo_thompson_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(Xs), M, _ptr(omega),
-                                    _ptr(phase), _ptr(W), _ptr(E), F, S, _ptr(idx), _ptr(val), _ptr(nan), _ptr(f),
-                                    out.info_ptr)
-    _lib.check(st, "gpbo_thompson_host_f64")
+    _lib.call(lib.gpbo_thompson_host_f64, X, y, N, d, ls, JITTER_KERNEL, JITTER_ASSEMBLY, Xs, M, omega, phase, W, E, F, S, idx,
+              val, nan, f, out.info_ptr)
     keep = first_distinct(idx, q)
     return dict(indices=idx[keep], values=val[keep], all_indices=idx, all_values=val, nan_counts=nan, info=out.decode()["info"],
                 f=f)
@@ -222,10 +206,8 @@ def select_nei(X, y, ls, Xs, n_fantasies: int = 16, seed: int = 0, xi: float = 0
     fbest = np.empty(S)
     out = _Result()
     _lib.note_hip_use()
-    st = lib.gpbo_nei_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), kid, float(jitter1), float(jitter2), delta, _ptr(Xs), M, _ptr(Z),
-                               _ptr(E), S, xi, int(chunk), _ptr(b), _ptr(mu), _ptr(sigma), _ptr(acq), _ptr(fbest), out.res_ptr,
-                               out.info_ptr)
-    _lib.check(st, "gpbo_nei_host_f64")
+    _lib.call(lib.gpbo_nei_host_f64, X, y, N, d, ls, kid, float(jitter1), float(jitter2), delta, Xs, M, Z, E, S, xi, int(chunk),
+              b, mu, sigma, acq, fbest, out.res, out.info_ptr)
     return dict(out.decode(), acq=acq, sigma=sigma, mu=mu, fantasy_best=fbest)
 
 
@@ -243,10 +225,8 @@ def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: fl
     acq, acq0, pg, accepted = np.empty(P), np.empty(P), np.empty(P), np.empty(P, dtype=np.int32)
     out = _Result()
     _lib.note_hip_use()
-    st = lib.gpbo_refine_host_f64(_ptr(X), _ptr(y), N, d, _ptr(ls), JITTER_KERNEL, JITTER_ASSEMBLY, _ptr(x), P, _ptr(lo), _ptr(hi),
-                                  kind, p0, p1, iters, step0, _ptr(acq), _ptr(acq0), _ptr(accepted), _ptr(pg),
-                                  out.res_ptr, out.info_ptr)
-    _lib.check(st, "gpbo_refine_host_f64")
+    _lib.call(lib.gpbo_refine_host_f64, X, y, N, d, ls, JITTER_KERNEL, JITTER_ASSEMBLY, x, P, lo, hi, kind, p0, p1, iters, step0,
+              acq, acq0, accepted, pg, out.res, out.info_ptr)
     r = out.decode()
     return dict(x=x, acq=acq, acq0=acq0, accepted=accepted, pg=pg, best=r["best_idx"], best_val=r["best_val"],
                 nan_count=r["nan_count"], info=r["info"])

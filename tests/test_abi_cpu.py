@@ -60,10 +60,142 @@ def test_every_compute_entry_point_rejects_null_arguments():
     for name, (res, args) in _lib.SIGNATURES.items():
         if res is not C.c_int or name in skip:
             continue
-        a = [None if t is C.c_void_p else (0.0 if t is C.c_double else 0) for t in args]
+        a = [None if t is _lib.Pointer else (0.0 if t is C.c_double else 0) for t in args]
         assert getattr(lib, name)(*a) == -1, name
         checked += 1
-    assert checked >= 15
+    assert checked >= 61   # (the 70 functions that return a status, less the nine of them in `skip`)
+
+
+def _header_prototypes():
+    """name -> (return kind, [argument kinds]) of every prototype of include/gpbo.h; kinds: "ptr" (any `T *`), "str"
+    (`const char *` as a return), "i64", "i32" (int32_t or int), "f64", "void"."""
+    src = open(os.path.join(REPO, "include", "gpbo.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    src = re.sub(r"typedef\s+struct\s+\w*\s*\{.*?\}\s*\w+\s*;", "", src, flags=re.S)
+    src = src.replace('extern "C" {', "")
+    scalar = {"int64_t": "i64", "int32_t": "i32", "int": "i32", "double": "f64", "void": "void"}
+
+    def kind(decl, is_return=False):
+        words = decl.replace("*", " * ").split()
+        if "*" in words:
+            return "str" if is_return and words[:3] == ["const", "char", "*"] else "ptr"
+        words = [w for w in words if w != "const"]
+        return scalar[words[0]]   # (an argument: the type, then its name)
+
+    protos = {}
+    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(gpbo_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        args = [a.strip() for a in args.split(",")]
+        assert name not in protos, name
+        protos[name] = (kind(ret, True), [] if args == ["void"] else [kind(a) for a in args])
+    return protos
+
+
+def _table_kind(t):
+    if t is None:
+        return "void"
+    if t is ctypes.c_char_p:
+        return "str"
+    if issubclass(t, (ctypes.c_void_p, ctypes._Pointer)):
+        return "ptr"
+    return {ctypes.c_int64: "i64", ctypes.c_int32: "i32", ctypes.c_int: "i32", ctypes.c_double: "f64"}[t]
+
+
+def _table_mismatches(table, protos):
+    """Every way `table` (name -> (restype, argtypes)) departs from the header's prototypes, as strings."""
+    bad = [f"{n}: only in the {'table' if n in table else 'header'}" for n in sorted(set(table) ^ set(protos))]
+    for name in sorted(set(table) & set(protos)):
+        res, args = table[name]
+        ret, kinds = protos[name]
+        if _table_kind(res) != ret:
+            bad.append(f"{name}: returns {ret}, bound as {_table_kind(res)}")
+        if len(args) != len(kinds):
+            bad.append(f"{name}: {len(kinds)} arguments, {len(args)} bound")
+        bad += [f"{name}: argument {i} is {k}, bound as {_table_kind(t)}"
+                for i, (t, k) in enumerate(zip(args, kinds)) if _table_kind(t) != k]
+    return bad
+
+
+def test_every_prototype_matches_its_ctypes_signature():
+    """Return type and every argument, in order and by width, of include/gpbo.h against _lib.SIGNATURES: an int32 bound
+    where the header says int64_t would shift every later argument of the call without an error."""
+    protos = _header_prototypes()
+    assert sorted(protos) == _header_functions() and len(protos) >= 97   # every function of the header parsed
+    assert _table_mismatches(_lib.SIGNATURES, protos) == []
+
+
+def _seeded(edit):
+    res, args = _lib.SIGNATURES["gpbo_posterior_acq_kern_f64"]   # (Xs, M, X, N, Np: int64, d: int32, ls_host, ...)
+    args = list(args)
+    edit(args)
+    return dict(_lib.SIGNATURES, gpbo_posterior_acq_kern_f64=(res, args))
+
+
+def _swap(i, j):
+    def edit(args):
+        args[i], args[j] = args[j], args[i]
+    return edit
+
+
+@pytest.mark.parametrize("edit,what", [(lambda args: args.pop(9), "24 bound"), (_swap(4, 5), "argument 4 is i64, bound as i32"),
+                                       (_swap(0, 1), "argument 0 is ptr, bound as i64")],
+                         ids=["dropped argument", "int32 for int64", "scalar for pointer"])
+def test_the_signature_check_sees_a_seeded_mistake(edit, what):
+    bad = _table_mismatches(_seeded(edit), _header_prototypes())
+    assert bad and all(b.startswith("gpbo_posterior_acq_kern_f64: ") for b in bad) and any(what in b for b in bad), bad
+
+
+def _address_seen_by_the_callee(obj):
+    """What a C function receives for `obj` through an argument of type _lib.Pointer: memmove(dst, src, 0) returns dst."""
+    memmove = ctypes.CDLL(None).memmove
+    memmove.restype, memmove.argtypes = ctypes.c_void_p, [_lib.Pointer, _lib.Pointer, ctypes.c_size_t]
+    return memmove(obj, ctypes.create_string_buffer(1), 0)
+
+
+def test_pointer_arguments_take_arrays_and_tensors_as_they_are():
+    import torch
+
+    arr = (ctypes.c_int64 * 4)()
+    a = np.zeros((4, 6))
+    t = torch.zeros((4, 6), dtype=torch.float64)
+    word = ctypes.c_int32(0)
+    assert _lib.Pointer.from_param(None) is None   # (ctypes passes None as NULL)
+    assert _address_seen_by_the_callee(ctypes.c_void_p(4096)) == 4096
+    assert _address_seen_by_the_callee(4096) == 4096
+    assert _address_seen_by_the_callee(arr) == ctypes.addressof(arr)
+    assert _address_seen_by_the_callee(ctypes.byref(word)) == ctypes.addressof(word)
+    assert _address_seen_by_the_callee(a) == a.ctypes.data and _address_seen_by_the_callee(a[1:, :]) == a.ctypes.data + 48
+    assert _address_seen_by_the_callee(t) == t.data_ptr() and _address_seen_by_the_callee(t[2]) == t.data_ptr() + 96
+    # a view that is not contiguous never reaches the library
+    lib = _lib.load()
+    for view in (a[:, ::2], a.T, t.t(), t[:, 1:]):
+        with pytest.raises(ctypes.ArgumentError, match="contiguous"):
+            lib.gpbo_kxx_f64(view, 4, 2, None, 1e-4, 1e-6, None, 128, None)
+    with pytest.raises(ctypes.ArgumentError):
+        lib.gpbo_kxx_f64(None, 4, 2, 1.5, 1e-4, 1e-6, None, 128, None)   # (a float is no pointer)
+
+
+def test_checked_call_raises_with_the_function_name_and_the_status_text():
+    lib = _lib.load()
+    null = [None if t is _lib.Pointer else (0.0 if t is ctypes.c_double else 0)
+            for t in _lib.SIGNATURES["gpbo_posterior_acq_kern_f64"][1]]
+    with pytest.raises(_lib.GpboError) as by_check:
+        _lib.check(lib.gpbo_posterior_acq_kern_f64(*null), "gpbo_posterior_acq_kern_f64")
+    with pytest.raises(_lib.GpboError) as by_call:
+        _lib.call(lib.gpbo_posterior_acq_kern_f64, *null)
+    assert str(by_call.value) == str(by_check.value)
+    assert str(by_call.value) == f"gpbo_posterior_acq_kern_f64: {lib.gpbo_strerror(-1).decode()} (status -1)"
+    # another function and another status: a workspace of 8 bytes (refused before the pointers are touched)
+    buf = (ctypes.c_char * 1024)()
+    p = ctypes.c_void_p((ctypes.addressof(buf) + 255) & ~255)
+    ls = (ctypes.c_double * 2)(0.5, 0.5)
+    with pytest.raises(_lib.GpboError) as short:
+        _lib.call(lib.gpbo_factorise_f64, p, p, 100, 2, ls, 1e-4, 1e-6, 128, p, p, p, p, p, 8, None)
+    assert str(short.value) == f"gpbo_factorise_f64: {lib.gpbo_strerror(-3).decode()} (status -3)"
+    # GPBO_OK returns (an empty product: nothing is launched)
+    empty = [None if t is _lib.Pointer else (0.0 if t is ctypes.c_double else 0) for t in _lib.SIGNATURES["gpbo_gemm_f64"][1]]
+    assert _lib.call(lib.gpbo_gemm_f64, *empty) is None
 
 
 def test_size_contracts_are_checked_on_the_host():

@@ -4,7 +4,9 @@ byte pattern; callers hand the library the QUERIED size, so nothing else changes
 workspace are intact, and the results equal a plain DeviceGP's on the same inputs bit for bit.
 
 Shapes: N = 130 (Np = 256: two column blocks), d = 3; M = 1025 with chunk = 512 - three chunks, both chunk buffers, a ragged
-last chunk; the fp32 screen, whose chunks are multiples of 1024, at chunk = 1024 and M = 2049."""
+last chunk; the fp32 screen, whose chunks are multiples of 1024, at chunk = 1024 and M = 2049.  GuardedEnsemble is the same
+for DeviceEnsemble's two workspaces: S = 3 models at N = 67 (not a multiple of 64; Np = 128), M = 1030 with chunk = 512 - two
+chunks and a ragged tail."""
 import dataclasses
 
 import numpy as np
@@ -13,7 +15,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from bayesian_optimisation_amd import DeviceGP  # noqa: E402
+from bayesian_optimisation_amd import DeviceEnsemble, DeviceGP  # noqa: E402
+from bayesian_optimisation_amd.model import SurrogateModel  # noqa: E402
 from bayesian_optimisation_amd.synthetic import make_problem  # noqa: E402
 
 DEV = "cuda:0"
@@ -22,7 +25,7 @@ N, D, M = 130, 3, 1025
 X, Y, XS, LS = make_problem(N, 2049, D)
 
 
-class GuardedGP(DeviceGP):
+class _Guards:
     """Every workspace is `nbytes` as queried plus GUARD bytes of PATTERN, kept in self.guards[slot] = (nbytes, raw buffer)."""
 
     def __init__(self, *a, **k):
@@ -43,6 +46,18 @@ class GuardedGP(DeviceGP):
             setattr(self, slot_name, raw[: (nbytes + 7) // 8 * 8].view(torch.float64))
         return getattr(self, slot_name)
 
+    def check_guards(self, *expected):
+        torch.cuda.synchronize()
+        assert set(expected) <= set(self.guards), (expected, sorted(self.guards))
+        for name, (nbytes, raw) in self.guards.items():
+            assert raw.numel() >= nbytes + GUARD and bool((raw[nbytes:] == PATTERN).all()), f"{name}: written past {nbytes} bytes"
+
+
+class GuardedEnsemble(_Guards, DeviceEnsemble):
+    pass
+
+
+class GuardedGP(_Guards, DeviceGP):
     def prepare_i8(self):   # (the int8 factor image is a buffer of its own: gpbo_prepare_i8_bytes)
         need = int(self.lib.gpbo_prepare_i8_bytes(self.Np))
         if "U8" not in self.guards or self.guards["U8"][0] != need:
@@ -57,12 +72,6 @@ class GuardedGP(DeviceGP):
                 fb[key] = self._guarded("fit_" + key, nbytes)
             fb.update(wh=wh, out_hyper=torch.empty(4 + fb["d"], dtype=torch.float64, device=self.device), guarded=True)
         return fb
-
-    def check_guards(self, *expected):
-        torch.cuda.synchronize()
-        assert set(expected) <= set(self.guards), (expected, sorted(self.guards))
-        for name, (nbytes, raw) in self.guards.items():
-            assert raw.numel() >= nbytes + GUARD and bool((raw[nbytes:] == PATTERN).all()), f"{name}: written past {nbytes} bytes"
 
 
 _PAIRS = {}
@@ -181,3 +190,16 @@ def test_nlml_hyper_stays_inside_its_workspaces():
     g, p = _pair()
     _same(g.nlml_hyper(X, Y, LS, 1e-3), p.nlml_hyper(X, Y, LS, 1e-3))
     g.check_guards("fit_work_fact", "fit_work_grad", "fit_work_hyper")
+
+
+def test_ensemble_stays_inside_its_workspaces():
+    n, m = 67, 1030
+    models = [(LS * f, SurrogateModel("se", j1, 0.0, mean, scale, True), w)
+              for f, j1, mean, scale, w in ((0.8, 1e-3, 0.1, 1.5, 0.5), (1.0, 1e-4, 0.0, 1.0, 0.3), (1.3, 1e-2, -0.2, 0.7, 0.2))]
+    g, p = (cls(device=DEV, chunk=512).factorise(X[:n], Y[:n], models) for cls in (GuardedEnsemble, DeviceEnsemble))
+    g.check_guards("_work_fact")
+    _same(g.U, p.U, "U")
+    _same(g.alpha, p.alpha, "alpha")
+    for kw in (dict(acquisition="lcb"), dict(acquisition="ei", f_best=float(Y[:n].min()), xi=0.01)):
+        _same(g.score(XS[:m], dense=True, **kw), p.score(XS[:m], dense=True, **kw))
+        g.check_guards("_work_fact", "_work")
