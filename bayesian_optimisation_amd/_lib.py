@@ -34,6 +34,9 @@ HYPER_SCALE = 2     # ... and the signal variance
 HYPER_CELLS_MAX_N = 64   # gpbo_nlml_hyper_cells_f64: a cell's rows are the lanes of one wave
 ENSEMBLE_MAX_S = 64      # gpbo_ensemble_acq_f64: models per call
 NEI_MAX_S = 64           # gpbo_posterior_nei_kern_f64: fantasies per call
+MES_MAX_LEVELS = 64      # gpbo_mes_log_survival_f64: levels per call
+MES_MAX_S = 64           # gpbo_mes_acq_f64: sampled minima per call
+MES_WORK_BYTES = 1 << 20   # the workspace of both: a constant
 # covariance families of the gpbo_*_kern_f64 entry points (include/gpbo.h: GPBO_KERNEL_*)
 KERNEL_IDS = {"se": 0, "matern32": 1, "matern52": 2}
 
@@ -203,6 +206,10 @@ SIGNATURES = {
                                               _p, _i64, _p, _p, _p, _p, _i64, _p]),
     "gpbo_nei_host_f64": (C.c_int, [_p, _p, _i64, _i32, _p, _i32, _f64, _f64, _f64, _p, _i64, _p, _p, _i32, _f64, _i64, _p, _p,
                                     _p, _p, _p, _p, _p]),
+    "gpbo_mes_log_survival_f64": (C.c_int, [_p, _p, _i64, _p, _i32, _p, _p, _p, _i64, _p]),
+    "gpbo_mes_acq_f64": (C.c_int, [_p, _p, _i64, _p, _i32, _i64, _p, _p, _p, _i64, _p]),
+    "gpbo_mes_log_survival_host_f64": (C.c_int, [_p, _p, _i64, _p, _i32, _p, _p]),
+    "gpbo_mes_acq_host_f64": (C.c_int, [_p, _p, _i64, _p, _i32, _p, _p]),
     "gpbo_gemm_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
                                 _i32, _i32, _p]),
     "gpbo_gemm_tri_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,

@@ -10,6 +10,7 @@
 //   gpbo_select_batch_host_f64     = the same step, then q points for parallel evaluation (not in the reference; batch.hip)
 //   gpbo_thompson_host_f64         = the factorisation, then q points as minimisers of posterior sample paths (thompson.hip)
 //   gpbo_nei_host_f64              = the factorisation and its noise-free twin, then noisy expected improvement (nei.hip)
+//   gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64 = max-value entropy search on a dense posterior the caller holds (mes.hip)
 //   gpbo_refine_host_f64           = the factorisation, then gradient refinement of given starts off the grid (refine.hip)
 //   gpbo_nlml_grid_host_f64        = tune_kernel()'s likelihood grid (float32, the reference's det underflow)
 //   gpbo_nlml_grid_logdet_host_f64 = the same grid in fp64 with log det from the factor
@@ -408,6 +409,41 @@ extern "C" int gpbo_nei_host_f64(const double *X, const double *y, int64_t N, in
     if (sigma_out) okc = okc && A.d2h(sigma_out, dsig, sizeof(double) * M);
     if (acq_out) okc = okc && A.d2h(acq_out, dacq, sizeof(double) * M);
     if (best_out) okc = okc && A.d2h(best_out, dbest, sizeof(double) * S);
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+}
+
+// Max-value entropy search on host arrays (csrc/mes.hip): no factorisation - the two calls work on a dense posterior (mu, sigma)
+// the caller already holds.  The refusals are the device entries' own (mes_values_ok, host_driver.h), made before the arena exists.
+extern "C" int gpbo_mes_log_survival_host_f64(const double *mu, const double *sigma, int64_t M, const double *z, int32_t Q,
+                                              double *out, int64_t *nan_out) {
+    if (!mu || !sigma || !z || !out || !nan_out || !mes_values_ok(M, z, Q, GPBO_MES_MAX_LEVELS)) return GPBO_ERR_ARG;
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    double *dmu = A.alloc<double>(M), *dsig = A.alloc<double>(M), *dout = A.alloc<double>(Q);
+    int64_t *dnan = A.alloc<int64_t>(1);
+    char *dwork = A.alloc<char>(GPBO_MES_WORK_BYTES);   // (hipMalloc: 256-byte aligned)
+    if (!A.ok) return GPBO_ERR_WORKSPACE;
+    if (!A.h2d(dmu, mu, sizeof(double) * M) || !A.h2d(dsig, sigma, sizeof(double) * M)) return GPBO_ERR_LAUNCH;
+    const int rc = gpbo_mes_log_survival_f64(dmu, dsig, M, z, Q, dout, dnan, dwork, GPBO_MES_WORK_BYTES, A.st());
+    if (rc != GPBO_OK) return rc;
+    return A.d2h(out, dout, sizeof(double) * Q) && A.d2h(nan_out, dnan, sizeof(int64_t)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+}
+
+extern "C" int gpbo_mes_acq_host_f64(const double *mu, const double *sigma, int64_t M, const double *ystar, int32_t S,
+                                     double *acq_out, gpbo_result *result) {
+    if (!mu || !sigma || !ystar || !result || !mes_values_ok(M, ystar, S, GPBO_MES_MAX_S)) return GPBO_ERR_ARG;
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    double *dmu = A.alloc<double>(M), *dsig = A.alloc<double>(M);
+    double *dacq = acq_out ? A.alloc<double>(M) : nullptr;
+    gpbo_result *dres = A.alloc<gpbo_result>(1);
+    char *dwork = A.alloc<char>(GPBO_MES_WORK_BYTES);   // (hipMalloc: 256-byte aligned)
+    if (!A.ok) return GPBO_ERR_WORKSPACE;
+    if (!A.h2d(dmu, mu, sizeof(double) * M) || !A.h2d(dsig, sigma, sizeof(double) * M)) return GPBO_ERR_LAUNCH;
+    const int rc = gpbo_mes_acq_f64(dmu, dsig, M, ystar, S, 0, dacq, dres, dwork, GPBO_MES_WORK_BYTES, A.st());
+    if (rc != GPBO_OK) return rc;
+    bool okc = A.d2h(result, dres, sizeof(gpbo_result));
+    if (acq_out) okc = okc && A.d2h(acq_out, dacq, sizeof(double) * M);
     return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 

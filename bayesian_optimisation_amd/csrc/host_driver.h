@@ -60,6 +60,15 @@ inline bool length_scales_ok(const double *ls, int d) {
     return true;
 }
 
+// max-value entropy search (mes.hip and its host entries in host_api.hip): 1 <= M <= 2^40 candidates and 1 <= n <= n_max values
+// that travel by value (levels or sampled minima), each finite
+inline bool mes_values_ok(int64_t M, const double *v_host, int32_t n, int32_t n_max) {
+    if (M < 1 || M > ((int64_t)1 << 40) || n < 1 || n > n_max) return false;
+    for (int32_t i = 0; i < n; ++i)
+        if (!(v_host[i] - v_host[i] == 0.0)) return false;
+    return true;
+}
+
 // ---- the length scales as the kernels take them: il2[k] = 1 / ls_k^2 (cov_r2, cov_entry.h), isc[k] = 1 / (ls_k sqrt 2)
 // (the scoring form of cov_entry.h), k < d; either may be null.  EXACTLY these expressions: the values feed kernels whose
 // outputs are compared bit for bit.  The entries k >= d are the caller's.  false: a length scale that is not positive.

@@ -179,6 +179,45 @@ def gather_concat_tensors(locals_, total: int, group=None):
     return full
 
 
+def allreduce_min(values, group=None):
+    """Element-wise minimum over the ranks of a few fp64 values (exact: a minimum does not round), as a host array on every
+    rank.  One all_reduce(MIN).  Outside a process group: the values themselves."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    v = np.ascontiguousarray(np.asarray(values, dtype=np.float64).reshape(-1))
+    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return v
+    t = torch.from_numpy(v.copy()).to(_collective_device(group))
+    dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
+    return t.cpu().numpy()
+
+
+def sum_in_rank_order(partial, count: int = 0, group=None):
+    """(sum over the ranks of `partial` [Q] fp64, sum of `count`), the SAME bits on every rank: the partial sums are gathered
+    (as their bit patterns, one all_gather of Q + 1 int64 per rank) and added in rank order on every rank - an all_reduce(SUM)
+    may add in another order on another rank, and the ranks of a sharded max-value entropy search must fit the same Gumbel
+    law to the same log S.  Outside a process group and with one rank: the identity."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    p = np.ascontiguousarray(np.asarray(partial, dtype=np.float64).reshape(-1))
+    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return p, int(count)
+    world, Q = dist.get_world_size(group), p.size
+    dev = _collective_device(group)
+    mine = torch.from_numpy(np.concatenate([p.view(np.int64), np.array([int(count)], dtype=np.int64)])).to(dev)
+    out = torch.empty(world * (Q + 1), dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(out, mine, group=group)
+    rows = out.cpu().numpy().reshape(world, Q + 1)
+    total = rows[0, :Q].copy().view(np.float64).copy()
+    for r in range(1, world):
+        total = total + rows[r, :Q].copy().view(np.float64)
+    return total, int(rows[:, Q].sum())
+
+
 def all_agree(flag: bool, group=None) -> bool:
     """True iff `flag` is true on EVERY rank (a collective decision: e.g. append-or-refactorise must be taken the same
     way everywhere, or the ranks' factors differ at rounding level and the lowest-index tie rule no longer holds).

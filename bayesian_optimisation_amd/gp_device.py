@@ -160,6 +160,19 @@ class NeiResult:
     mu: Optional[object] = None      # ... and the S means [S x M]
 
 
+@dataclass
+class MesResult:
+    """What DeviceGP.mes_on_posterior / select_mes return."""
+    best_val: float
+    best_idx: int
+    nan_count: int
+    acq: Optional[object] = None        # dense=True: torch fp64 device tensor, MES [M]
+    y_star: Optional[np.ndarray] = None   # float64 [S]: the sampled minima the terms were measured against (units of the model)
+    quartiles: Optional[np.ndarray] = None   # y_star="gumbel": (z75, z50, z25), the levels where Pr[m* > z] = 0.75, 0.5, 0.25
+    mu: Optional[object] = None         # select_mes: the posterior the pass returned, fp64 [M] device tensors
+    sigma: Optional[object] = None
+
+
 def refine_params(P: int, d: int, iters: int, step0: float) -> tuple:
     """(iters, step0) as the C ABI takes them; refuses what gpbo_refine_f64 refuses (include/gpbo.h)."""
     if not 1 <= int(P) <= _lib.REFINE_MAX_P:
@@ -338,7 +351,7 @@ class DeviceGP(DeviceSide, LikelihoodFits):
         # workspaces, kept from call to call and only ever grown (_workspace)
         self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
         self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = self._work_loo = None
-        self._work_nei = None
+        self._work_nei = self._work_mes = None
         self._epoch = 0              # counts factorise() / append() / load_state_dict(): ThompsonPaths belong to one of them
         self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
         self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
@@ -1138,6 +1151,108 @@ class DeviceGP(DeviceSide, LikelihoodFits):
         Xsd, _ = self._candidates(Xs)
         return self.score_nei(self.fantasies(n_fantasies, seed, delta), Xsd, xi=xi, dense=dense, idx_offset=idx_offset,
                               check=check)
+
+    # -- max-value entropy search on the dense posterior (csrc/mes.hip) --------------------------------
+    def _posterior_pair(self, mu, sigma) -> tuple:
+        """(mu, sigma as contiguous fp64 device tensors, M); refuses anything but two flat arrays of one length."""
+        mud, sgd = self._dev(mu).reshape(-1), self._dev(sigma).reshape(-1)
+        M = int(mud.numel())
+        if M < 1 or int(sgd.numel()) != M:
+            raise ValueError("mu and sigma must hold one value per candidate (at least one)")
+        return mud, sgd, M
+
+    def log_survival(self, mu, sigma, z) -> tuple:
+        """(log S(z_q) = sum_c log Phi((mu_c - z_q) / sigma_c) as a float64 host array [Q], the number of candidates skipped
+        because their mu or sigma is NaN) over dense mu / sigma [M] (gpbo_mes_log_survival_f64: one pass whatever Q <= 64; the
+        edge rules are stated in include/gpbo.h).  Works without a factorisation.  One read-back (synchronises)."""
+        torch = self.torch
+        zh = np.ascontiguousarray(np.asarray(z, dtype=np.float64).reshape(-1))
+        Q = int(zh.size)
+        if not 1 <= Q <= _lib.MES_MAX_LEVELS or not np.all(np.isfinite(zh)):
+            raise ValueError(f"z must hold 1 to {_lib.MES_MAX_LEVELS} finite levels")
+        mud, sgd, M = self._posterior_pair(mu, sigma)
+        with torch.cuda.device(self.device):
+            work = self._workspace("_work_mes", _lib.MES_WORK_BYTES)
+            out = torch.empty(Q + 1, dtype=torch.float64, device=self.device)   # log S [Q] | the NaN count (int64)
+            _lib.call(self.lib.gpbo_mes_log_survival_f64, mud, sgd, M, zh, Q, out, out[Q:], work, _lib.MES_WORK_BYTES,
+                      self._stream())
+            h = out.cpu()   # synchronises: the levels have travelled by value, mud / sgd have been consumed
+        return h[:Q].numpy().copy(), int(h[Q:].view(torch.int64)[0])
+
+    def mes_on_posterior(self, mu, sigma, y_star, idx_offset: int = 0, dense: bool = True) -> MesResult:
+        """MES(x) = mean_s h((mu(x) - y_star_s) / sigma(x)) over dense mu / sigma [M] and its first arg-max (gpbo_mes_acq_f64).
+        y_star: 1 to 64 finite sampled minima, in the units of mu.  One read-back (synchronises)."""
+        from .mes import mes_y_star
+
+        torch = self.torch
+        ys = np.ascontiguousarray(np.asarray(y_star, dtype=np.float64).reshape(-1))
+        if not 1 <= ys.size <= _lib.MES_MAX_S:
+            raise ValueError(f"y_star must hold 1 to {_lib.MES_MAX_S} values, got {ys.size}")
+        ys = mes_y_star(ys, int(ys.size))
+        mud, sgd, M = self._posterior_pair(mu, sigma)
+        with torch.cuda.device(self.device):
+            work = self._workspace("_work_mes", _lib.MES_WORK_BYTES)
+            acq = torch.empty(M, dtype=torch.float64, device=self.device) if dense else None
+            _lib.call(self.lib.gpbo_mes_acq_f64, mud, sgd, M, ys, int(ys.size), int(idx_offset), acq, self._result, work,
+                      _lib.MES_WORK_BYTES, self._stream())
+            v, i, n = self.read_result(self._result)   # synchronises
+        return MesResult(v, i, n, acq, ys)
+
+    def mes_minima(self, mu, sigma, Xs, S: int, seed: int, y_star, cap, log_survival=None, reduce_min=None) -> tuple:
+        """(the S sampled minima m*_s [S] in the units of mu, the quartiles or None) for a MES call on the posterior (mu, sigma)
+        of the candidates Xs.  y_star: "gumbel" (mes.gumbel_quartiles on log_survival(), mes.sample_minima with
+        mes.mes_uniforms(S, seed)), "thompson" (m*_s = -val_out[s] of thompson_score with S paths and this seed: kernel='se'),
+        or S values used verbatim.  cap: a number or None.  log_survival / reduce_min: what a sharded caller puts between the
+        local pass and the fit (the rank-order sum of the partial log S, the MIN all-reduce of the brackets)."""
+        from . import mes as MES
+
+        y_star = MES.mes_y_star(y_star, S)
+        if not isinstance(y_star, str):
+            return y_star, None
+        if y_star == "thompson":
+            r = self.thompson_score(self.thompson_paths(S, seed=seed), Xs)
+            return -np.asarray(r.values, dtype=np.float64), None   # (minima of actual paths: the cap is the Gumbel route's)
+        torch = self.torch
+        with torch.cuda.device(self.device):
+            # the brackets: plumbing on the dense arrays (NaN candidates are skipped, as log S skips them)
+            ok = ~(torch.isnan(mu) | torch.isnan(sigma))
+            inf = torch.full_like(mu, float("inf"))
+            lo_hi = torch.stack([torch.where(ok, mu - MES.LO_SIGMAS * sigma, inf).min(),
+                                 torch.where(ok, mu + MES.HI_SIGMAS * sigma, inf).min()]).cpu().numpy()
+        if reduce_min is not None:
+            lo_hi = reduce_min(lo_hi)
+        if not np.all(np.isfinite(lo_hi)):
+            raise IndexError(NAN_ACQUISITION)   # no candidate with a usable posterior
+        ls = log_survival if log_survival is not None else (lambda z: self.log_survival(mu, sigma, z))
+        quartiles, _ = MES.gumbel_quartiles(ls, lo_hi[0], lo_hi[1])
+        return MES.sample_minima(quartiles, MES.mes_uniforms(S, seed), cap), quartiles
+
+    def select_mes(self, Xs, n_samples: int = 16, seed: int = 0, y_star="gumbel", cap="observed", dense: bool = False,
+                   idx_offset: int = 0, prior_var: Optional[float] = None) -> MesResult:
+        """The next point by max-value entropy search (Wang & Jegelka 2017): the unchanged fp64 pass for (mu, sigma)
+        at the rows of Xs, n_samples samples of the minimum's VALUE, then MES and its first arg-max.  No trade-off parameter
+        and no incumbent; every kernel family.  y_star: "gumbel" (the Gumbel fit to three quartiles of Pr[m* > z] under an
+        independence approximation: four passes of gpbo_mes_log_survival_f64), "thompson" (the minima of n_samples posterior
+        sample paths: kernel='se'), or n_samples values.  cap: "observed" (m*_s <= min(y): the paper's rule), a number or
+        None.  prior_var: the pass's (default: that of this factorisation's jitters).  ValueError on bad parameters before any
+        GPU work."""
+        from .mes import mes_params, mes_y_star
+
+        S, seed, cap = mes_params(n_samples, seed, cap)
+        y_star = mes_y_star(y_star, S)
+        if isinstance(y_star, str) and y_star == "thompson":
+            need_se(self.kernel, "select_mes(y_star='thompson')")
+        if self.N < 1:
+            raise _lib.GpboError("select_mes() needs a factorised surrogate")
+        Xsd, M = self._candidates(Xs)
+        pv = (1.0 + self.jitter1) + self.jitter2 if prior_var is None else float(prior_var)
+        s = self.score(Xsd, acquisition="lcb", explore=0.0, dense=True, prior_var=pv)
+        if isinstance(cap, str):
+            cap = float(self.y[: self.N].min().item())
+        m, quartiles = self.mes_minima(s.mu, s.sigma, Xsd, S, seed, y_star, cap)
+        r = self.mes_on_posterior(s.mu, s.sigma, m, idx_offset=idx_offset, dense=dense)
+        r.quartiles, r.mu, r.sigma = quartiles, s.mu, s.sigma
+        return r
 
     # -- acquisition gradients and off-grid refinement (csrc/refine.hip, DESIGN 4d) -------------------------------
     def _points(self, Xq, what: str):

@@ -211,6 +211,46 @@ def select_nei(X, y, ls, Xs, n_fantasies: int = 16, seed: int = 0, xi: float = 0
     return dict(out.decode(), acq=acq, sigma=sigma, mu=mu, fantasy_best=fbest)
 
 
+def _posterior_pair(mu, sigma):
+    mu, sigma = _f64(mu).reshape(-1), _f64(sigma).reshape(-1)
+    if mu.size < 1 or sigma.size != mu.size:
+        raise ValueError("mu and sigma must hold one value per candidate (at least one)")
+    return mu, sigma, int(mu.size)
+
+
+def mes_log_survival(mu, sigma, z, lib=None) -> tuple:
+    """(log S(z_q) = sum_c log Phi((mu_c - z_q) / sigma_c) [Q], the number of candidates skipped as NaN) on host arrays
+    (gpbo_mes_log_survival_host_f64; Q <= 64 levels in one pass)."""
+    mu, sigma, M = _posterior_pair(mu, sigma)
+    z = _f64(z).reshape(-1)
+    if not 1 <= z.size <= _lib.MES_MAX_LEVELS or not np.all(np.isfinite(z)):
+        raise ValueError(f"z must hold 1 to {_lib.MES_MAX_LEVELS} finite levels")
+    lib = lib or _lib.load()
+    out, nan = np.empty(z.size), np.zeros(1, dtype=np.int64)
+    _lib.note_hip_use()
+    _lib.call(lib.gpbo_mes_log_survival_host_f64, mu, sigma, M, z, int(z.size), out, nan)
+    return out, int(nan[0])
+
+
+def mes_acq(mu, sigma, y_star, dense: bool = True, lib=None) -> dict:
+    """Max-value entropy search on host arrays (gpbo_mes_acq_host_f64): MES(x) = mean_s h((mu - y_star_s) / sigma) over dense
+    mu / sigma [M] and its first arg-max.  Returns dict(best_val, best_idx, nan_count, acq [M])."""
+    from .mes import mes_y_star
+
+    mu, sigma, M = _posterior_pair(mu, sigma)
+    ys = _f64(y_star).reshape(-1)
+    if not 1 <= ys.size <= _lib.MES_MAX_S:
+        raise ValueError(f"y_star must hold 1 to {_lib.MES_MAX_S} values, got {ys.size}")
+    ys = mes_y_star(ys, int(ys.size))
+    lib = lib or _lib.load()
+    acq = np.empty(M) if dense else None
+    out = _Result()
+    _lib.note_hip_use()
+    _lib.call(lib.gpbo_mes_acq_host_f64, mu, sigma, M, ys, int(ys.size), acq, out.res)
+    r = out.decode()
+    return dict(best_val=r["best_val"], best_idx=r["best_idx"], nan_count=r["nan_count"], acq=acq)
+
+
 def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
            iters: int = 30, step0: float = 0.1, lib=None) -> dict:
     """Off-grid refinement on host arrays (gpbo_refine_host_f64: factorisation and refinement in one call).  Returns
@@ -362,6 +402,36 @@ class PointSelectorHost(PointSelector):
         r = self._factorised(select_nei(X, m.to_model(y), ls, Xs, S, seed, xi=xi, delta=delta, chunk=self._chunk, lib=self.lib,
                                         jitter1=m.jitter1, jitter2=m.jitter2, kernel=m.kernel))
         return r["acq"], (r["best_val"], r["best_idx"], r["nan_count"]), r["fantasy_best"]
+
+    def max_value_entropy_search(self, n_samples=16, seed=0, y_star="gumbel", cap="observed"):
+        """PointSelector.max_value_entropy_search on the host-pointer route: the same samples for the same seed, the same
+        index.  y_star: "gumbel" or n_samples values; "thompson" needs PointSelector (ValueError)."""
+        if isinstance(y_star, str) and y_star == "thompson":
+            raise ValueError("max_value_entropy_search(y_star='thompson') needs PointSelector (the sample paths are drawn on the "
+                             "factorisation, which does not outlive a host-pointer call): use y_star='gumbel' or an array")
+        return super().max_value_entropy_search(n_samples=n_samples, seed=seed, y_star=y_star, cap=cap)
+
+    def _mes_scores(self, S, seed, y_star, cap):
+        """PointSelector.max_value_entropy_search on the host-pointer route (gpbo_mes_log_survival_host_f64 /
+        gpbo_mes_acq_host_f64 on mean_func / cov_func, taken back to the units of the model): the same samples for the same
+        seed, the same values."""
+        from . import mes as MES
+
+        m = self._model
+        mu = _f64(m.to_model(np.asarray(self.mean_func, dtype=np.float64))).reshape(-1)
+        sigma = _f64(np.asarray(self.cov_func, dtype=np.float64) / m.y_scale if m.fitted else self.cov_func).reshape(-1)
+        if isinstance(y_star, str):
+            ok = ~(np.isnan(mu) | np.isnan(sigma))
+            if not np.any(ok):
+                raise IndexError(NAN_ACQUISITION)
+            lo = float(np.min(mu[ok] - MES.LO_SIGMAS * sigma[ok]))
+            hi = float(np.min(mu[ok] + MES.HI_SIGMAS * sigma[ok]))
+            quartiles, _ = MES.gumbel_quartiles(lambda z: mes_log_survival(mu, sigma, z, self.lib), lo, hi)
+            minima = MES.sample_minima(quartiles, MES.mes_uniforms(S, seed), cap)
+        else:
+            minima = y_star
+        r = mes_acq(mu, sigma, minima, lib=self.lib)
+        return r["acq"], (r["best_val"], r["best_idx"], r["nan_count"]), minima
 
     def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
         """PointSelector.refine_next on the host-pointer route (gpbo_refine_host_f64): the same d coordinates, the same

@@ -72,8 +72,8 @@ class SurrogateModel:
 
     def acq_to_y(self, kind: str, acq):
         """LCB = s acq - m (explore s sigma - (m + s mu)), EI / qEI = s acq.  Both maps increase, so the arg-max and its
-        tie rule are those of the kernels."""
-        if not self.fitted:
+        tie rule are those of the kernels.  "mes" (max-value entropy search) has no unit: an entropy of a ratio."""
+        if not self.fitted or kind == "mes":
             return acq
         return self.y_scale * acq - self.y_mean if kind == "lcb" else self.y_scale * acq
 

@@ -25,6 +25,8 @@ Differences from the reference, all deliberate:
     candidate: the route that is exact by construction is `dense_outputs=False` (the prefix bound).
     Also extra: `expected_improvement(xi)`, `noisy_expected_improvement()` (EI averaged over samples of the best latent value at
     the observed points instead of measured against min(measured_vals), the luckiest noise draw: INTEGRATION.md 9),
+    `max_value_entropy_search()` (the information gained about the minimum's value: no incumbent, no trade-off parameter;
+    INTEGRATION.md 10),
     `q_expected_improvement()`, `select_thompson(q)` (q points as the minimisers of posterior sample paths), `select_batch(q)` (q points for parallel evaluation: greedy Kriging believer / GP-BUCB /
     constant liar), `refine_next()` (the next point off the grid: the best candidates polished by acquisition gradients), `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
     calls go through the exact prefix bound), `kernel_params` may be preset (then no
@@ -188,6 +190,7 @@ class PointSelector:
         self.last_update = None        # "factorise" | "append": what the last update_surrogate() did
         self.last_screen = None        # screened precisions: DeviceGP.last_screen of the last acquisition + sigma_abs_tol
         self.fantasy_best = None       # noisy_expected_improvement(): the incumbent of every fantasy [S], in the units of y
+        self.sampled_minima = None     # max_value_entropy_search(): the sampled values of the minimum [S], in the units of y
 
     # ------------------------------------------------------------------------------------------
     def _cov_get(self, name):
@@ -745,3 +748,61 @@ class PointSelector:
             self._cached[key] = (model.acq_to_y("ei", acq).reshape(fd), model.best_to_y("ei", best), model.mean_to_y(fbest))
         self.fantasy_best = self._cached[key][2]
         return self._finish(key, "nei")
+
+    def _mes_scores(self, S, seed, y_star, cap):
+        """(MES over all candidates [M], (best value, flat index, NaN count), the sampled minima [S] in the units of the MODEL):
+        what each class provides to max_value_entropy_search().  Sharded candidates: the brackets' minima are an exact MIN
+        all-reduce and every round's partial log S is added in rank order, so every rank fits the same Gumbel law and draws the
+        same samples (distributed.sum_in_rank_order; with one rank the identity)."""
+        gp, mu, sigma, lo = self._gp, self._mu_dev, self._sigma_dev, self._lo_hi[0]
+        if isinstance(y_star, str) and y_star == "thompson" and self._world()[0] > 1:
+            raise NotImplementedError("max_value_entropy_search(y_star='thompson') with candidates sharded over several ranks is "
+                                      "not implemented")
+        m, _ = gp.mes_minima(mu, sigma, self._cand[0], S, seed, y_star, cap,
+                             log_survival=lambda z: D.sum_in_rank_order(*gp.log_survival(mu, sigma, z)),
+                             reduce_min=D.allreduce_min)
+        r = gp.mes_on_posterior(mu, sigma, m, idx_offset=lo, dense=True)
+        best = D.allreduce_argmax(r.best_val, r.best_idx, r.nan_count)
+        M = int(np.prod([int(v) for v in self.feature_domain]))
+        return D.gather_concat_tensors([r.acq], M)[0].cpu().numpy(), best, m
+
+    def max_value_entropy_search(self, n_samples=16, seed=0, y_star="gumbel", cap="observed"):
+        """Not in the reference: max-value entropy search (Wang & Jegelka 2017) for minimisation - the expected reduction of the
+        entropy of the minimum's VALUE m* over the candidates, MES(x) = mean_s h((mu(x) - m*_s) / sigma(x)) with
+        h(g) = g phi(g) / (2 Phi(g)) - log Phi(g).  No trade-off parameter and no incumbent, invariant under an affine map of
+        measured_vals, and a function of the posterior update_surrogate() has left on the device: no variance pass, every
+        kernel= and every model record.  y_star: how the n_samples minima are sampled - "gumbel" (a Gumbel law fitted to three
+        quartiles of Pr[m* > z] under an independence approximation), "thompson" (the minima of n_samples posterior
+        sample paths with this seed: kernel='se', one rank) or n_samples values in the units of measured_vals.  cap: "observed"
+        (no Gumbel sample above min(measured_vals): the paper's rule), a number in the units of measured_vals, or None.
+        Returns the multi-index as expected_improvement() does; acq_func_eval holds the values (unit-free) and sampled_minima
+        [n_samples] the samples in the units of measured_vals.  One seed gives the same samples on every rank of a sharded call
+        and in PointSelectorHost.  ard="marginal", a screened precision= and dense_outputs=False raise ValueError; IndexError
+        when the acquisition contains NaN."""
+        from .mes import mes_params, mes_y_star
+
+        self._not_in_marginal_mode("max_value_entropy_search()")
+        if self._precision != "fp64":
+            raise ValueError(f"max_value_entropy_search() needs precision='fp64', got precision={self._precision!r} (the stored "
+                             "sigma of a screened precision is the screen's)")
+        if not self._dense:
+            raise ValueError("max_value_entropy_search() needs dense_outputs=True (it works on the dense posterior)")
+        S, seed, cap = mes_params(n_samples, seed, cap)
+        y_star = mes_y_star(y_star, S)
+        if isinstance(y_star, str) and y_star == "thompson":
+            need_se(self._kernel, "max_value_entropy_search(y_star='thompson')")
+        self._need_update()
+        model = self._model
+        key = ("mes", S, seed, y_star if isinstance(y_star, str) else tuple(y_star.tolist()), cap)
+        if key not in self._cached:
+            # everything below in the units of the model (MES itself has no unit)
+            if isinstance(cap, str):
+                cap_m = float(np.min(model.to_model(np.asarray(self.measured_vals, dtype=np.float64))))
+            else:
+                cap_m = None if cap is None else float(model.to_model(cap))
+            ys = y_star if isinstance(y_star, str) else np.ascontiguousarray(model.to_model(y_star))
+            acq, best, minima = self._mes_scores(S, seed, ys, cap_m)
+            fd = [int(v) for v in self.feature_domain]
+            self._cached[key] = (model.acq_to_y("mes", acq).reshape(fd), best, model.mean_to_y(minima))
+        self.sampled_minima = self._cached[key][2]
+        return self._finish(key, "mes")

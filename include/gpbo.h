@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_kxx_kern_f64 / gpbo_kstar_mu_kern_f64 / gpbo_factorise_kern_f64 / gpbo_posterior_acq_kern_f64 / gpbo_nlml_grad_kern_f64 / gpbo_nlml_hyper_kern_f64 / gpbo_select_next_host_kern_f64 / gpbo_nlml_grad_host_kern_f64 / gpbo_nlml_hyper_host_kern_f64, the Matern 3/2 and 5/2 covariance families on the fp64 path; gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_mes_log_survival_f64 / gpbo_mes_acq_f64 / gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64, max-value entropy search on the dense posterior; gpbo_nei_fantasies_workspace_bytes / gpbo_nei_fantasies_f64 / gpbo_posterior_nei_workspace_bytes / gpbo_posterior_nei_kern_f64 / gpbo_nei_host_f64, noisy expected improvement; gpbo_kxx_kern_f64 / gpbo_kstar_mu_kern_f64 / gpbo_factorise_kern_f64 / gpbo_posterior_acq_kern_f64 / gpbo_nlml_grad_kern_f64 / gpbo_nlml_hyper_kern_f64 / gpbo_select_next_host_kern_f64 / gpbo_nlml_grad_host_kern_f64 / gpbo_nlml_hyper_host_kern_f64, the Matern 3/2 and 5/2 covariance families on the fp64 path; gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -717,6 +717,50 @@ int gpbo_nei_host_f64(const double *X_host, const double *y_host, int64_t N, int
                       const double *E_host, int32_t S, double xi, int64_t chunk, const double *best_in_host,
                       double *mu_out_host, double *sigma_out_host, double *acq_out_host, double *best_out_host,
                       gpbo_result *result_host, int32_t *info_host);
+
+/* ---- Max-value entropy search on the dense posterior (csrc/mes.hip; Wang & Jegelka 2017; not in the reference).
+ * For minimisation.  m* is the minimum of the latent function over the candidates; with S sampled minima m*_s and
+ * gamma_s(x) = (mu(x) - m*_s) / sigma(x),
+ *     MES(x) = (1 / S) sum_s h(gamma_s),   h(gamma) = gamma phi(gamma) / (2 Phi(gamma)) - log Phi(gamma) >= 0.
+ * No trade-off parameter and no incumbent; invariant under y -> a + b y (mu, sigma and the samples in ONE unit, any unit); a
+ * function of (mu, sigma) alone, so both calls read dense device arrays a scoring pass has left and build no covariance entry:
+ * every kernel family, every model record.  h and log Phi are evaluated in three branches (csrc/mes_math.h), t = -gamma / sqrt 2:
+ *     gamma > 0          log Phi = log1p(-erfc(gamma / sqrt 2) / 2),     h = gamma phi / (2 Phi) - log Phi
+ *     -1 <= gamma <= 0   log Phi = log(erfc(t) / 2),                     h = gamma phi / (2 Phi) - log Phi
+ *     gamma < -1         log Phi = -t^2 + log(erfcx(t) / 2),             h = (t^2 - t / (sqrt(pi) erfcx(t))) - log(erfcx(t) / 2)
+ *   (below -1 both terms of the plain h grow like gamma^2 / 2 and cancel, and Phi underflows at gamma ~ -38); against 60-digit
+ *   values the error stays within a few units of eps (max(1, gamma^2 / 2 for gamma < 0) + |h|).
+ *
+ * gpbo_mes_log_survival_f64: out[q] = log S(z_q) = sum_c log Phi((mu_c - z_q) / sigma_c), q < Q - the logarithm of Pr[m* > z_q]
+ *   when the candidates are taken as independent - at Q levels in ONE pass over the M candidates, and nan_out[0] = the number of
+ *   candidates skipped.  It serves the sampling of m*: the caller brackets the three levels where S = 0.75, 0.5, 0.25, fits a
+ *   Gumbel law to them and draws the m*_s from it (bayesian_optimisation_amd/mes.py; the draws are the caller's, as everywhere in
+ *   this ABI).  z_host [Q] travels by value.
+ * gpbo_mes_acq_f64: MES over the M candidates and its first arg-max; the S terms are added in index order and divided by S.
+ *   ystar_host [S]: the sampled minima, by value.  acq_out: optional dense [M].  result: as every other acquisition (best_idx =
+ *   idx_offset + the LOWEST candidate attaining the maximum).
+ * Edge rules: a candidate whose mu or sigma is NaN is skipped by log S and counted in nan_out; its acquisition is NaN, it counts
+ *   once in nan_count and is never chosen.  sigma == 0: the term of log S is 0 where mu > z and -inf otherwise; the acquisition
+ *   is 0.  (sigma is a standard deviation: >= 0.)
+ * Sums run in a fixed order (a thread's candidates ascending, a butterfly inside a wave, waves in wave order, workgroups in index
+ *   order) on a grid that depends on M alone: two calls give the same bits.  Only the integer NaN counter is atomic.
+ * 1 <= M <= 2^40, 1 <= Q <= GPBO_MES_MAX_LEVELS, 1 <= S <= GPBO_MES_MAX_S, every level and sample finite, no null pointer
+ *   but acq_out (GPBO_ERR_ARG otherwise);  work: GPBO_MES_WORK_BYTES bytes - a constant: 1024 x 64 partial sums and the arg-max
+ *   records - 256-byte aligned (GPBO_ERR_WORKSPACE otherwise);  all of it before any HIP call.  Both calls only enqueue.
+ * gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64: the same two on host arrays (conventions of the other *_host entries:
+ *   device buffers are allocated, filled, used and released inside the call, on a stream of its own; synchronous). */
+#define GPBO_MES_MAX_LEVELS 64
+#define GPBO_MES_MAX_S 64
+#define GPBO_MES_WORK_BYTES 1048576
+int gpbo_mes_log_survival_f64(const double *mu, const double *sigma, int64_t M, const double *z_host, int32_t Q,
+                              double *out /* device [Q] */, int64_t *nan_out /* device [1] */, void *work, int64_t work_bytes,
+                              void *stream);
+int gpbo_mes_acq_f64(const double *mu, const double *sigma, int64_t M, const double *ystar_host, int32_t S, int64_t idx_offset,
+                     double *acq_out /* optional [M] */, gpbo_result *result, void *work, int64_t work_bytes, void *stream);
+int gpbo_mes_log_survival_host_f64(const double *mu_host, const double *sigma_host, int64_t M, const double *z_host, int32_t Q,
+                                   double *out_host, int64_t *nan_out_host);
+int gpbo_mes_acq_host_f64(const double *mu_host, const double *sigma_host, int64_t M, const double *ystar_host, int32_t S,
+                          double *acq_out_host, gpbo_result *result_host);
 
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;

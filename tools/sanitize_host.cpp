@@ -213,6 +213,32 @@ int main() {
         EXPECT(gpbo_nei_host_f64(pd, pd, 100, 2, ls, 0, 0.09, 0.0, 1e-6, pd, 1000, pd, pd, 65, 0.0, 0, nullptr, nullptr, nullptr, nullptr,
                                  nullptr, &res_n, &info_n) == GPBO_ERR_ARG);
     }
+    // max-value entropy search (tests/test_mes_abi_cpu.py): the ranges of M, Q and S, the values that travel by value read on
+    // the host (only the first Q / S of them), the constant workspace one byte short or misaligned
+    {
+        gpbo_result res_m;
+        int64_t nan_m = 0;
+        double lv[64], bad[3] = {0.0, 1.0, __builtin_nan("")};
+        for (int q = 0; q < 64; ++q) lv[q] = -1.0 + q / 32.0;
+        auto surv = [&](int64_t M, const double *z, int32_t Q, void *w, int64_t wbytes) {
+            return gpbo_mes_log_survival_f64(pd, pd, M, z, Q, pd, reinterpret_cast<int64_t *>(pd), w, wbytes, nullptr);
+        };
+        auto acq = [&](int64_t M, const double *y, int32_t S, void *w, int64_t wbytes) {
+            return gpbo_mes_acq_f64(pd, pd, M, y, S, 0, nullptr, &res_m, w, wbytes, nullptr);
+        };
+        const int64_t wm = GPBO_MES_WORK_BYTES;
+        EXPECT(surv(0, lv, 63, p, wm) == GPBO_ERR_ARG && surv(((int64_t)1 << 40) + 1, lv, 63, p, wm) == GPBO_ERR_ARG);
+        EXPECT(surv(1000, lv, 0, p, wm) == GPBO_ERR_ARG && surv(1000, lv, 65, p, wm) == GPBO_ERR_ARG);
+        EXPECT(surv(1000, bad, 3, p, wm) == GPBO_ERR_ARG && surv(1000, bad, 2, p, wm - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(surv(1000, lv, 64, p, wm - 1) == GPBO_ERR_WORKSPACE && surv(1000, lv, 64, static_cast<char *>(p) + 8, wm) == GPBO_ERR_WORKSPACE);
+        EXPECT(surv(1000, nullptr, 1, p, wm) == GPBO_ERR_ARG && surv(1000, lv, 1, nullptr, wm) == GPBO_ERR_ARG);
+        EXPECT(acq(0, lv, 16, p, wm) == GPBO_ERR_ARG && acq(1000, lv, 0, p, wm) == GPBO_ERR_ARG && acq(1000, lv, 65, p, wm) == GPBO_ERR_ARG);
+        EXPECT(acq(1000, bad, 3, p, wm) == GPBO_ERR_ARG && acq(1000, lv, 64, p, wm - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(gpbo_mes_log_survival_host_f64(pd, pd, 10, bad, 3, pd, &nan_m) == GPBO_ERR_ARG);
+        EXPECT(gpbo_mes_log_survival_host_f64(pd, pd, 10, lv, 65, pd, &nan_m) == GPBO_ERR_ARG);
+        EXPECT(gpbo_mes_acq_host_f64(pd, pd, 0, lv, 16, nullptr, &res_m) == GPBO_ERR_ARG);
+        EXPECT(gpbo_mes_acq_host_f64(pd, pd, 10, bad, 3, nullptr, &res_m) == GPBO_ERR_ARG);
+    }
     // the likelihood of many hyperparameter cells and the ensemble pass (tests/test_marginal_abi_cpu.py): the size limits, the
     // model table read on the host (weights, scales, every model's length scales), the workspace one byte short
     {
