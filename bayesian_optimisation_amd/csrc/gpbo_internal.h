@@ -159,7 +159,10 @@ int gpbo_kstar_mu_mfma(const double *Xs, int64_t Mc, int64_t N, int64_t Np, int3
                        int64_t store_rows, void *stream);
 int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
                        const double *ls_host, int32_t kernel, const double *alpha, double diag_add, int64_t cand_base,
-                       double *KsT, int64_t ldk, double *mu_part, int64_t store_rows, void *stream);
+                       double *KsT, int64_t ldk, double *mu_part, int64_t store_rows,
+                       int beside /* the co-resident form where it exists (gpbo_kstar_beside_ok), same bits */, void *stream);
+// the co-resident form exists for this feature count / family, and a launch of `chunk` candidates is one workgroup per compute unit
+bool gpbo_kstar_beside_ok(int32_t d, int32_t kernel, double diag_add, int64_t chunk);
 int gpbo_kstar_mu_anyd(const double *Xs, int64_t Mc, const double *X, int64_t N, int64_t Np, int32_t d, const double *ls_host,
                        const double *alpha, double diag_add, int64_t cand_base, double *KsT, int64_t ldk, double *mu_part,
                        void *stream);

@@ -84,20 +84,31 @@ __device__ __forceinline__ void store_pair(float *p, double a, double b) {
 // fp64 path - the mean partials are the same doubles bit for bit - and only the stored K*^T is rounded to fp32
 // (relative error <= 2^-24 per entry) for the fp32 variance screen.
 // KERN: cov_from_s<KERN> (cov_entry.h).  The HAS_DIAG quirk belongs to the reference's kernel_rbf: squared exponential only.
-template <int D, int VARIANT, bool HAS_DIAG, typename TK, bool NT, int KERN = GPBO_KERNEL_SE>
-__global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict__ Xs, int64_t Mc,
+// BESIDE = false: grid (ldk_used/512, Np/64), one slice of 64 observations per workgroup.
+// BESIDE = true: the form that runs on the compute units of a variance launch (sigma_acq.hip: K(X*,X) of chunk c + 1 beside
+// the variance kernel of chunk c).  A variance workgroup leaves 64 of a SIMD's 512 registers and 4 KiB of LDS free, so this
+// form is held to 64 VGPRs (waves-per-EU 8) and is instantiated only where that costs neither a spill nor scratch
+// (KSTAR_BESIDE_MAX_D).  Its grid is (ldk_used/512, gy) with gy chosen by the launcher so that there is one workgroup per
+// compute unit at the most, each walking the slices blockIdx.y, blockIdx.y + gy, ...: once the workgroups are resident nothing
+// is pending that could take a freed compute unit ahead of the next variance workgroup.  Per entry the same instructions and
+// over n the same order as the other form, hence the same bits.
+template <int D, int VARIANT, bool HAS_DIAG, bool BESIDE, typename TK, bool NT, int KERN = GPBO_KERNEL_SE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BESIDE ? 8 : 0, BESIDE ? 8 : 0)))
+void kstar_mu_kernel(const double *__restrict__ Xs, int64_t Mc,
                                                        const double *__restrict__ Xsc, int N, CovLs ls,
                                                        const double *__restrict__ alpha, double diag_add,
                                                        int64_t cand_base, TK *__restrict__ KsT, int64_t ldk,
                                                        double *__restrict__ mu_part,
                                                        int store_rows /* rows n >= store_rows are not stored (multiple of 64):
                                                                          the prefix-bound screen needs the mean of all N
-                                                                         observations but K*^T of the first few only */) {
+                                                                         observations but K*^T of the first few only */,
+                                                       int nslices /* BESIDE: Np / 64 (the grid no longer says) */) {
     static_assert(KERN == GPBO_KERNEL_SE || (!HAS_DIAG && VARIANT == 0), "the quirk and the timing variants are SE-only");
+    static_assert(!BESIDE || (VARIANT == 0 && !HAS_DIAG && KERN == GPBO_KERNEL_SE), "the co-resident form: the plain build only");
+    static_assert(!BESIDE || sizeof(TK) == sizeof(double), "the co-resident form: fp64 rows (one byte offset serves K*^T and mu_part)");
     __shared__ double tab[GPBO_EXP_E];
     cov_stage_tab(tab, threadIdx.x);
     const int64_t c0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    const int n0 = blockIdx.y * KS_SLICE;
     double xa[D], xb[D];   // (the scaled load stays written out: see cov_entry.h)
 #pragma unroll
     for (int k = 0; k < D; ++k) {
@@ -105,21 +116,30 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
         xb[k] = ((c0 + 1 < Mc) ? Xs[(c0 + 1) * D + k] : 0.0) * ls.isc[k];
     }
     __syncthreads();
-    double mua = 0.0, mub = 0.0;
     bool nan_a = false, nan_b = false;  // NaN candidate coordinates: the reference's k is NaN, hence mu and the acquisition
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         nan_a = nan_a || (xa[k] != xa[k]);
         nan_b = nan_b || (xb[k] != xb[k]);
     }
-    TK *out = KsT + (int64_t)n0 * ldk + c0;
+    // BESIDE: rows are addressed as a wave-uniform base plus the thread's 32-bit byte offset (a row is at most 2^24 entries), which
+    // keeps the 64-bit c0 and a 64-bit pointer per thread out of the loop: three registers of the 64
+    const unsigned voff = ((unsigned)blockIdx.x * 256u + threadIdx.x) * 2u * (unsigned)sizeof(TK);
+    auto at = [&](auto *row) { return BESIDE ? reinterpret_cast<decltype(row)>(reinterpret_cast<char *>(row) + voff) : row; };
+    int by = blockIdx.y;
+    do {   // (BESIDE: the slices of this workgroup; else the one slice)
+    const int n0 = by * KS_SLICE;
+    double mua = 0.0, mub = 0.0;
+    TK *out = KsT + (int64_t)n0 * ldk + (BESIDE ? 0 : c0);
     const bool do_store = n0 < store_rows;   // workgroup-uniform
     int nend = n0 + KS_SLICE;
     if (nend > N) nend = N;  // observations beyond N are padding: exact zeros, written below
     // two observations per trip: four independent distance/exp chains per thread (the loop is bound by the
-    // latency of dependent fp64 instructions, not by their count)
+    // latency of dependent fp64 instructions, not by their count).  BESIDE: one observation per trip throughout (the tail's
+    // form below: two chains, the registers of the other two are what the cap takes) - per entry the same instructions, and the
+    // mean partials add up in the same order over n either way.
     int n = n0;
-    for (; n + 1 < nend; n += 2) {
+    if (!BESIDE) for (; n + 1 < nend; n += 2) {
         const double *xo0 = Xsc + (int64_t)n * D;  // wave-uniform rows -> scalar loads
         const double *xo1 = xo0 + D;
         double s00, s01, s10, s11;
@@ -143,8 +163,8 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
         mub = fma(k11, a1, mub);
         if (VARIANT != 1) {
             if (do_store) {
-                store_pair<NT>(out, k00, k01);
-                store_pair<NT>(out + ldk, k10, k11);
+                store_pair<NT>(at(out), k00, k01);
+                store_pair<NT>(at(out + ldk), k10, k11);
             }
         } else {
             mua += (k00 + k10) * 1e-300;
@@ -152,7 +172,7 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
         }
         out += 2 * ldk;
     }
-    if (n < nend) {  // odd tail
+    if (n < nend) do {  // odd tail
         const double *xo = Xsc + (int64_t)n * D;
         double sa, sb;
         cov_s2<D>(xa, xb, xo, sa, sb);
@@ -164,16 +184,18 @@ __global__ __launch_bounds__(256) void kstar_mu_kernel(const double *__restrict_
         const double an = alpha[n];
         mua = fma(ka, an, mua);
         mub = fma(kb, an, mub);
-        if (do_store) store_pair<NT>(out, ka, kb);
+        if (do_store) store_pair<NT>(at(out), ka, kb);
         out += ldk;
         ++n;
-    }
+    } while (BESIDE && n < nend);
     for (n = (nend > n0 ? nend : n0); n < n0 + KS_SLICE; ++n) {
-        if (do_store) store_pair<NT>(out, 0.0, 0.0);
+        if (do_store) store_pair<NT>(at(out), 0.0, 0.0);
         out += ldk;
     }
     d2_t m = {nan_a ? __builtin_nan("") : mua, nan_b ? __builtin_nan("") : mub};
-    *reinterpret_cast<d2_t *>(mu_part + (int64_t)blockIdx.y * ldk + c0) = m;
+    *reinterpret_cast<d2_t *>(at(mu_part + (int64_t)by * ldk + (BESIDE ? 0 : c0))) = m;
+    by += gridDim.y;
+    } while (BESIDE && by < nslices);
 }
 
 // Xsc[n][k] = X[n][k] / (ls_k sqrt 2), rows n >= N zero.   One thread per element.
@@ -368,14 +390,50 @@ extern "C" int gpbo_kstar_mu_f64(const double *Xs, int64_t Mc, const double *Xsc
 extern "C" int gpbo_kstar_mu_kern_f64(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
                                       const double *ls_host, int32_t kernel, const double *alpha, double diag_add,
                                       int64_t cand_base, double *KsT, int64_t ldk, double *mu_part, void *stream) {
-    return gpbo_kstar_mu_rows(Xs, Mc, Xsc, N, Np, d, ls_host, kernel, alpha, diag_add, cand_base, KsT, ldk, mu_part, Np, stream);
+    // GPBO_KSTAR_BESIDE=1: this stand-alone entry launches the co-resident form (tests and A/B runs compare it with the shipped one)
+    static const bool beside_env = env_flag("GPBO_KSTAR_BESIDE");
+    return gpbo_kstar_mu_rows(Xs, Mc, Xsc, N, Np, d, ls_host, kernel, alpha, diag_add, cand_base, KsT, ldk, mu_part, Np, beside_env,
+                              stream);
 }
+
+// The co-resident form of kstar_mu_kernel (BESIDE) exists for the feature counts at which the 64-register cap costs no spill and
+// no scratch (hipcc -Rpass-analysis=kernel-resource-usage; DESIGN.md 8b lists them), for the squared exponential without the
+// N == M quirk, with fp64 stores.
+constexpr int KSTAR_BESIDE_MAX_D = 9;
+static int compute_units() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return cus;
+}
+// ... and a launch is bounded to one workgroup per compute unit only while its candidate blocks (512 candidates each) are no more
+// than the compute units: a larger chunk keeps the in-order path
+bool gpbo_kstar_beside_ok(int32_t d, int32_t kernel, double diag_add, int64_t chunk) {
+    return d >= 1 && d <= KSTAR_BESIDE_MAX_D && kernel == GPBO_KERNEL_SE && diag_add == 0.0 &&
+           round_up_granule(chunk) / 512 <= compute_units();
+}
+
+namespace {
+template <int DD>
+void launch_kstar_beside(bool nt, dim3 grid, hipStream_t st, const double *Xs, int64_t Mc, const double *Xsc, int N, const CovLs &ls,
+                         const double *alpha, int64_t cand_base, double *KsT, int64_t ldk, double *mu_part, int store_rows,
+                         int nslices) {
+    if constexpr (DD <= KSTAR_BESIDE_MAX_D) {
+        if (nt)
+            hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, true, double, true>), grid, dim3(256), 0, st, Xs, Mc, Xsc, N, ls,
+                               alpha, 0.0, cand_base, KsT, ldk, mu_part, store_rows, nslices);
+        else
+            hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, true, double, false>), grid, dim3(256), 0, st, Xs, Mc, Xsc, N, ls,
+                               alpha, 0.0, cand_base, KsT, ldk, mu_part, store_rows, nslices);
+    }
+}
+}  // namespace
 
 // store_rows: only rows n < store_rows of K*^T are written (a multiple of 64; Np = everything); the mean partials always
 // cover all N observations.
+// beside != 0: the co-resident form where gpbo_kstar_beside_ok() says it exists (the same bits), the shipped form elsewhere.
 int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t N, int64_t Np, int32_t d,
                        const double *ls_host, int32_t kernel, const double *alpha, double diag_add, int64_t cand_base,
-                       double *KsT, int64_t ldk, double *mu_part, int64_t store_rows, void *stream) {
+                       double *KsT, int64_t ldk, double *mu_part, int64_t store_rows, int beside, void *stream) {
     if (!Xs || !Xsc || !alpha || !KsT || !mu_part) return GPBO_ERR_ARG;
     if (!kernel_ok(kernel, d, diag_add)) return GPBO_ERR_ARG;
     if (store_rows < 0 || store_rows > Np || store_rows % KS_SLICE) return GPBO_ERR_ARG;
@@ -386,6 +444,7 @@ int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t 
     if (rc != GPBO_OK) return rc;
     const int64_t used = round_up_granule(Mc);
     dim3 grid((unsigned)(used / 512), (unsigned)(Np / KS_SLICE));
+    const int nslices = (int)(Np / KS_SLICE);
     // Timing-only variants (1 = no stores, 3 = stores with a trivial body; wrong results) exist only in a diagnostics
     // build (GPBO_DIAG=1 bayesian_optimisation_amd/csrc/build.sh); the shipped library has no switch into them.
 #ifdef GPBO_DIAGNOSTICS
@@ -394,14 +453,30 @@ int gpbo_kstar_mu_rows(const double *Xs, int64_t Mc, const double *Xsc, int64_t 
     constexpr int variant = 0;
 #endif
     const bool nt = (int64_t)sizeof(double) * store_rows * ldk > ((int64_t)1 << 30);  // slab beyond what the Infinity Cache keeps
+    if (beside && variant == 0 && gpbo_kstar_beside_ok(d, kernel, diag_add, Mc)) {
+        // one workgroup per compute unit at the most (see kstar_mu_kernel): the slices are dealt out over cus / nbx rows of them
+        int gy = (int)(compute_units() / (used / 512));
+        if (gy > nslices) gy = nslices;
+#ifdef GPBO_BESIDE_FULL_GRID   // (A/B builds: every slice its own workgroup, the unbounded grid of DESIGN.md 8b)
+        gy = nslices;
+#endif
+        const dim3 gb((unsigned)(used / 512), (unsigned)gy);
+#define CALL(DD)                                                                                                        \
+    launch_kstar_beside<DD>(nt, gb, gpbo_stream(stream), Xs, Mc, Xsc, (int)N, ls, alpha, cand_base, KsT, ldk, mu_part, \
+                            (int)store_rows, nslices)
+        GPBO_FOR_D(d, CALL)
+#undef CALL
+        GPBO_CHECK_LAUNCH();
+        return GPBO_OK;
+    }
 #define KSTAR_LAUNCH1(DD, V, H, NTF)                                                                                  \
-    hipLaunchKernelGGL((kstar_mu_kernel<DD, V, H, double, NTF>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, Xsc, (int)N, \
-                       ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)store_rows)
+    hipLaunchKernelGGL((kstar_mu_kernel<DD, V, H, false, double, NTF>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, Xsc, (int)N, \
+                       ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)store_rows, nslices)
 #define KSTAR_LAUNCH(DD, V, H) \
     do { if (nt) KSTAR_LAUNCH1(DD, V, H, true); else KSTAR_LAUNCH1(DD, V, H, false); } while (0)
 #define KSTAR_MATERN1(DD, NTF, KK)                                                                                                \
-    hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, double, NTF, KK>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, Xsc, (int)N, \
-                       ls, alpha, 0.0, cand_base, KsT, ldk, mu_part, (int)store_rows)
+    hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, false, double, NTF, KK>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, Xsc, (int)N, \
+                       ls, alpha, 0.0, cand_base, KsT, ldk, mu_part, (int)store_rows, nslices)
 #define KSTAR_MATERN(DD, KK) \
     do { if (nt) KSTAR_MATERN1(DD, true, KK); else KSTAR_MATERN1(DD, false, KK); } while (0)
 #ifdef GPBO_DIAGNOSTICS
@@ -441,14 +516,14 @@ int gpbo_kstar_mu_mixed(const double *Xs, int64_t Mc, const double *Xsc, int64_t
     const bool nt = (int64_t)sizeof(float) * Np * ldk > ((int64_t)1 << 30);
 #define CALL(DD)                                                                                                     \
     if (diag_add != 0.0)                                                                                             \
-        hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, true, float, false>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc,  \
-                           Xsc, (int)N, ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)Np);                 \
+        hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, true, false, float, false>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc,  \
+                           Xsc, (int)N, ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)Np, (int)(Np / KS_SLICE));                 \
     else if (nt)                                                                                                     \
-        hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, float, true>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc,  \
-                           Xsc, (int)N, ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)Np);                 \
+        hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, false, float, true>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc,  \
+                           Xsc, (int)N, ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)Np, (int)(Np / KS_SLICE));                 \
     else                                                                                                             \
-        hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, float, false>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, \
-                           Xsc, (int)N, ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)Np)
+        hipLaunchKernelGGL((kstar_mu_kernel<DD, 0, false, false, float, false>), grid, dim3(256), 0, gpbo_stream(stream), Xs, Mc, \
+                           Xsc, (int)N, ls, alpha, diag_add, cand_base, KsT, ldk, mu_part, (int)Np, (int)(Np / KS_SLICE))
     GPBO_FOR_D(d, CALL)
 #undef CALL
     GPBO_CHECK_LAUNCH();

@@ -492,13 +492,14 @@ __global__ __launch_bounds__(256) void acq_argmax_kernel(const double *__restric
     }
 }
 
-// Helper stream + events for the K(X*,X) / variance overlap, one set per device, created on first use and
-// kept for the life of the process (nothing is retained about the caller's buffers).  Opt-in only (GPBO_OVERLAP=1, a
-// measured null result kept for A/B runs): with it, ONE scoring call per device at a time - two callers on different
-// streams would re-record the same events.  The table itself is created under a lock.
+// Helper stream + events for the K(X*,X) / variance overlap, one set per device, created on first use and kept for the life of
+// the process (nothing is retained about the caller's buffers).  ONE scoring call per device at a time records these events: a
+// call holds `busy` from its first record to its last (HelperLease), and a caller that finds it taken - another thread on
+// another stream - runs the in-order path, which gives the same bits.  The table itself is created under a lock.
 struct Helper {
     hipStream_t stream;
     hipEvent_t fork, kdone[2], sdone[2];
+    std::mutex busy;
 };
 
 Helper *helper_for_current_device() {
@@ -509,6 +510,8 @@ Helper *helper_for_current_device() {
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
     if (!tab[dev]) {
         Helper *h = new Helper;
+        // (default priority: with the lowest one of hipDeviceGetStreamPriorityRange the unbounded grid stays zero-sum and the
+        //  bounded grid gains nothing)
         bool ok = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) == hipSuccess;
         ok = ok && hipEventCreateWithFlags(&h->fork, hipEventDisableTiming) == hipSuccess;
         for (int i = 0; i < 2 && ok; ++i) {
@@ -520,6 +523,22 @@ Helper *helper_for_current_device() {
     }
     return tab[dev];
 }
+
+// the helper of this device for the length of a scoring call, or nothing (get() == nullptr) when another call holds it
+class HelperLease {
+    Helper *h_ = nullptr;
+
+public:
+    explicit HelperLease(bool wanted) {
+        if (!wanted) return;
+        Helper *h = helper_for_current_device();
+        if (h && h->busy.try_lock()) h_ = h;
+    }
+    ~HelperLease() { if (h_) h_->busy.unlock(); }
+    HelperLease(const HelperLease &) = delete;
+    HelperLease &operator=(const HelperLease &) = delete;
+    Helper *get() const { return h_; }
+};
 
 static_assert(BN == GPBO_NPAD, "f64_column_groups (host_driver.h) counts column blocks of GPBO_NPAD");
 
@@ -880,20 +899,30 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
         if (rc0 != GPBO_OK) return rc0;
     }
 
-    // Measured on MI355X (N=512, M=2^20): running K(X*,X) of chunk c+1 beside the variance kernel of chunk c gains
-    // nothing - the variance launches slow down by what the overlap hides (0.59 -> 0.70 ms), i.e. fp64 VALU work
-    // and fp64 MFMA work do not co-execute on gfx950.  The same at N = 4096, 2^21 candidates (same box, two runs each):
-    // 507.0 / 507.6 ms per step without, 508.4 / 507.3 ms with; the variance launches 30.67 -> 31.54 ms, which is the
-    // 0.9 ms of the K(X*,X) launch that ran beside them.  Kept as an opt-in (GPBO_OVERLAP=1) for other shapes.
+    // K(X*,X) of chunk c + 1 beside the variance kernel of chunk c.  As two ordinary launches this is zero-sum:
+    // a variance workgroup holds 448 of a SIMD's 512 registers and all but 4 KiB of the LDS, a 72-register K(X*,X) workgroup never
+    // shares a compute unit with it, and the two kernels time-slice whole compute units (N = 4096, 2^21 candidates: the variance
+    // launches 29.51 -> 30.16 ms, the step 485.8 -> 485.6 ms; the 64-register form in an unbounded grid: 30.29 ms, 487.7 ms).
+    // The co-resident form of kstar_mu_kernel (kernel_build.hip) in its bounded grid - one workgroup per compute unit, resident
+    // beside the variance workgroups from the start of the launch - costs the variance launch 0.34 ms (29.51 -> 29.85) for a
+    // build that takes 0.70 ms alone and issues 0.5 ms of fp64 vector instructions: 480.8 against 485.8 ms per step.  So an fp64
+    // vector instruction of another wave does take the SIMD's issue slot from the fp64 MFMA, but only about two thirds of the
+    // build's vector issue shows up as lost matrix time, and none of its store time.
+    // Default where that form exists, the call has more than one chunk and takes the grouped launch (below that the launches
+    // are too short to matter); GPBO_OVERLAP=0 switches it off (the A/B switch), any other value switches it on for every call
+    // of more than one chunk (the co-resident form where it exists, the stand-alone form elsewhere).
     const int64_t nchunks = (M + chunk - 1) / chunk;
-    Helper *hp = (nchunks > 1 && overlap_env) ? helper_for_current_device() : nullptr;
-    // Fork: the helper stream builds K(X*,X)+mu of chunk c+1 (fp64 VALU + HBM writes) while the caller's
-    // stream runs the variance kernel of chunk c (matrix cores); two chunk buffers, events both ways.
+    static const int overlap_mode = env_int("GPBO_OVERLAP", -1);   // -1: not set
+    const bool beside = !anyd && !kstar_mfma && gpbo_kstar_beside_ok(d, gp.kernel, diag_add, chunk);
+    const bool overlap = nchunks > 1 && (overlap_env || (overlap_mode < 0 && beside && split_max == 1 && n_prefix == 0 &&
+                                                         f64_column_groups(M, Np) > 1));
+    // (a second caller on this device while this call records: in order, the same bits)
+    const HelperLease lease(overlap);
+    Helper *hp = lease.get();
+    // Fork: the helper stream builds K(X*,X)+mu of chunk c+1 (fp64 VALU + HBM writes) while the caller's stream runs the
+    // variance kernel of chunk c (matrix cores); two chunk buffers, events both ways.  Chunk 0 has nothing to run beside: it is
+    // built on the caller's stream in the stand-alone form, and the fork follows it.
     hipStream_t ks = hp ? hp->stream : st;
-    if (hp) {
-        if (hipEventRecord(hp->fork, st) != hipSuccess || hipStreamWaitEvent(ks, hp->fork, 0) != hipSuccess)
-            return GPBO_ERR_LAUNCH;
-    }
     // partials of the mean per candidate: 64-observation slices, coarser ones from the matrix-core K(X*,X) kernel
     const int nsl = kstar_mfma ? (int)(Np / gpbo_kstar_mfma_slice(Np)) : (int)(Np / GPBO_KS_SLICE);
     ProfileRecorder slots(prof);
@@ -901,9 +930,12 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
         const int64_t s = c * chunk;
         const int64_t Mc = (M - s < chunk) ? (M - s) : chunk;
         const int b = (int)(c & 1);
-        // K(X*,X) launches are timed only in the plain in-order mode, where the launches of this call form one chain
-        // on the caller's stream
-        if (!slots.kstar(ks, c > 0, !hp)) return GPBO_ERR_LAUNCH;
+        hipStream_t kst = (hp && c > 0) ? ks : st;
+        // The K(X*,X) interval of a slot is timed where the launch runs alone on the caller's stream: every chunk in the in-order
+        // mode, chunk 0 of a call in the overlapped mode - so the figure read from the slots stays the stand-alone build's; the
+        // builds that run beside a variance launch show up in that launch's interval (begin / end below), which is what they cost.
+        // (a build on the helper stream is enqueued while the slot of the chunk before it is still open: marked untimed below)
+        if ((!hp || c == 0) && !slots.kstar(st, c > 0)) return GPBO_ERR_LAUNCH;
         int rc;
         if (kstar_mfma) {
             // The MEAN of all N observations from the matrix-core kernel (expanded distances; reported from below by its
@@ -912,26 +944,30 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
             // (unnormalised inputs), is amplified by |U| and would need a data-dependent variance pad; with the plain
             // pass's own entries |v[:J]|^2 is a partial sum of the very squares the plain pass adds up, so the bound
             // holds for any inputs.  Costs n_prefix / N of the fp64-VALU kernel: 6 % at N / 16.
-            rc = gpbo_kstar_mu_mfma(Xs + s * d, Mc, N, Np, d, ls_host, alpha, L.prep, L.kst[b], chunk, L.mup[b], 0, ks);
+            rc = gpbo_kstar_mu_mfma(Xs + s * d, Mc, N, Np, d, ls_host, alpha, L.prep, L.kst[b], chunk, L.mup[b], 0, kst);
             if (rc != GPBO_OK) return rc;
             const int64_t nrow = (N < n_prefix) ? N : n_prefix;
             // (its mean partials - of the first n_prefix observations only - are not wanted: they go to rows of the K*^T
             //  slab that the prefix mode neither writes nor reads, [n_prefix, n_prefix + n_prefix / 64))
             rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, L.xsc, nrow, n_prefix, d, ls_host, GPBO_KERNEL_SE, alpha, 0.0, idx_offset + s,
-                                    L.kst[b], chunk, L.kst[b] + n_prefix * chunk, n_prefix, ks);
+                                    L.kst[b], chunk, L.kst[b] + n_prefix * chunk, n_prefix, 0, kst);
         } else if (anyd) {
             rc = gpbo_kstar_mu_anyd(Xs + s * d, Mc, X, N, Np, d, ls_host, alpha, diag_add, idx_offset + s, L.kst[b], chunk,
-                                    L.mup[b], ks);
+                                    L.mup[b], kst);
         } else {
             rc = gpbo_kstar_mu_rows(Xs + s * d, Mc, L.xsc, N, Np, d, ls_host, gp.kernel, alpha, diag_add, idx_offset + s, L.kst[b],
-                                    chunk, L.mup[b], n_prefix ? n_prefix : Np, ks);
+                                    chunk, L.mup[b], n_prefix ? n_prefix : Np, hp && c > 0 && beside, kst);
         }
         if (rc != GPBO_OK) return rc;
-        if (hp && hipEventRecord(hp->kdone[b], ks) != hipSuccess) return GPBO_ERR_LAUNCH;
+        if (hp && c > 0 && hipEventRecord(hp->kdone[b], ks) != hipSuccess) return GPBO_ERR_LAUNCH;
         return GPBO_OK;
     };
     int rc = launch_kstar(0);
     if (rc != GPBO_OK) return rc;
+    if (hp) {
+        if (hipEventRecord(hp->fork, st) != hipSuccess || hipStreamWaitEvent(ks, hp->fork, 0) != hipSuccess)
+            return GPBO_ERR_LAUNCH;
+    }
     int64_t nparts = 0;
     for (int64_t c = 0; c < nchunks; ++c) {
         const int64_t s = c * chunk;
@@ -943,8 +979,9 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
             rc = launch_kstar(c + 1);
             if (rc != GPBO_OK) return rc;
         }
-        if (hp && hipStreamWaitEvent(st, hp->kdone[b], 0) != hipSuccess) return GPBO_ERR_LAUNCH;
+        if (hp && c > 0 && hipStreamWaitEvent(st, hp->kdone[b], 0) != hipSuccess) return GPBO_ERR_LAUNCH;
         const int64_t nblk = (Mc + BM - 1) / BM;
+        if (hp && c > 0 && !slots.kstar(st, false, false)) return GPBO_ERR_LAUNCH;
         if (!slots.begin(st)) return GPBO_ERR_LAUNCH;
         const int S = split_factor(nblk, (n_prefix ? n_prefix : Np) / BN, split_max);
         // Column groups on one XCD for large calls (see the kernel): measured on MI355X at N = 4096, 2^21 candidates,

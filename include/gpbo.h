@@ -32,7 +32,10 @@ extern "C" {
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
  *   GPBO_F64_GROUPS=g     column groups of the fp64 variance kernel for large calls (default 8: one per XCD)
- *   GPBO_OVERLAP=1        K(X*,X) of chunk c + 1 on a second stream beside the variance launch of chunk c (measured: no gain)
+ *   GPBO_OVERLAP=0        never build K(X*,X) of chunk c + 1 on a second stream beside the variance launch of chunk c (the default
+ *                         does where the co-resident K(X*,X) form exists - d <= 9, squared exponential - and the call takes the
+ *                         grouped variance launch: -1.0 % per headline step); any other value: for every call of several chunks
+ *   GPBO_KSTAR_BESIDE=1   gpbo_kstar_mu_f64 / gpbo_kstar_mu_kern_f64 launch the co-resident form (the same bits; tests, A/B runs)
  *   GPBO_PREFIX_VALU=1    the prefix bound's first-level mean from the difference-form kernel instead of the MFMA one
  *   GPBO_FACTOR_OLD=1     the round-2 factorisation chain (Cholesky + triangular inverse) instead of the fused sweep
  *   GPBO_NO_LOOKAHEAD=1   that chain without its helper stream
