@@ -37,6 +37,10 @@ NEI_MAX_S = 64           # gpbo_posterior_nei_kern_f64: fantasies per call
 MES_MAX_LEVELS = 64      # gpbo_mes_log_survival_f64: levels per call
 MES_MAX_S = 64           # gpbo_mes_acq_f64: sampled minima per call
 MES_WORK_BYTES = 1 << 20   # the workspace of both: a constant
+CONS_BASE_NONE, CONS_BASE_EI, CONS_BASE_PI = 0, 1, 2   # gpbo_constrained_acq_f64: the base term (GPBO_CONS_BASE_*)
+CONS_BASE_IDS = {"none": CONS_BASE_NONE, "ei": CONS_BASE_EI, "pi": CONS_BASE_PI}
+CONS_MAX_C = 8             # ... constraints per call
+CONS_WORK_BYTES = 16640    # ... its workspace: a constant
 # covariance families of the gpbo_*_kern_f64 entry points (include/gpbo.h: GPBO_KERNEL_*)
 KERNEL_IDS = {"se": 0, "matern32": 1, "matern52": 2}
 
@@ -210,6 +214,8 @@ SIGNATURES = {
     "gpbo_mes_acq_f64": (C.c_int, [_p, _p, _i64, _p, _i32, _i64, _p, _p, _p, _i64, _p]),
     "gpbo_mes_log_survival_host_f64": (C.c_int, [_p, _p, _i64, _p, _i32, _p, _p]),
     "gpbo_mes_acq_host_f64": (C.c_int, [_p, _p, _i64, _p, _i32, _p, _p]),
+    "gpbo_constrained_acq_f64": (C.c_int, [_p, _p, _i64, _i32, _f64, _f64, _p, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p]),
+    "gpbo_constrained_acq_host_f64": (C.c_int, [_p, _p, _i64, _i32, _f64, _f64, _p, _p, _i64, _i32, _p, _p, _p, _p]),
     "gpbo_gemm_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
                                 _i32, _i32, _p]),
     "gpbo_gemm_tri_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,

@@ -11,6 +11,7 @@
 //   gpbo_thompson_host_f64         = the factorisation, then q points as minimisers of posterior sample paths (thompson.hip)
 //   gpbo_nei_host_f64              = the factorisation and its noise-free twin, then noisy expected improvement (nei.hip)
 //   gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64 = max-value entropy search on a dense posterior the caller holds (mes.hip)
+//   gpbo_constrained_acq_host_f64  = constrained EI / PI / probability of feasibility on dense posteriors the caller holds (constrained.hip)
 //   gpbo_refine_host_f64           = the factorisation, then gradient refinement of given starts off the grid (refine.hip)
 //   gpbo_nlml_grid_host_f64        = tune_kernel()'s likelihood grid (float32, the reference's det underflow)
 //   gpbo_nlml_grid_logdet_host_f64 = the same grid in fp64 with log det from the factor
@@ -444,6 +445,35 @@ extern "C" int gpbo_mes_acq_host_f64(const double *mu, const double *sigma, int6
     if (rc != GPBO_OK) return rc;
     bool okc = A.d2h(result, dres, sizeof(gpbo_result));
     if (acq_out) okc = okc && A.d2h(acq_out, dacq, sizeof(double) * M);
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+}
+
+// The constrained acquisitions on host arrays (csrc/constrained.hip): no factorisation - the call works on the dense posteriors
+// the caller already holds, the objective's and the C constraints' [C x ldc].  The refusals are the device entry's own
+// (cons_args_ok, host_driver.h), made before the arena exists; the rows are uploaded without their padding (ldc = M on the device).
+extern "C" int gpbo_constrained_acq_host_f64(const double *mu, const double *sigma, int64_t M, int32_t base, double f_best,
+                                             double xi, const double *cons_mu, const double *cons_sigma, int64_t ldc, int32_t C,
+                                             const double *upper, double *val_out, double *feas_out, gpbo_result *result) {
+    if (!cons_args_ok(mu, sigma, M, base, f_best, xi, cons_mu, cons_sigma, ldc, C, upper) || !result) return GPBO_ERR_ARG;
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    const bool reads = base != GPBO_CONS_BASE_NONE;
+    double *dmu = reads ? A.alloc<double>(M) : nullptr, *dsig = reads ? A.alloc<double>(M) : nullptr;
+    double *dcm = C > 0 ? A.alloc<double>(C * M) : nullptr, *dcs = C > 0 ? A.alloc<double>(C * M) : nullptr;
+    double *dval = val_out ? A.alloc<double>(M) : nullptr, *dfeas = feas_out ? A.alloc<double>(M) : nullptr;
+    gpbo_result *dres = A.alloc<gpbo_result>(1);
+    char *dwork = A.alloc<char>(GPBO_CONS_WORK_BYTES);   // (hipMalloc: 256-byte aligned)
+    if (!A.ok) return GPBO_ERR_WORKSPACE;
+    bool okc = !reads || (A.h2d(dmu, mu, sizeof(double) * M) && A.h2d(dsig, sigma, sizeof(double) * M));
+    for (int32_t c = 0; c < C && okc; ++c)
+        okc = A.h2d(dcm + c * M, cons_mu + c * ldc, sizeof(double) * M) && A.h2d(dcs + c * M, cons_sigma + c * ldc, sizeof(double) * M);
+    if (!okc) return GPBO_ERR_LAUNCH;
+    const int rc = gpbo_constrained_acq_f64(dmu, dsig, M, base, f_best, xi, dcm, dcs, M, C, upper, 0, dval, dfeas, dres, dwork,
+                                            GPBO_CONS_WORK_BYTES, A.st());
+    if (rc != GPBO_OK) return rc;
+    okc = A.d2h(result, dres, sizeof(gpbo_result));
+    if (val_out) okc = okc && A.d2h(val_out, dval, sizeof(double) * M);
+    if (feas_out) okc = okc && A.d2h(feas_out, dfeas, sizeof(double) * M);
     return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 

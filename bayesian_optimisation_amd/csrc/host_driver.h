@@ -69,6 +69,20 @@ inline bool mes_values_ok(int64_t M, const double *v_host, int32_t n, int32_t n_
     return true;
 }
 
+// the constrained acquisitions (constrained.hip and its host entry in host_api.hip): 1 <= M <= 2^40 candidates, one of the three
+// bases, 0 <= C <= GPBO_CONS_MAX_C constraints (at least one when there is no base) in rows of ldc >= M values, finite limits, a
+// finite f_best and xi where the base reads them; mu / sigma may be null only without a base, cons_* / upper only with C == 0
+inline bool cons_args_ok(const double *mu, const double *sigma, int64_t M, int32_t base, double f_best, double xi,
+                         const double *cons_mu, const double *cons_sigma, int64_t ldc, int32_t C, const double *upper_host) {
+    if (M < 1 || M > ((int64_t)1 << 40) || ldc < M || C < 0 || C > GPBO_CONS_MAX_C) return false;
+    if (base != GPBO_CONS_BASE_NONE && base != GPBO_CONS_BASE_EI && base != GPBO_CONS_BASE_PI) return false;
+    if (base == GPBO_CONS_BASE_NONE ? C == 0 : (!mu || !sigma || !(f_best - f_best == 0.0) || !(xi - xi == 0.0))) return false;
+    if (C > 0 && (!cons_mu || !cons_sigma || !upper_host)) return false;
+    for (int32_t c = 0; c < C; ++c)
+        if (!(upper_host[c] - upper_host[c] == 0.0)) return false;
+    return true;
+}
+
 // ---- the length scales as the kernels take them: il2[k] = 1 / ls_k^2 (cov_r2, cov_entry.h), isc[k] = 1 / (ls_k sqrt 2)
 // (the scoring form of cov_entry.h), k < d; either may be null.  EXACTLY these expressions: the values feed kernels whose
 // outputs are compared bit for bit.  The entries k >= d are the caller's.  false: a length scale that is not positive.

@@ -1,5 +1,5 @@
 // Scalar arithmetic of max-value entropy search (mes.hip): log Phi and the entropy term h, each in three branches
-// of which none cancels beyond what its bound states.  Used by the two kernels of mes.hip and by nothing else.
+// of which none cancels beyond what its bound states.  Used by the two kernels of mes.hip; log Phi also by cons_math.h (constrained.hip).
 //   gamma > 0         Phi = 1 - erfc(gamma / sqrt 2) / 2 is close to 1:       log1p(-erfc(gamma / sqrt 2) / 2)
 //   -1 <= gamma <= 0  Phi = erfc(-gamma / sqrt 2) / 2, in [0.158, 0.5]:       log(erfc(-gamma / sqrt 2) / 2)
 //   gamma < -1        t = -gamma / sqrt 2, Phi = exp(-t^2) erfcx(t) / 2 (Phi itself underflows at gamma ~ -38):

@@ -173,6 +173,18 @@ class MesResult:
     sigma: Optional[object] = None
 
 
+@dataclass
+class ConstrainedResult:
+    """What DeviceGP.constrained_on_posterior / select_constrained return.  Every value is a LOGARITHM (-inf is a legal value)."""
+    best_val: float
+    best_idx: int
+    nan_count: int
+    base: str                                     # the base term that was used: "ei", "pi" or "none"
+    value: Optional[object] = None                # dense=True: torch fp64 device tensors [M], base + log feasibility ...
+    log_feasibility: Optional[object] = None      # ... and sum_c log Phi((u_c - mu_c) / sigma_c) alone
+    f_best: Optional[float] = None                # the incumbent the base was measured against (None without a base)
+
+
 def refine_params(P: int, d: int, iters: int, step0: float) -> tuple:
     """(iters, step0) as the C ABI takes them; refuses what gpbo_refine_f64 refuses (include/gpbo.h)."""
     if not 1 <= int(P) <= _lib.REFINE_MAX_P:
@@ -351,7 +363,7 @@ class DeviceGP(DeviceSide, LikelihoodFits):
         # workspaces, kept from call to call and only ever grown (_workspace)
         self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
         self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = self._work_loo = None
-        self._work_nei = self._work_mes = None
+        self._work_nei = self._work_mes = self._work_cons = None
         self._epoch = 0              # counts factorise() / append() / load_state_dict(): ThompsonPaths belong to one of them
         self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
         self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
@@ -1253,6 +1265,90 @@ class DeviceGP(DeviceSide, LikelihoodFits):
         r = self.mes_on_posterior(s.mu, s.sigma, m, idx_offset=idx_offset, dense=dense)
         r.quartiles, r.mu, r.sigma = quartiles, s.mu, s.sigma
         return r
+
+    # -- constrained EI / PI / probability of feasibility in log space (csrc/constrained.hip) ------------
+    def constrained_on_posterior(self, mu, sigma, cons_mu, cons_sigma, upper, base: str = "ei", f_best: Optional[float] = None,
+                                 xi: float = 0.0, idx_offset: int = 0, dense: bool = True,
+                                 ldc: Optional[int] = None) -> ConstrainedResult:
+        """value(x) = base(x) + sum_c log Phi((upper_c - cons_mu_c(x)) / cons_sigma_c(x)) over dense posteriors and its first
+        arg-max (gpbo_constrained_acq_f64; the formulas and edge rules are stated in include/gpbo.h).  base: "ei" (log sigma +
+        log h(z): the logarithm of constrained expected improvement), "pi" (log Phi(z)) or "none" (the log-probability of
+        feasibility alone; mu / sigma may be None).  mu, sigma [M]; cons_mu, cons_sigma [C x M] (None or empty with no
+        constraint; with ldc: flat buffers whose row c starts at c ldc); upper [C].  f_best, xi: in the units of mu, needed
+        with a base.  Works without a factorisation.  One read-back (synchronises)."""
+        from .constrained import cons_limits, cons_params
+
+        torch = self.torch
+        u = cons_limits(upper)
+        C = int(u.size)
+        bid, fb, xi = cons_params(base, f_best, xi, C)
+        if bid == _lib.CONS_BASE_NONE:
+            mud = sgd = None
+        else:
+            mud, sgd, M = self._posterior_pair(mu, sigma)
+        cmd = csd = None
+        if C > 0:
+            cmd, csd = self._dev(cons_mu), self._dev(cons_sigma)
+            if ldc is None:
+                cmd, csd = cmd.reshape(C, -1), csd.reshape(C, -1)
+                ldc = int(cmd.shape[1])
+                if bid == _lib.CONS_BASE_NONE:
+                    M = ldc
+                elif ldc != M:
+                    raise ValueError("cons_mu and cons_sigma must hold one row of M values per limit (longer rows: pass ldc)")
+            elif bid == _lib.CONS_BASE_NONE:
+                raise ValueError("ldc needs a base (the candidate count is that of mu)")
+            ldc = int(ldc)
+            if ldc < M or M < 1 or int(cmd.numel()) < (C - 1) * ldc + M or csd.shape != cmd.shape:
+                raise ValueError("cons_mu and cons_sigma must hold one row of at least M values per limit")
+        with torch.cuda.device(self.device):
+            work = self._workspace("_work_cons", _lib.CONS_WORK_BYTES)
+            val = torch.empty(M, dtype=torch.float64, device=self.device) if dense else None
+            feas = torch.empty(M, dtype=torch.float64, device=self.device) if dense else None
+            _lib.call(self.lib.gpbo_constrained_acq_f64, mud, sgd, M, bid, fb, xi, cmd, csd, ldc if C > 0 else M, C, u,
+                      int(idx_offset), val, feas, self._result, work, _lib.CONS_WORK_BYTES, self._stream())
+            v, i, n = self.read_result(self._result)   # synchronises: cmd / csd have been consumed
+        return ConstrainedResult(v, i, n, base, val, feas, None if bid == _lib.CONS_BASE_NONE else fb)
+
+    def select_constrained(self, Xs, constraints=(), upper=(), base: str = "ei", f_best: Optional[float] = None,
+                           xi: float = 0.0, dense: bool = False, idx_offset: int = 0) -> ConstrainedResult:
+        """The next point by constrained expected improvement (base="ei"), constrained probability of improvement ("pi") or
+        the probability of feasibility ("none"): this surrogate and every DeviceGP of `constraints` - each factorised on ITS
+        quantity's observations, with any kernel family and model of its own - score the rows of Xs with the unchanged fp64
+        pass, then constrained_on_posterior() combines them.  upper: one limit per constraint, in the units of its
+        observations.  f_best: a number, or None for the smallest of this surrogate's observations among those at which every
+        constraint's observation is within its limit (constrained.feasible_incumbent: the same points in all surrogates); if
+        none is, the call maximises the probability of feasibility alone and the result's base says "none".  Every pass uses
+        its own factorisation's prior variance ((1 + jitter1) + jitter2).  ValueError on bad parameters, on a constraint that is
+        no DeviceGP or lives on another device, before any GPU work; GpboError for a surrogate that is not factorised."""
+        from .constrained import cons_limits, cons_params, feasible_incumbent
+
+        constraints = list(constraints)
+        u = cons_limits(upper, len(constraints))
+        cons_params(base, 0.0 if f_best is None else f_best, xi, len(constraints))
+        for g in constraints:
+            if not isinstance(g, DeviceGP) or g.device != self.device:
+                raise ValueError(f"select_constrained(): every constraint must be a DeviceGP on {self.device}")
+        for g in (self, *constraints):
+            if g.N < 1:
+                raise _lib.GpboError("select_constrained() needs a factorised surrogate for the objective and every constraint")
+        if base != "none" and f_best is None:
+            X0, y0 = self.observations_host()
+            obs = [g.observations_host() for g in constraints]
+            f_best = feasible_incumbent(X0, y0, [o[0] for o in obs], [o[1] for o in obs], u)
+            if f_best is None:
+                base = "none"
+        Xsd, M = self._candidates(Xs)
+        post = []
+        for g in (*constraints, *(() if base == "none" else (self,))):
+            pv = (1.0 + g.jitter1) + g.jitter2
+            s = g.score(g._candidates(Xsd)[0], acquisition="lcb", explore=0.0, dense=True, prior_var=pv)
+            post.append((s.mu, s.sigma))
+        mu, sigma = post.pop() if base != "none" else (None, None)
+        cm = self.torch.stack([p[0] for p in post]) if post else None
+        cs = self.torch.stack([p[1] for p in post]) if post else None
+        return self.constrained_on_posterior(mu, sigma, cm, cs, u, base=base, f_best=f_best, xi=xi, idx_offset=idx_offset,
+                                             dense=dense)
 
     # -- acquisition gradients and off-grid refinement (csrc/refine.hip, DESIGN 4d) -------------------------------
     def _points(self, Xq, what: str):

@@ -251,6 +251,38 @@ def mes_acq(mu, sigma, y_star, dense: bool = True, lib=None) -> dict:
     return dict(best_val=r["best_val"], best_idx=r["best_idx"], nan_count=r["nan_count"], acq=acq)
 
 
+def constrained_acq(mu, sigma, cons_mu, cons_sigma, upper, base: str = "ei", f_best=None, xi: float = 0.0, dense: bool = True,
+                    lib=None) -> dict:
+    """The constrained acquisitions on host arrays (gpbo_constrained_acq_host_f64): value = base + sum_c log Phi((upper_c -
+    cons_mu_c) / cons_sigma_c) over dense posteriors and its first arg-max; base "ei", "pi" or "none" (mu / sigma may be None
+    then).  cons_mu, cons_sigma: [C x M] (None or empty with no constraint).  Returns dict(best_val, best_idx, nan_count,
+    value [M], log_feasibility [M])."""
+    from .constrained import cons_limits, cons_params
+
+    u = cons_limits(upper)
+    C = int(u.size)
+    bid, fb, xi = cons_params(base, f_best, xi, C)
+    cm = cs = None
+    if C > 0:
+        cm, cs = _f64(cons_mu).reshape(C, -1), _f64(cons_sigma).reshape(C, -1)
+        if cm.shape != cs.shape or cm.shape[1] < 1:
+            raise ValueError("cons_mu and cons_sigma must hold one row of M values per limit")
+    if bid == _lib.CONS_BASE_NONE:
+        mu = sigma = None
+        M = int(cm.shape[1])
+    else:
+        mu, sigma, M = _posterior_pair(mu, sigma)
+        if C > 0 and cm.shape[1] != M:
+            raise ValueError("cons_mu and cons_sigma must hold one row of M values per limit")
+    lib = lib or _lib.load()
+    val, feas = (np.empty(M), np.empty(M)) if dense else (None, None)
+    out = _Result()
+    _lib.note_hip_use()
+    _lib.call(lib.gpbo_constrained_acq_host_f64, mu, sigma, M, bid, fb, xi, cm, cs, M, C, u, val, feas, out.res)
+    r = out.decode()
+    return dict(best_val=r["best_val"], best_idx=r["best_idx"], nan_count=r["nan_count"], value=val, log_feasibility=feas)
+
+
 def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
            iters: int = 30, step0: float = 0.1, lib=None) -> dict:
     """Off-grid refinement on host arrays (gpbo_refine_host_f64: factorisation and refinement in one call).  Returns
@@ -432,6 +464,21 @@ class PointSelectorHost(PointSelector):
             minima = y_star
         r = mes_acq(mu, sigma, minima, lib=self.lib)
         return r["acq"], (r["best_val"], r["best_idx"], r["nan_count"]), minima
+
+    def _cons_posterior(self) -> tuple:
+        """mean_func / cov_func taken back to the units of the model, as host arrays [M]."""
+        m = self._model
+        mu = _f64(m.to_model(np.asarray(self.mean_func, dtype=np.float64))).reshape(-1)
+        sigma = _f64(np.asarray(self.cov_func, dtype=np.float64) / m.y_scale if m.fitted else self.cov_func).reshape(-1)
+        return mu, sigma
+
+    def _cons_scores(self, base, f_best, xi, posteriors, upper):
+        """PointSelector._cons_scores on the host-pointer route (gpbo_constrained_acq_host_f64): the same values."""
+        mu, sigma = self._cons_posterior()
+        cm = np.stack([p[0] for p in posteriors]) if posteriors else None
+        cs = np.stack([p[1] for p in posteriors]) if posteriors else None
+        r = constrained_acq(mu, sigma, cm, cs, upper, base=base, f_best=f_best, xi=xi, lib=self.lib)
+        return r["value"], r["log_feasibility"], (r["best_val"], r["best_idx"], r["nan_count"])
 
     def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
         """PointSelector.refine_next on the host-pointer route (gpbo_refine_host_f64): the same d coordinates, the same

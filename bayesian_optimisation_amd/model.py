@@ -72,9 +72,13 @@ class SurrogateModel:
 
     def acq_to_y(self, kind: str, acq):
         """LCB = s acq - m (explore s sigma - (m + s mu)), EI / qEI = s acq.  Both maps increase, so the arg-max and its
-        tie rule are those of the kernels.  "mes" (max-value entropy search) has no unit: an entropy of a ratio."""
-        if not self.fitted or kind == "mes":
+        tie rule are those of the kernels.  "mes" (max-value entropy search) has no unit: an entropy of a ratio.  The
+        constrained acquisitions are LOGARITHMS: "log_cei" = log EI_model + log s (a probability of feasibility has no unit),
+        "log_pi" and "log_pof" are logarithms of probabilities and have none."""
+        if not self.fitted or kind in ("mes", "log_pi", "log_pof"):
             return acq
+        if kind == "log_cei":
+            return acq + float(np.log(self.y_scale))
         return self.y_scale * acq - self.y_mean if kind == "lcb" else self.y_scale * acq
 
     def best_to_y(self, kind: str, best):

@@ -26,7 +26,8 @@ Differences from the reference, all deliberate:
     Also extra: `expected_improvement(xi)`, `noisy_expected_improvement()` (EI averaged over samples of the best latent value at
     the observed points instead of measured against min(measured_vals), the luckiest noise draw: INTEGRATION.md 9),
     `max_value_entropy_search()` (the information gained about the minimum's value: no incumbent, no trade-off parameter;
-    INTEGRATION.md 10),
+    INTEGRATION.md 10), `constrained_expected_improvement()` / `probability_of_feasibility()` (black-box constraints, each a
+    selector object of its own; evaluated in log space) and `probability_of_improvement()`,
     `q_expected_improvement()`, `select_thompson(q)` (q points as the minimisers of posterior sample paths), `select_batch(q)` (q points for parallel evaluation: greedy Kriging believer / GP-BUCB /
     constant liar), `refine_next()` (the next point off the grid: the best candidates polished by acquisition gradients), `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
     calls go through the exact prefix bound), `kernel_params` may be preset (then no
@@ -191,6 +192,10 @@ class PointSelector:
         self.last_screen = None        # screened precisions: DeviceGP.last_screen of the last acquisition + sigma_abs_tol
         self.fantasy_best = None       # noisy_expected_improvement(): the incumbent of every fantasy [S], in the units of y
         self.sampled_minima = None     # max_value_entropy_search(): the sampled values of the minimum [S], in the units of y
+        self.log_feasibility = None    # the constrained calls: the dense log-probability that every constraint holds
+        self.constrained_base = None   # ... the base term that was used: "ei", "pi", or "none" (no feasible observation: the
+        #                                probability of feasibility alone was maximised) ...
+        self.constrained_incumbent = None   # ... and the incumbent it was measured against, in the units of y (None: no base)
 
     # ------------------------------------------------------------------------------------------
     def _cov_get(self, name):
@@ -806,3 +811,112 @@ class PointSelector:
             self._cached[key] = (model.acq_to_y("mes", acq).reshape(fd), best, model.mean_to_y(minima))
         self.sampled_minima = self._cached[key][2]
         return self._finish(key, "mes")
+
+    # -- constrained acquisitions in log space (csrc/constrained.hip) ------------------------------------------
+    def _cons_refusals(self, what: str):
+        self._not_in_marginal_mode(what)
+        if self._precision != "fp64":
+            raise ValueError(f"{what} needs precision='fp64', got precision={self._precision!r} (the stored sigma of a screened "
+                             "precision is the screen's)")
+        if not self._dense:
+            raise ValueError(f"{what} needs dense_outputs=True (it works on the dense posterior)")
+
+    def _cons_posterior(self) -> tuple:
+        """(mu, sigma) of the last update_surrogate() over this rank's candidates in the units of the MODEL, in the form this
+        class's _cons_scores takes them (here: the device tensors the pass left)."""
+        return self._mu_dev, self._sigma_dev
+
+    def _cons_scores(self, base, f_best, xi, posteriors, upper):
+        """(value over all candidates [M], log-feasibility [M], (best value, flat index, NaN count)), everything in the units of
+        the MODELS: what each class provides to _constrained().  posteriors: _cons_posterior() of every constraint."""
+        gp, lo = self._gp, self._lo_hi[0]
+        mu, sigma = self._cons_posterior()
+        cm = gp.torch.stack([p[0] for p in posteriors]) if posteriors else None
+        cs = gp.torch.stack([p[1] for p in posteriors]) if posteriors else None
+        r = gp.constrained_on_posterior(mu, sigma, cm, cs, upper, base=base, f_best=f_best, xi=xi, idx_offset=lo, dense=True)
+        best = D.allreduce_argmax(r.best_val, r.best_idx, r.nan_count)
+        M = int(np.prod([int(v) for v in self.feature_domain]))
+        val, feas = (t.cpu().numpy() for t in D.gather_concat_tensors([r.value, r.log_feasibility], M))
+        return val, feas, best
+
+    def _constrained(self, what, base, constraints, upper, xi, f_best):
+        """The three constrained calls.  base: "ei", "pi" or "none"; f_best: "feasible" or a number in the units of
+        measured_vals.  Refusals first, then "call update_surrogate() first", then the library."""
+        from .constrained import _finite_number, cons_limits, cons_params, feasible_incumbent, incumbent_rule
+
+        self._cons_refusals(what)
+        constraints = list(constraints)
+        for c in constraints:
+            if type(c) is not type(self):
+                raise ValueError(f"{what}: every constraint must be a {type(self).__name__} (holding that quantity's observations "
+                                 f"as its measured_vals), got {type(c).__name__}")
+            c._cons_refusals(what + " (a constraint)")
+        u = cons_limits(upper, len(constraints))
+        xi = _finite_number("xi", xi)
+        if base != "none":
+            f_best = incumbent_rule(f_best)
+        cons_params(base, 0.0, xi, len(constraints))
+        self._need_update()
+        fd = [int(v) for v in self.feature_domain]
+        Xs = np.ascontiguousarray(self.predicted_pts, dtype=np.float64)
+        for k, c in enumerate(constraints):
+            c._need_update()
+            if ([int(v) for v in c.feature_domain] != fd or getattr(c, "_lo_hi", None) != getattr(self, "_lo_hi", None)
+                    or np.ascontiguousarray(c.predicted_pts, dtype=np.float64).tobytes() != Xs.tobytes()):
+                raise ValueError(f"{what}: constraint {k} was not updated on the same predicted_pts (feature_domain, the shard "
+                                 "and every coordinate, bit for bit)")
+        model = self._model
+        if base == "none":
+            f_best = None
+        elif isinstance(f_best, str):   # "feasible"; with no constraint: min(measured_vals)
+            f_best = feasible_incumbent(self.measured_pts, self.measured_vals, [c.measured_pts for c in constraints],
+                                        [c.measured_vals for c in constraints], u)
+            if f_best is None:
+                base = "none"   # no feasible observation yet: maximise the probability of feasibility (Gelbart's rule)
+        # everything below in the units of the models: each limit in its own constraint's, f_best and xi in the objective's
+        u_m = np.array([float(c._model.to_model(u[k])) for k, c in enumerate(constraints)], dtype=np.float64)
+        kw = model.acq_kw(dict(f_best=f_best, xi=xi))
+        val, feas, best = self._cons_scores(base, kw["f_best"], kw["xi"], [c._cons_posterior() for c in constraints], u_m)
+        kind = {"ei": "log_cei", "pi": "log_pi", "none": "log_pof"}[base]
+        key = ("constrained",)   # never reused: the constraints' posteriors are not part of this object's cache
+        self._cached[key] = (model.acq_to_y(kind, val).reshape(fd), model.best_to_y(kind, best))
+        self.log_feasibility = feas.reshape(fd)
+        self.constrained_base, self.constrained_incumbent = base, f_best
+        return self._finish(key, kind)
+
+    def probability_of_improvement(self, xi=0.0, f_best=None):
+        """Not in the reference (whose docs name it as a wish): probability of improvement for minimisation,
+        Phi(((f_best - mu) - xi) / sigma), evaluated as its LOGARITHM (it does not underflow: log Phi(-40) = -804.6, where Phi
+        itself is 0 in fp64 and every candidate would tie).  f_best: a number in the units of measured_vals, default
+        min(measured_vals).  Returns the multi-index as expected_improvement() does; acq_func_eval holds log PI (unit-free).  A
+        function of the posterior update_surrogate() has left on the device: every kernel= and every model record.
+        ard="marginal", a screened precision= and dense_outputs=False raise ValueError; IndexError when a value is NaN."""
+        from .constrained import _finite_number
+
+        self._cons_refusals("probability_of_improvement()")
+        # (no constraint: the feasible incumbent of _constrained IS min(measured_vals))
+        f_best = "feasible" if f_best is None else _finite_number("f_best", f_best)
+        return self._constrained("probability_of_improvement()", "pi", [], [], xi, f_best)
+
+    def constrained_expected_improvement(self, constraints, upper, xi=0.0, f_best="feasible"):
+        """Not in the reference: constrained expected improvement (Gardner et al. 2014; Gelbart, Snoek & Adams 2014) for
+        minimisation under black-box constraints g_c(x) <= upper[c] - EI times the probability that every constraint holds,
+        evaluated as log EI + sum_c log Phi((upper_c - mu_c) / sigma_c): the plain product is exactly 0 a few dozen standard
+        deviations inside the infeasible region, where every candidate would tie.  constraints: selector objects of this
+        class, one per constraint, each holding that quantity's observations as its measured_vals - with a kernel=, ard= and
+        model of its own - whose update_surrogate() has run on the same predicted_pts.  upper: one limit per constraint, in
+        the units of that selector's measured_vals (a two-sided band: two constraints, g <= u and -g <= -l).  f_best:
+        "feasible" (the smallest of measured_vals among the observations at which every constraint's observation is within
+        its limit: all selectors must hold the same measured_pts; if no observation is feasible the call maximises the
+        probability of feasibility alone and constrained_base says "none") or a number in the units of measured_vals.
+        Returns the multi-index as expected_improvement() does; acq_func_eval holds the LOG values (log of the units of
+        measured_vals; -inf is a legal value), log_feasibility the dense log-probability of feasibility, constrained_base the
+        base that was used and constrained_incumbent f_best.  ard="marginal", a screened precision= and dense_outputs=False
+        raise ValueError, for this object and for every constraint; IndexError when a value is NaN."""
+        return self._constrained("constrained_expected_improvement()", "ei", constraints, upper, xi, f_best)
+
+    def probability_of_feasibility(self, constraints, upper):
+        """Not in the reference: the point at which all constraints are most likely to hold, by
+        sum_c log Phi((upper_c - mu_c) / sigma_c) (acq_func_eval and log_feasibility; unit-free).  constraints, upper and the
+        refusals: as constrained_expected_improvement().  This object's own posterior is not read."""
+        return self._constrained("probability_of_feasibility()", "none", constraints, upper, 0.0, None)

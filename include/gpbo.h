@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_mes_log_survival_f64 / gpbo_mes_acq_f64 / gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64, max-value entropy search on the dense posterior; gpbo_nei_fantasies_workspace_bytes / gpbo_nei_fantasies_f64 / gpbo_posterior_nei_workspace_bytes / gpbo_posterior_nei_kern_f64 / gpbo_nei_host_f64, noisy expected improvement; gpbo_kxx_kern_f64 / gpbo_kstar_mu_kern_f64 / gpbo_factorise_kern_f64 / gpbo_posterior_acq_kern_f64 / gpbo_nlml_grad_kern_f64 / gpbo_nlml_hyper_kern_f64 / gpbo_select_next_host_kern_f64 / gpbo_nlml_grad_host_kern_f64 / gpbo_nlml_hyper_host_kern_f64, the Matern 3/2 and 5/2 covariance families on the fp64 path; gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_constrained_acq_f64 / gpbo_constrained_acq_host_f64, constrained expected improvement, probability of improvement and probability of feasibility in log space; gpbo_mes_log_survival_f64 / gpbo_mes_acq_f64 / gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64, max-value entropy search on the dense posterior; gpbo_nei_fantasies_workspace_bytes / gpbo_nei_fantasies_f64 / gpbo_posterior_nei_workspace_bytes / gpbo_posterior_nei_kern_f64 / gpbo_nei_host_f64, noisy expected improvement; gpbo_kxx_kern_f64 / gpbo_kstar_mu_kern_f64 / gpbo_factorise_kern_f64 / gpbo_posterior_acq_kern_f64 / gpbo_nlml_grad_kern_f64 / gpbo_nlml_hyper_kern_f64 / gpbo_select_next_host_kern_f64 / gpbo_nlml_grad_host_kern_f64 / gpbo_nlml_hyper_host_kern_f64, the Matern 3/2 and 5/2 covariance families on the fp64 path; gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -764,6 +764,54 @@ int gpbo_mes_log_survival_host_f64(const double *mu_host, const double *sigma_ho
                                    double *out_host, int64_t *nan_out_host);
 int gpbo_mes_acq_host_f64(const double *mu_host, const double *sigma_host, int64_t M, const double *ystar_host, int32_t S,
                           double *acq_out_host, gpbo_result *result_host);
+
+/* ---- Constrained expected improvement, probability of improvement and probability of feasibility on the dense posterior, in
+ * LOG space (csrc/constrained.hip; Gardner et al. 2014, Gelbart, Snoek & Adams 2014; not in the reference).  For
+ * minimisation.  A candidate has the objective's posterior (mu, sigma) and C >= 0 constraint posteriors (mu_c, sigma_c), each
+ * from a GP of its own, with upper limits u_c: feasible means g_c(x) <= u_c for every c, the constraints taken as independent.
+ *     feas(x)  = sum_{c < C} log Phi((u_c - mu_c) / sigma_c)        (added in index order, c = 0 first, starting from 0)
+ *     value(x) = base(x) + feas(x)
+ *     base = 0                                                      GPBO_CONS_BASE_NONE: the probability of feasibility alone
+ *          = log sigma + log h(z),  h(z) = phi(z) + z Phi(z)        GPBO_CONS_BASE_EI:   log of constrained expected improvement
+ *          = log Phi(z)                                             GPBO_CONS_BASE_PI:   log of constrained probability of improvement
+ *     z = ((f_best - mu) - xi) / sigma
+ *   Every standardised argument is formed as written: subtractions, then ONE division.  The plain product of CDFs is exactly 0
+ *   once the candidates are a few dozen standard deviations inside the infeasible region, and plain EI below z ~ -38.5; the
+ *   logarithms keep the order.  log Phi as for max-value entropy search above; log h in three branches (csrc/cons_math.h),
+ *   t = -z / sqrt 2, u = 1 / (2 t^2):
+ *     z >= -1           log(phi(z) + z Phi(z))
+ *     -1e3 < z < -1     -t^2 - log(2 pi) / 2 + log1p(-sqrt(pi) t erfcx(t))
+ *     z <= -1e3         -t^2 - log(2 pi) / 2 + log(u (1 - 3 u (1 - 5 u)))
+ *   against 60-digit values the error stays within a few units of eps (max(1, z^2 / 2 for z < 0) + |log h|).
+ * mu, sigma [M]: read only with a base (may be null with GPBO_CONS_BASE_NONE).  cons_mu, cons_sigma: [C x ldc], row c the
+ *   posterior of constraint c over the M candidates, ldc >= M (may be null with C == 0).  upper_host [C]: the limits, by value,
+ *   in the units of cons_mu.  All of (mu, sigma, f_best, xi) in ONE unit, any unit.
+ * val_out, feas_out: optional dense [M], value and feas; the result does not depend on their presence.  result: as every other
+ *   acquisition (best_idx = idx_offset + the LOWEST candidate attaining the maximum).
+ * Edge rules: a NaN in any value of a candidate the call reads makes its value NaN; it counts once in nan_count and is never
+ *   chosen.  sigma_c == 0: the term is 0 where mu_c <= u_c and -inf otherwise.  sigma == 0, imp = (f_best - mu) - xi: EI gives
+ *   log(max(imp, 0)), PI gives 0 where imp > 0 and -inf otherwise.  -inf is a legal value: when every candidate is -inf the lowest
+ *   index is returned with best_val = -inf and nan_count untouched.  (sigma is a standard deviation: >= 0.)
+ * No sum crosses candidates, the grid depends on M alone, only the integer NaN counter is atomic: two calls give the same bits.
+ * 1 <= M <= 2^40, base one of the three, 0 <= C <= GPBO_CONS_MAX_C and C >= 1 without a base, ldc >= M, every limit finite,
+ *   f_best and xi finite when there is a base, no null pointer but those named above (GPBO_ERR_ARG otherwise);  work:
+ *   GPBO_CONS_WORK_BYTES bytes - a constant: the arg-max records of 1024 workgroups and the counter - 256-byte aligned
+ *   (GPBO_ERR_WORKSPACE otherwise);  all of it before any HIP call.  The call only enqueues.
+ * gpbo_constrained_acq_host_f64: the same on host arrays (conventions of the other *_host entries: device buffers are allocated,
+ *   filled, used and released inside the call, on a stream of its own; synchronous; idx_offset = 0). */
+#define GPBO_CONS_BASE_NONE 0
+#define GPBO_CONS_BASE_EI 1
+#define GPBO_CONS_BASE_PI 2
+#define GPBO_CONS_MAX_C 8
+#define GPBO_CONS_WORK_BYTES 16640
+int gpbo_constrained_acq_f64(const double *mu, const double *sigma, int64_t M, int32_t base, double f_best, double xi,
+                             const double *cons_mu, const double *cons_sigma, int64_t ldc, int32_t C, const double *upper_host,
+                             int64_t idx_offset, double *val_out /* optional [M] */, double *feas_out /* optional [M] */,
+                             gpbo_result *result, void *work, int64_t work_bytes, void *stream);
+int gpbo_constrained_acq_host_f64(const double *mu_host, const double *sigma_host, int64_t M, int32_t base, double f_best,
+                                  double xi, const double *cons_mu_host, const double *cons_sigma_host, int64_t ldc, int32_t C,
+                                  const double *upper_host, double *val_out_host, double *feas_out_host,
+                                  gpbo_result *result_host);
 
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;

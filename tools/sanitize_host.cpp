@@ -239,6 +239,26 @@ int main() {
         EXPECT(gpbo_mes_acq_host_f64(pd, pd, 0, lv, 16, nullptr, &res_m) == GPBO_ERR_ARG);
         EXPECT(gpbo_mes_acq_host_f64(pd, pd, 10, bad, 3, nullptr, &res_m) == GPBO_ERR_ARG);
     }
+    // the constrained acquisitions (tests/test_constrained_abi_cpu.py): the ranges of M, base, C and ldc, the limits read on the
+    // host (only the first C of them), f_best / xi only with a base, the constant workspace one byte short or misaligned
+    {
+        gpbo_result res_c;
+        double up[8] = {0.0, 0.5, -0.5, 1.0, 2.0, -2.0, 0.25, 0.75}, bad[3] = {0.0, 1.0, __builtin_nan("")};
+        const double nan = __builtin_nan("");
+        auto cons = [&](int64_t M, int32_t base, double fb, int64_t ldc, int32_t Cn, const double *u, void *w, int64_t wbytes) {
+            return gpbo_constrained_acq_f64(pd, pd, M, base, fb, 0.0, pd, pd, ldc, Cn, u, 0, nullptr, nullptr, &res_c, w, wbytes, nullptr);
+        };
+        const int64_t wc = GPBO_CONS_WORK_BYTES;
+        EXPECT(cons(0, GPBO_CONS_BASE_EI, 0.0, 10, 3, up, p, wc) == GPBO_ERR_ARG && cons(((int64_t)1 << 40) + 1, GPBO_CONS_BASE_EI, 0.0, (int64_t)1 << 41, 3, up, p, wc) == GPBO_ERR_ARG);
+        EXPECT(cons(1000, 3, 0.0, 1000, 3, up, p, wc) == GPBO_ERR_ARG && cons(1000, GPBO_CONS_BASE_NONE, 0.0, 1000, 0, up, p, wc) == GPBO_ERR_ARG);
+        EXPECT(cons(1000, GPBO_CONS_BASE_PI, 0.0, 1000, 9, up, p, wc) == GPBO_ERR_ARG && cons(1000, GPBO_CONS_BASE_PI, 0.0, 999, 3, up, p, wc) == GPBO_ERR_ARG);
+        EXPECT(cons(1000, GPBO_CONS_BASE_EI, 0.0, 1000, 3, bad, p, wc) == GPBO_ERR_ARG && cons(1000, GPBO_CONS_BASE_EI, 0.0, 1000, 2, bad, p, wc - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(cons(1000, GPBO_CONS_BASE_EI, nan, 1000, 3, up, p, wc) == GPBO_ERR_ARG && cons(1000, GPBO_CONS_BASE_NONE, nan, 1000, 3, up, p, wc - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(cons(1000, GPBO_CONS_BASE_EI, 0.0, 1037, 8, up, static_cast<char *>(p) + 8, wc) == GPBO_ERR_WORKSPACE);
+        EXPECT(cons(1000, GPBO_CONS_BASE_EI, 0.0, 1000, 0, nullptr, p, wc - 1) == GPBO_ERR_WORKSPACE && cons(1000, GPBO_CONS_BASE_EI, 0.0, 1000, 1, nullptr, p, wc) == GPBO_ERR_ARG);
+        EXPECT(gpbo_constrained_acq_host_f64(pd, pd, 10, GPBO_CONS_BASE_EI, 0.0, 0.0, pd, pd, 10, 3, bad, nullptr, nullptr, &res_c) == GPBO_ERR_ARG);
+        EXPECT(gpbo_constrained_acq_host_f64(pd, pd, 10, GPBO_CONS_BASE_NONE, 0.0, 0.0, nullptr, nullptr, 10, 0, nullptr, nullptr, nullptr, &res_c) == GPBO_ERR_ARG);
+    }
     // the likelihood of many hyperparameter cells and the ensemble pass (tests/test_marginal_abi_cpu.py): the size limits, the
     // model table read on the host (weights, scales, every model's length scales), the workspace one byte short
     {
