@@ -41,6 +41,8 @@ CONS_BASE_NONE, CONS_BASE_EI, CONS_BASE_PI = 0, 1, 2   # gpbo_constrained_acq_f6
 CONS_BASE_IDS = {"none": CONS_BASE_NONE, "ei": CONS_BASE_EI, "pi": CONS_BASE_PI}
 CONS_MAX_C = 8             # ... constraints per call
 CONS_WORK_BYTES = 16640    # ... its workspace: a constant
+EHVI_MAX_P = 128           # gpbo_ehvi_acq_f64: front points per call (GPBO_EHVI_MAX_P)
+EHVI_WORK_BYTES = 16640    # ... its workspace: a constant
 # covariance families of the gpbo_*_kern_f64 entry points (include/gpbo.h: GPBO_KERNEL_*)
 KERNEL_IDS = {"se": 0, "matern32": 1, "matern52": 2}
 
@@ -216,6 +218,8 @@ SIGNATURES = {
     "gpbo_mes_acq_host_f64": (C.c_int, [_p, _p, _i64, _p, _i32, _p, _p]),
     "gpbo_constrained_acq_f64": (C.c_int, [_p, _p, _i64, _i32, _f64, _f64, _p, _p, _i64, _i32, _p, _i64, _p, _p, _p, _p, _i64, _p]),
     "gpbo_constrained_acq_host_f64": (C.c_int, [_p, _p, _i64, _i32, _f64, _f64, _p, _p, _i64, _i32, _p, _p, _p, _p]),
+    "gpbo_ehvi_acq_f64": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _f64, _f64, _i64, _p, _p, _p, _i64, _p]),
+    "gpbo_ehvi_acq_host_f64": (C.c_int, [_p, _p, _p, _p, _i64, _p, _i32, _f64, _f64, _p, _p]),
     "gpbo_gemm_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,
                                 _i32, _i32, _p]),
     "gpbo_gemm_tri_f64": (C.c_int, [_i32, _i64, _i64, _i64, _f64, _p, _i64, _i64, _p, _i64, _i64, _f64, _p, _i64, _i64,

@@ -12,6 +12,7 @@
 //   gpbo_nei_host_f64              = the factorisation and its noise-free twin, then noisy expected improvement (nei.hip)
 //   gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64 = max-value entropy search on a dense posterior the caller holds (mes.hip)
 //   gpbo_constrained_acq_host_f64  = constrained EI / PI / probability of feasibility on dense posteriors the caller holds (constrained.hip)
+//   gpbo_ehvi_acq_host_f64         = two-objective expected hypervolume improvement on dense posteriors the caller holds (ehvi.hip)
 //   gpbo_refine_host_f64           = the factorisation, then gradient refinement of given starts off the grid (refine.hip)
 //   gpbo_nlml_grid_host_f64        = tune_kernel()'s likelihood grid (float32, the reference's det underflow)
 //   gpbo_nlml_grid_logdet_host_f64 = the same grid in fp64 with log det from the factor
@@ -474,6 +475,33 @@ extern "C" int gpbo_constrained_acq_host_f64(const double *mu, const double *sig
     okc = A.d2h(result, dres, sizeof(gpbo_result));
     if (val_out) okc = okc && A.d2h(val_out, dval, sizeof(double) * M);
     if (feas_out) okc = okc && A.d2h(feas_out, dfeas, sizeof(double) * M);
+    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+}
+
+// Two-objective expected hypervolume improvement on host arrays (csrc/ehvi.hip): no factorisation - the call works on the two
+// dense posteriors the caller already holds.  The refusals are the device entry's own (ehvi_args_ok, host_driver.h), made before
+// the arena exists.
+extern "C" int gpbo_ehvi_acq_host_f64(const double *mu1, const double *sigma1, const double *mu2, const double *sigma2, int64_t M,
+                                      const double *front, int32_t P, double ref1, double ref2, double *val_out,
+                                      gpbo_result *result) {
+    if (!ehvi_args_ok(mu1, sigma1, mu2, sigma2, M, front, P, ref1, ref2) || !result) return GPBO_ERR_ARG;
+    DeviceArena A;
+    if (!A.ok) return GPBO_ERR_LAUNCH;
+    const double *src[4] = {mu1, sigma1, mu2, sigma2};
+    double *dev[4];
+    for (double *&p : dev) p = A.alloc<double>(M);
+    double *dval = val_out ? A.alloc<double>(M) : nullptr;
+    gpbo_result *dres = A.alloc<gpbo_result>(1);
+    char *dwork = A.alloc<char>(GPBO_EHVI_WORK_BYTES);   // (hipMalloc: 256-byte aligned)
+    if (!A.ok) return GPBO_ERR_WORKSPACE;
+    bool okc = true;
+    for (int k = 0; k < 4 && okc; ++k) okc = A.h2d(dev[k], src[k], sizeof(double) * M);
+    if (!okc) return GPBO_ERR_LAUNCH;
+    const int rc = gpbo_ehvi_acq_f64(dev[0], dev[1], dev[2], dev[3], M, front, P, ref1, ref2, 0, dval, dres, dwork,
+                                     GPBO_EHVI_WORK_BYTES, A.st());
+    if (rc != GPBO_OK) return rc;
+    okc = A.d2h(result, dres, sizeof(gpbo_result));
+    if (val_out) okc = okc && A.d2h(val_out, dval, sizeof(double) * M);
     return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 

@@ -83,6 +83,22 @@ inline bool cons_args_ok(const double *mu, const double *sigma, int64_t M, int32
     return true;
 }
 
+// two-objective expected hypervolume improvement (ehvi.hip and its host entry in host_api.hip): 1 <= M <= 2^40 candidates, a
+// finite reference point, 0 <= P <= GPBO_EHVI_MAX_P front points (a_i, c_i) in rows of front_host [P x 2] - every value finite,
+// a strictly ascending, c strictly descending, every point strictly below the reference point; front_host may be null only with
+// P == 0
+inline bool ehvi_args_ok(const double *mu1, const double *sigma1, const double *mu2, const double *sigma2, int64_t M,
+                         const double *front_host, int32_t P, double ref1, double ref2) {
+    if (M < 1 || M > ((int64_t)1 << 40) || P < 0 || P > GPBO_EHVI_MAX_P || !mu1 || !sigma1 || !mu2 || !sigma2) return false;
+    if (!(ref1 - ref1 == 0.0) || !(ref2 - ref2 == 0.0) || (P > 0 && !front_host)) return false;
+    for (int32_t i = 0; i < P; ++i) {
+        const double a = front_host[2 * i], c = front_host[2 * i + 1];
+        if (!(a - a == 0.0) || !(c - c == 0.0) || !(a < ref1) || !(c < ref2)) return false;
+        if (i > 0 && (!(front_host[2 * i - 2] < a) || !(front_host[2 * i - 1] > c))) return false;
+    }
+    return true;
+}
+
 // ---- the length scales as the kernels take them: il2[k] = 1 / ls_k^2 (cov_r2, cov_entry.h), isc[k] = 1 / (ls_k sqrt 2)
 // (the scoring form of cov_entry.h), k < d; either may be null.  EXACTLY these expressions: the values feed kernels whose
 // outputs are compared bit for bit.  The entries k >= d are the caller's.  false: a length scale that is not positive.

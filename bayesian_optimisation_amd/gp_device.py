@@ -185,6 +185,17 @@ class ConstrainedResult:
     f_best: Optional[float] = None                # the incumbent the base was measured against (None without a base)
 
 
+@dataclass
+class EhviResult:
+    """What DeviceGP.ehvi_on_posterior / select_ehvi return.  Every value is a LOGARITHM (-inf is a legal value)."""
+    best_val: float
+    best_idx: int
+    nan_count: int
+    value: Optional[object] = None                # dense=True: torch fp64 device tensor [M], log EHVI
+    front: Optional[np.ndarray] = None            # the front [P x 2] and the reference point (r1, r2) that were used
+    ref: Optional[tuple] = None
+
+
 def refine_params(P: int, d: int, iters: int, step0: float) -> tuple:
     """(iters, step0) as the C ABI takes them; refuses what gpbo_refine_f64 refuses (include/gpbo.h)."""
     if not 1 <= int(P) <= _lib.REFINE_MAX_P:
@@ -363,7 +374,7 @@ class DeviceGP(DeviceSide, LikelihoodFits):
         # workspaces, kept from call to call and only ever grown (_workspace)
         self._work_post = self._work_fact = self._work_order = self._work_screen = self._work_rescore = None
         self._work_qei = self._work_ard = self._work_batch = self._work_refine = self._work_thompson = self._work_loo = None
-        self._work_nei = self._work_mes = self._work_cons = None
+        self._work_nei = self._work_mes = self._work_cons = self._work_ehvi = None
         self._epoch = 0              # counts factorise() / append() / load_state_dict(): ThompsonPaths belong to one of them
         self._order_flag = None      # device int32: factorise(order="fps") fell back to the arrival order
         self.U32, self.Np32, self._u32_valid = None, 0, False   # prepare_f32()
@@ -1349,6 +1360,63 @@ class DeviceGP(DeviceSide, LikelihoodFits):
         cs = self.torch.stack([p[1] for p in post]) if post else None
         return self.constrained_on_posterior(mu, sigma, cm, cs, u, base=base, f_best=f_best, xi=xi, idx_offset=idx_offset,
                                              dense=dense)
+
+    # -- two-objective expected hypervolume improvement in log space (csrc/ehvi.hip) --------------------
+    def ehvi_on_posterior(self, mu1, sigma1, mu2, sigma2, front, ref, idx_offset: int = 0, dense: bool = True) -> EhviResult:
+        """log EHVI(x) of two minimised, independent objectives over their dense posteriors and its first arg-max
+        (gpbo_ehvi_acq_f64; the formula and edge rules are stated in include/gpbo.h).  mu1, sigma1, mu2, sigma2 [M]; front
+        [P x 2]: rows (objective 1, objective 2), strictly ascending in the first and strictly descending in the second
+        (pareto.pareto_front returns that form; None or empty: no front); ref: two finite numbers above every front point.  All in
+        the units of the posteriors.  Works without a factorisation.  One read-back (synchronises)."""
+        from .pareto import check_front
+
+        torch = self.torch
+        F, r = check_front(front, ref)
+        m1, s1, M = self._posterior_pair(mu1, sigma1)
+        m2, s2, M2 = self._posterior_pair(mu2, sigma2)
+        if M2 != M:
+            raise ValueError("the two objectives' posteriors must hold one value per candidate each")
+        with torch.cuda.device(self.device):
+            work = self._workspace("_work_ehvi", _lib.EHVI_WORK_BYTES)
+            val = torch.empty(M, dtype=torch.float64, device=self.device) if dense else None
+            _lib.call(self.lib.gpbo_ehvi_acq_f64, m1, s1, m2, s2, M, F, int(F.shape[0]), r[0], r[1], int(idx_offset), val,
+                      self._result, work, _lib.EHVI_WORK_BYTES, self._stream())
+            v, i, n = self.read_result(self._result)   # synchronises: the converted inputs have been consumed
+        return EhviResult(v, i, n, val, F, r)
+
+    def select_ehvi(self, Xs, other, front=None, ref="nadir", dense: bool = False, idx_offset: int = 0) -> EhviResult:
+        """The next point by expected hypervolume improvement of two minimised objectives: this surrogate (objective 1) and
+        `other` (objective 2) - each factorised on ITS objective's observations, with any kernel family and model of its own -
+        score the rows of Xs with the unchanged fp64 pass, then ehvi_on_posterior() combines them.  front: [P x 2] in the units
+        of the observations, or None for the Pareto front of the two surrogates' own observations (they must hold the same
+        points, bit for bit: observation i of each is one evaluation).  ref: two numbers, or "nadir" (pareto.reference_point
+        over those observations).  Every pass uses its own factorisation's prior variance ((1 + jitter1) + jitter2).  ValueError
+        on bad parameters, on an `other` that is no DeviceGP or lives on another device, before any GPU work; GpboError for a
+        surrogate that is not factorised."""
+        from .pareto import check_front, observed_pairs, pareto_front, reference_point
+
+        if not isinstance(other, DeviceGP) or other.device != self.device:
+            raise ValueError(f"select_ehvi(): other must be a DeviceGP on {self.device}")
+        if not (isinstance(ref, str) and ref == "nadir"):
+            ref = reference_point(None, ref)
+        if front is not None and isinstance(ref, tuple):
+            check_front(front, ref)
+        for g in (self, other):
+            if g.N < 1:
+                raise _lib.GpboError("select_ehvi() needs a factorised surrogate for both objectives")
+        if front is None or isinstance(ref, str):
+            Y = observed_pairs(*self.observations_host(), *other.observations_host())
+            ref = reference_point(Y, ref)
+            if front is None:
+                front = pareto_front(Y, ref)
+        F, r = check_front(front, ref)
+        Xsd, M = self._candidates(Xs)
+        post = []
+        for g in (self, other):
+            pv = (1.0 + g.jitter1) + g.jitter2
+            s = g.score(g._candidates(Xsd)[0], acquisition="lcb", explore=0.0, dense=True, prior_var=pv)
+            post.append((s.mu, s.sigma))
+        return self.ehvi_on_posterior(post[0][0], post[0][1], post[1][0], post[1][1], F, r, idx_offset=idx_offset, dense=dense)
 
     # -- acquisition gradients and off-grid refinement (csrc/refine.hip, DESIGN 4d) -------------------------------
     def _points(self, Xq, what: str):

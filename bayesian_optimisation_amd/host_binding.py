@@ -283,6 +283,26 @@ def constrained_acq(mu, sigma, cons_mu, cons_sigma, upper, base: str = "ei", f_b
     return dict(best_val=r["best_val"], best_idx=r["best_idx"], nan_count=r["nan_count"], value=val, log_feasibility=feas)
 
 
+def ehvi_acq(mu1, sigma1, mu2, sigma2, front, ref, dense: bool = True, lib=None) -> dict:
+    """Two-objective expected hypervolume improvement on host arrays (gpbo_ehvi_acq_host_f64): log EHVI over the dense posteriors
+    of two minimised objectives and its first arg-max.  front [P x 2], ref (r1, r2): as DeviceGP.ehvi_on_posterior.  Returns
+    dict(best_val, best_idx, nan_count, value [M])."""
+    from .pareto import check_front
+
+    F, r = check_front(front, ref)
+    mu1, sigma1, M = _posterior_pair(mu1, sigma1)
+    mu2, sigma2, M2 = _posterior_pair(mu2, sigma2)
+    if M2 != M:
+        raise ValueError("the two objectives' posteriors must hold one value per candidate each")
+    lib = lib or _lib.load()
+    val = np.empty(M) if dense else None
+    out = _Result()
+    _lib.note_hip_use()
+    _lib.call(lib.gpbo_ehvi_acq_host_f64, mu1, sigma1, mu2, sigma2, M, F, int(F.shape[0]), r[0], r[1], val, out.res)
+    res = out.decode()
+    return dict(best_val=res["best_val"], best_idx=res["best_idx"], nan_count=res["nan_count"], value=val)
+
+
 def refine(X, y, ls, starts, lower, upper, acquisition: str = "lcb", explore: float = 4.0, f_best=None, xi: float = 0.0,
            iters: int = 30, step0: float = 0.1, lib=None) -> dict:
     """Off-grid refinement on host arrays (gpbo_refine_host_f64: factorisation and refinement in one call).  Returns
@@ -479,6 +499,12 @@ class PointSelectorHost(PointSelector):
         cs = np.stack([p[1] for p in posteriors]) if posteriors else None
         r = constrained_acq(mu, sigma, cm, cs, upper, base=base, f_best=f_best, xi=xi, lib=self.lib)
         return r["value"], r["log_feasibility"], (r["best_val"], r["best_idx"], r["nan_count"])
+
+    def _ehvi_scores(self, posterior2, front, ref):
+        """PointSelector._ehvi_scores on the host-pointer route (gpbo_ehvi_acq_host_f64): the same values."""
+        mu1, sigma1 = self._cons_posterior()
+        r = ehvi_acq(mu1, sigma1, posterior2[0], posterior2[1], front, ref, lib=self.lib)
+        return r["value"], (r["best_val"], r["best_idx"], r["nan_count"])
 
     def refine_next(self, n_starts=64, iters=30, acquisition="lcb", explore=4, xi=0.0):
         """PointSelector.refine_next on the host-pointer route (gpbo_refine_host_f64): the same d coordinates, the same

@@ -74,10 +74,11 @@ class SurrogateModel:
         """LCB = s acq - m (explore s sigma - (m + s mu)), EI / qEI = s acq.  Both maps increase, so the arg-max and its
         tie rule are those of the kernels.  "mes" (max-value entropy search) has no unit: an entropy of a ratio.  The
         constrained acquisitions are LOGARITHMS: "log_cei" = log EI_model + log s (a probability of feasibility has no unit),
-        "log_pi" and "log_pof" are logarithms of probabilities and have none."""
+        "log_pi" and "log_pof" are logarithms of probabilities and have none; "log_ehvi" is the logarithm of an AREA, the product
+        of two objectives' units: each objective's model adds its own log s (the caller applies both)."""
         if not self.fitted or kind in ("mes", "log_pi", "log_pof"):
             return acq
-        if kind == "log_cei":
+        if kind in ("log_cei", "log_ehvi"):
             return acq + float(np.log(self.y_scale))
         return self.y_scale * acq - self.y_mean if kind == "lcb" else self.y_scale * acq
 

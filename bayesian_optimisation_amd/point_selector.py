@@ -28,6 +28,7 @@ Differences from the reference, all deliberate:
     `max_value_entropy_search()` (the information gained about the minimum's value: no incumbent, no trade-off parameter;
     INTEGRATION.md 10), `constrained_expected_improvement()` / `probability_of_feasibility()` (black-box constraints, each a
     selector object of its own; evaluated in log space) and `probability_of_improvement()`,
+    `expected_hypervolume_improvement()` (two objectives, the second a selector object of its own),
     `q_expected_improvement()`, `select_thompson(q)` (q points as the minimisers of posterior sample paths), `select_batch(q)` (q points for parallel evaluation: greedy Kriging believer / GP-BUCB /
     constant liar), `refine_next()` (the next point off the grid: the best candidates polished by acquisition gradients), `dense_outputs=False` (next point only: the dense attributes stay None and the acquisition
     calls go through the exact prefix bound), `kernel_params` may be preset (then no
@@ -196,6 +197,9 @@ class PointSelector:
         self.constrained_base = None   # ... the base term that was used: "ei", "pi", or "none" (no feasible observation: the
         #                                probability of feasibility alone was maximised) ...
         self.constrained_incumbent = None   # ... and the incumbent it was measured against, in the units of y (None: no base)
+        self.pareto_front = None       # expected_hypervolume_improvement(): the front [P x 2] that was used, in the units of y ...
+        self.reference_point = None    # ... the reference point (r1, r2) ...
+        self.hypervolume = None        # ... and the area below it that the front dominates
 
     # ------------------------------------------------------------------------------------------
     def _cov_get(self, name):
@@ -920,3 +924,73 @@ class PointSelector:
         sum_c log Phi((upper_c - mu_c) / sigma_c) (acq_func_eval and log_feasibility; unit-free).  constraints, upper and the
         refusals: as constrained_expected_improvement().  This object's own posterior is not read."""
         return self._constrained("probability_of_feasibility()", "none", constraints, upper, 0.0, None)
+
+    # -- two-objective expected hypervolume improvement in log space (csrc/ehvi.hip, DESIGN 4p) ---------------------------
+    def _ehvi_scores(self, posterior2, front, ref):
+        """(log EHVI over all candidates [M], (best value, flat index, NaN count)), everything in the units of the MODELS: what
+        each class provides to expected_hypervolume_improvement().  posterior2: _cons_posterior() of the second objective."""
+        gp, lo = self._gp, self._lo_hi[0]
+        mu1, sigma1 = self._cons_posterior()
+        r = gp.ehvi_on_posterior(mu1, sigma1, posterior2[0], posterior2[1], front, ref, idx_offset=lo, dense=True)
+        best = D.allreduce_argmax(r.best_val, r.best_idx, r.nan_count)
+        M = int(np.prod([int(v) for v in self.feature_domain]))
+        (val,) = (t.cpu().numpy() for t in D.gather_concat_tensors([r.value], M))
+        return val, best
+
+    def expected_hypervolume_improvement(self, other, ref="nadir", front="observed"):
+        """Not in the reference: expected hypervolume improvement (Emmerich et al. 2006, 2016) for TWO minimised objectives - the
+        expected growth of the area below the reference point that the Pareto front dominates - evaluated as its LOGARITHM: the
+        plain value is exactly 0 wherever both objectives are a few dozen standard deviations from improving, where every
+        candidate would tie.  This object holds objective 1's observations as its measured_vals; other: a selector object of
+        this class holding objective 2's - with a kernel=, ard= and model of its own - whose update_surrogate() has run on the
+        same predicted_pts.  The objectives are taken as independent.  ref: two numbers in the units of the two measured_vals,
+        or "nadir": per objective the worst observation plus 10 % of the observed range (ValueError when a range is zero: pass
+        numbers).  front: "observed" (the Pareto front of the observed pairs below ref: both selectors must hold the same
+        measured_pts, bit for bit) or a [P x 2] array in the form pareto.pareto_front() returns, at most 128 points.
+        Returns the multi-index as expected_improvement() does; acq_func_eval holds log EHVI (log of the product of the two
+        units; -inf is a legal value), pareto_front, reference_point and hypervolume what was used, in the units of y.
+        ard="marginal", a screened precision= and dense_outputs=False raise ValueError, for this object and for other;
+        IndexError when a value is NaN.  To add black-box constraints, add log_feasibility of a constrained call to
+        acq_func_eval."""
+        from .pareto import check_front, hypervolume, observed_pairs, pareto_front, reference_point
+
+        what = "expected_hypervolume_improvement()"
+        self._cons_refusals(what)
+        if type(other) is not type(self):
+            raise ValueError(f"{what}: the second objective must be a {type(self).__name__} (holding its observations as its "
+                             f"measured_vals), got {type(other).__name__}")
+        other._cons_refusals(what + " (the second objective)")
+        nadir = isinstance(ref, str) and ref == "nadir"
+        if not nadir:
+            ref = reference_point(None, ref)
+        observed = isinstance(front, str)
+        if observed and front != "observed":
+            raise ValueError(f"front must be 'observed' or a [P x 2] array, got {front!r}")
+        if not observed and not nadir:
+            check_front(front, ref)
+        self._need_update()
+        other._need_update()
+        fd = [int(v) for v in self.feature_domain]
+        Xs = np.ascontiguousarray(self.predicted_pts, dtype=np.float64)
+        if ([int(v) for v in other.feature_domain] != fd or getattr(other, "_lo_hi", None) != getattr(self, "_lo_hi", None)
+                or np.ascontiguousarray(other.predicted_pts, dtype=np.float64).tobytes() != Xs.tobytes()):
+            raise ValueError(f"{what}: the second objective was not updated on the same predicted_pts (feature_domain, the shard "
+                             "and every coordinate, bit for bit)")
+        if observed or nadir:
+            Y = observed_pairs(self.measured_pts, self.measured_vals, other.measured_pts, other.measured_vals)
+            ref = reference_point(Y, ref)
+        F, r = check_front(pareto_front(Y, ref) if observed else front, ref)
+        # everything below in the units of the models: each coordinate in its own objective's
+        m1, m2 = self._model, other._model
+        F_m = np.stack([np.asarray(m1.to_model(F[:, 0]), dtype=np.float64), np.asarray(m2.to_model(F[:, 1]), dtype=np.float64)],
+                       axis=1)
+        r_m = (float(m1.to_model(r[0])), float(m2.to_model(r[1])))
+        val, best = self._ehvi_scores(other._cons_posterior(), F_m, r_m)
+
+        def to_y(v):   # log of an area: + log y_scale of each objective
+            return m2.acq_to_y("log_ehvi", m1.acq_to_y("log_ehvi", v))
+
+        key = ("ehvi",)   # never reused: the second objective's posterior is not part of this object's cache
+        self._cached[key] = (to_y(val).reshape(fd), (float(to_y(best[0])),) + tuple(best[1:]))
+        self.pareto_front, self.reference_point, self.hypervolume = F, r, hypervolume(F, r)
+        return self._finish(key, "log_ehvi")

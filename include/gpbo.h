@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_constrained_acq_f64 / gpbo_constrained_acq_host_f64, constrained expected improvement, probability of improvement and probability of feasibility in log space; gpbo_mes_log_survival_f64 / gpbo_mes_acq_f64 / gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64, max-value entropy search on the dense posterior; gpbo_nei_fantasies_workspace_bytes / gpbo_nei_fantasies_f64 / gpbo_posterior_nei_workspace_bytes / gpbo_posterior_nei_kern_f64 / gpbo_nei_host_f64, noisy expected improvement; gpbo_kxx_kern_f64 / gpbo_kstar_mu_kern_f64 / gpbo_factorise_kern_f64 / gpbo_posterior_acq_kern_f64 / gpbo_nlml_grad_kern_f64 / gpbo_nlml_hyper_kern_f64 / gpbo_select_next_host_kern_f64 / gpbo_nlml_grad_host_kern_f64 / gpbo_nlml_hyper_host_kern_f64, the Matern 3/2 and 5/2 covariance families on the fp64 path; gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
+#define GPBO_VERSION 151 /* 0.5.1 (symbols added since, backward compatible: gpbo_ehvi_acq_f64 / gpbo_ehvi_acq_host_f64, two-objective expected hypervolume improvement in log space; gpbo_constrained_acq_f64 / gpbo_constrained_acq_host_f64, constrained expected improvement, probability of improvement and probability of feasibility in log space; gpbo_mes_log_survival_f64 / gpbo_mes_acq_f64 / gpbo_mes_log_survival_host_f64 / gpbo_mes_acq_host_f64, max-value entropy search on the dense posterior; gpbo_nei_fantasies_workspace_bytes / gpbo_nei_fantasies_f64 / gpbo_posterior_nei_workspace_bytes / gpbo_posterior_nei_kern_f64 / gpbo_nei_host_f64, noisy expected improvement; gpbo_kxx_kern_f64 / gpbo_kstar_mu_kern_f64 / gpbo_factorise_kern_f64 / gpbo_posterior_acq_kern_f64 / gpbo_nlml_grad_kern_f64 / gpbo_nlml_hyper_kern_f64 / gpbo_select_next_host_kern_f64 / gpbo_nlml_grad_host_kern_f64 / gpbo_nlml_hyper_host_kern_f64, the Matern 3/2 and 5/2 covariance families on the fp64 path; gpbo_nlml_hyper_workspace_bytes / gpbo_nlml_hyper_f64 / gpbo_nlml_hyper_host_f64 / gpbo_loo_workspace_bytes / gpbo_loo_f64, the likelihood over noise, signal variance and mean with the length scales, and leave-one-out prediction; gpbo_thompson_weights_workspace_bytes / gpbo_thompson_weights_f64 / gpbo_thompson_paths_workspace_bytes / gpbo_thompson_paths_f64 / gpbo_thompson_host_f64, Thompson sampling by pathwise posterior samples; gpbo_posterior_grad_workspace_bytes / gpbo_posterior_grad_f64 / gpbo_refine_workspace_bytes / gpbo_refine_f64 / gpbo_refine_host_f64, acquisition gradients and off-grid refinement; gpbo_batch_workspace_bytes / gpbo_select_batch_f64 / gpbo_select_batch_host_f64, greedy q-point batch selection; gpbo_nlml_grad_workspace_bytes / gpbo_nlml_grad_f64 / gpbo_nlml_grad_host_f64, the likelihood gradient for ML-II length-scale fitting): + gpbo_nlml_grid_wave_f64 / _wave_logdet_f64 (the likelihood grid of N <= 64 observations, a wave per cell); 0.5.0: the likelihood grid of any N in one launch (one workgroup per cell), a second likelihood mode (log det from the factor: gpbo_nlml_grid_*logdet*) */
 
 /* Environment switches the SHIPPED library reads (each once per process; none changes a result beyond the rounding of a
  * different summation order, none is needed for normal use - they select between measured alternatives for A/B runs):
@@ -812,6 +812,48 @@ int gpbo_constrained_acq_host_f64(const double *mu_host, const double *sigma_hos
                                   double xi, const double *cons_mu_host, const double *cons_sigma_host, int64_t ldc, int32_t C,
                                   const double *upper_host, double *val_out_host, double *feas_out_host,
                                   gpbo_result *result_host);
+
+/* ---- Two-objective expected hypervolume improvement on the dense posteriors, in LOG space (csrc/ehvi.hip, DESIGN.md 4p;
+ * Emmerich, Giannakoglou & Naujoks 2006; Emmerich, Yang, Deutz et al. 2016; not in the reference).  BOTH objectives are
+ * minimised, each modelled by a GP of its own, taken as independent: a candidate has (mu1, sigma1) and (mu2, sigma2).  The
+ * reference point is r = (ref1, ref2).  The front holds P >= 0 points (a_i, c_i), i = 1..P, strictly ascending in objective 1
+ * and strictly descending in objective 2, every value finite, every point strictly below r in both coordinates; a_{P+1} = ref1,
+ * c_0 = ref2.  For one objective and a level a
+ *     g(a) = E[(a - f)+] = sigma h((a - mu) / sigma),  h(z) = phi(z) + z Phi(z)     (sigma > 0)
+ *          = max(a - mu, 0)                                                         (sigma == 0)
+ *     G(a) = log g(a) = log sigma + log h(z)           (log h: the three branches of the constrained acquisitions above)
+ * and the region below r, cut into vertical strips at the a_i (strip i has the non-dominated ceiling c_i), gives
+ *     EHVI  = sum_{i = 0..P} [g1(a_{i+1}) - g1(a_i)] g2(c_i),        g1(a_0) := 0      (every term >= 0)
+ *     value = logsumexp_{i = 0..P} (G1(a_{i+1}) + log(1 - exp(G1(a_i) - G1(a_{i+1}))) + G2(c_i))
+ *   Every z is formed as written: one subtraction, then ONE division.  The strips are added in index order, i = 0 first, by a
+ *   one-pass running-maximum logsumexp; the i = 0 strip has no subtraction; log(1 - exp(d)) is log(-expm1(d)) for d > -log 2
+ *   and log1p(-exp(d)) below, and -inf for d >= 0 (two levels whose G agree to the last bit).  A strip whose G1(a_{i+1}) or
+ *   G2(c_i) is -inf is -inf, not NaN.  The plain sum is exactly 0 wherever both objectives are a few dozen standard deviations
+ *   from improving; the logarithm is finite there and keeps the order.  Under y_j -> alpha_j + beta_j y_j (beta_j > 0) of the
+ *   posteriors, the front and r, the value shifts by log beta_1 + log beta_2.
+ * mu1, sigma1, mu2, sigma2 [M] (device).  front_host [P x 2], rows (a_i, c_i), read on the host during the call and passed to
+ *   the kernel by value (may be null with P == 0).
+ * val_out: optional dense [M]; the result does not depend on its presence.  result: as every other acquisition (best_idx =
+ *   idx_offset + the LOWEST candidate attaining the maximum).
+ * Edge rules: a NaN in any of a candidate's four values makes its value NaN; it counts once in nan_count and is never chosen.
+ *   sigma == 0 uses max(a - mu, 0).  -inf is a legal value that beats the empty record: when every candidate is -inf the lowest
+ *   index is returned with best_val = -inf and nan_count untouched.  Ties go to the lowest index.  (mu is finite or NaN, sigma a
+ *   standard deviation: >= 0.)
+ * No sum crosses candidates, the grid depends on M alone, only the integer NaN counter is atomic: two calls give the same bits.
+ * 1 <= M <= 2^40, 0 <= P <= GPBO_EHVI_MAX_P, ref1 / ref2 finite, the front as stated above, no null pointer but val_out (and
+ *   front_host with P == 0) (GPBO_ERR_ARG otherwise);  work: GPBO_EHVI_WORK_BYTES bytes - a constant: the arg-max records of
+ *   1024 workgroups and the counter - 256-byte aligned (GPBO_ERR_WORKSPACE otherwise);  all of it before any HIP call.  The
+ *   call only enqueues.
+ * gpbo_ehvi_acq_host_f64: the same on host arrays (conventions of the other *_host entries: device buffers are allocated,
+ *   filled, used and released inside the call, on a stream of its own; synchronous; idx_offset = 0). */
+#define GPBO_EHVI_MAX_P 128
+#define GPBO_EHVI_WORK_BYTES 16640
+int gpbo_ehvi_acq_f64(const double *mu1, const double *sigma1, const double *mu2, const double *sigma2, int64_t M,
+                      const double *front_host /* [P x 2] */, int32_t P, double ref1, double ref2, int64_t idx_offset,
+                      double *val_out /* optional [M] */, gpbo_result *result, void *work, int64_t work_bytes, void *stream);
+int gpbo_ehvi_acq_host_f64(const double *mu1_host, const double *sigma1_host, const double *mu2_host, const double *sigma2_host,
+                           int64_t M, const double *front_host, int32_t P, double ref1, double ref2, double *val_out_host,
+                           gpbo_result *result_host);
 
 /* Strided-batched fp64 MFMA GEMM used by the factorisation (exported for tests):
  * C_b = alpha * A_b * op(B_b) + beta * C_b, row-major, M and N multiples of 64, K a multiple of 16;

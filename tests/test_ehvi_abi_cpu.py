@@ -1,0 +1,220 @@
+"""CPU-only checks of the expected-hypervolume-improvement boundary (csrc/ehvi.hip): prototypes and constants of include/gpbo.h
+against the binding, every refusal of the two entry points made on the host before anything is launched, the Python layers'
+refusals without a GPU, and the compiled kernel: no scratch, no LDS beyond the arg-max slots (the front travels in the
+kernel-argument record), its barrier with the LDS writes waited for."""
+import ctypes as C
+import os
+import re
+import shutil
+import sys
+
+import numpy as np
+import pytest
+
+from bayesian_optimisation_amd import _lib
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import check_barriers as cb  # noqa: E402
+
+needs_hipcc = pytest.mark.skipif(shutil.which(cb.HIPCC) is None and not os.path.exists(cb.HIPCC), reason="hipcc not installed")
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("gpbo_ehvi_acq_f64", "gpbo_ehvi_acq_host_f64")
+WORK = 16640
+MAX_P = 128
+
+
+def _fake_pointer():
+    buf = (C.c_char * 1024)()
+    return buf, C.c_void_p((C.addressof(buf) + 255) & ~255)   # 256-byte aligned like a device allocation; never dereferenced
+
+
+def _rows(rows):
+    flat = [float(v) for r in rows for v in r]
+    a = (C.c_double * max(len(flat), 1))(*flat)
+    return a, C.cast(a, C.c_void_p)
+
+
+GOOD = [(0.0, 2.0), (1.0, 1.0), (2.0, 0.0)]
+NAN, INF = float("nan"), float("inf")
+BAD_FRONTS = {"nan": [(0.0, 2.0), (1.0, NAN), (2.0, 0.0)], "inf": [(-INF, 2.0), (1.0, 1.0), (2.0, 0.0)],
+              "minus_inf": [(0.0, 2.0), (1.0, 1.0), (2.0, -INF)], "equal_a": [(0.0, 2.0), (0.0, 1.0), (2.0, 0.0)],
+              "descending_a": [(1.0, 2.0), (0.0, 1.0), (2.0, 0.0)], "equal_c": [(0.0, 2.0), (1.0, 2.0), (2.0, 0.0)],
+              "ascending_c": [(0.0, 1.0), (1.0, 2.0), (2.0, 0.0)], "on_r1": [(0.0, 2.0), (1.0, 1.0), (3.0, 0.0)],
+              "beyond_r2": [(0.0, 3.5), (1.0, 1.0), (2.0, 0.0)]}
+
+
+def test_python_constants_and_signatures_match_the_header():
+    src = open(os.path.join(REPO, "include", "gpbo.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"#define\s+(GPBO_[A-Z_]+)\s+\(?(-?\d+)\)?", src)}
+    assert defs["GPBO_EHVI_MAX_P"] == _lib.EHVI_MAX_P == MAX_P
+    assert defs["GPBO_EHVI_WORK_BYTES"] == _lib.EHVI_WORK_BYTES == WORK and WORK % 256 == 0
+    assert WORK >= 2 * 8 * 1024 + 256                            # the arg-max records of 1024 workgroups, the counter
+    assert defs["GPBO_VERSION"] == 151 and _lib.load().gpbo_version() == 151
+    i64, i32, f64, p = C.c_int64, C.c_int32, C.c_double, _lib.Pointer
+    want = {"gpbo_ehvi_acq_f64": [p, p, p, p, i64, p, i32, f64, f64, i64, p, p, p, i64, p],
+            "gpbo_ehvi_acq_host_f64": [p, p, p, p, i64, p, i32, f64, f64, p, p]}
+    for name in NAMES:
+        assert name in src
+        assert _lib.SIGNATURES[name] == (C.c_int, want[name])
+        assert getattr(_lib.load(), name).argtypes == want[name]
+    assert not any(n.startswith("gpbo_ehvi") and n.endswith("_bytes") for n in _lib.SIGNATURES)   # the size is a constant
+
+
+def test_device_entry_refuses_on_the_host():
+    lib = _lib.load()
+    buf, p = _fake_pointer()
+    keep, fp = _rows(GOOD)
+
+    def call(mu1=p, s1=p, mu2=p, s2=p, M=1000, front=fp, P=3, r1=3.0, r2=3.0, off=0, val=None, res=p, work=p, wbytes=WORK):
+        return lib.gpbo_ehvi_acq_f64(mu1, s1, mu2, s2, M, front, P, r1, r2, off, val, res, work, wbytes, None)
+
+    assert lib.gpbo_ehvi_acq_f64(*([None] * 4 + [0, None, 0, 0.0, 0.0, 0] + [None] * 3 + [0, None])) == -1
+    for name in ("mu1", "s1", "mu2", "s2", "front", "res", "work"):
+        assert call(**{name: None}) == -1, name
+    assert call(M=0) == -1 and call(M=-5) == -1 and call(M=(1 << 40) + 1) == -1
+    assert call(P=-1) == -1
+    many = [(float(i), float(-i)) for i in range(MAX_P + 1)]
+    km, mp = _rows(many)
+    assert call(front=mp, P=MAX_P + 1, r1=1e3, r2=1e3) == -1 and call(front=mp, P=MAX_P, r1=1e3, r2=1e3, wbytes=WORK - 1) == -3
+    for name, rows in BAD_FRONTS.items():
+        kb, bp = _rows(rows)
+        assert call(front=bp) == -1, name
+        del kb
+    kb, bp = _rows(BAD_FRONTS["nan"])
+    assert call(front=bp, P=1, wbytes=WORK - 1) == -3            # the rows beyond P are not read
+    for bad in (NAN, INF, -INF):
+        assert call(r1=bad) == -1 and call(r2=bad) == -1 and call(P=0, r1=bad) == -1
+    assert call(r1=2.0) == -1 and call(r2=2.0) == -1             # a front point ON the reference point is not below it
+    # what may be null: the front with P == 0, the dense output always
+    assert call(front=None, P=0, wbytes=WORK - 1) == -3
+    assert call(val=p, off=(1 << 33) + 5, M=1 << 40, wbytes=WORK - 1) == -3
+    # the workspace: one byte short or not 256-byte aligned - after the arguments, before any HIP call
+    assert call(wbytes=WORK - 1) == -3 and call(wbytes=0) == -3
+    assert call(work=C.c_void_p(p.value + 8)) == -3
+    assert lib.gpbo_version() == 151
+    del buf, keep, km, kb
+
+
+def test_host_entry_refuses_on_the_host():
+    lib = _lib.load()
+    buf, p = _fake_pointer()
+    keep, fp = _rows(GOOD)
+
+    def call(mu1=p, s1=p, mu2=p, s2=p, M=10, front=fp, P=3, r1=3.0, r2=3.0, val=None, res=p):
+        return lib.gpbo_ehvi_acq_host_f64(mu1, s1, mu2, s2, M, front, P, r1, r2, val, res)
+
+    assert lib.gpbo_ehvi_acq_host_f64(*([None] * 4 + [0, None, 0, 0.0, 0.0, None, None])) == -1
+    for name in ("mu1", "s1", "mu2", "s2", "front", "res"):
+        assert call(**{name: None}) == -1, name
+    assert call(M=0) == -1 and call(M=(1 << 40) + 1) == -1 and call(P=-1) == -1 and call(P=MAX_P + 1) == -1
+    assert call(r1=NAN) == -1 and call(r2=INF) == -1 and call(r1=2.0) == -1
+    for name, rows in BAD_FRONTS.items():
+        kb, bp = _rows(rows)
+        assert call(front=bp) == -1, name
+        del kb
+    del buf, keep
+
+
+class _NoLibrary:
+    """Stands in for _lib.load() and the entry points: a refusal that reaches the library fails the test."""
+
+    def __call__(self, *a, **k):
+        raise AssertionError("the library was touched before the arguments were refused")
+
+
+def test_python_layers_refuse_bad_arguments_before_the_library_is_touched(monkeypatch):
+    import bayesian_optimisation_amd as pkg
+    from bayesian_optimisation_amd import PointSelector, PointSelectorHost
+    from bayesian_optimisation_amd import host_binding as H
+    from bayesian_optimisation_amd.model import SurrogateModel
+
+    assert "EhviResult" in pkg.__all__ and pkg.EhviResult.__dataclass_fields__.keys() >= {
+        "best_val", "best_idx", "nan_count", "value", "front", "ref"}
+    lib = _lib.load()   # (the selector classes bind it in their constructors)
+    host, host_c = PointSelectorHost(ard="hyper"), PointSelectorHost()
+    monkeypatch.setattr(_lib, "load", _NoLibrary())
+    for fn in NAMES:
+        monkeypatch.setattr(lib, fn, _NoLibrary(), raising=False)
+    mu, sigma = np.zeros(10), np.ones(10)
+    many = np.stack([np.arange(129.0), -np.arange(129.0)], axis=1)
+    bad_kw = [dict(front=np.array(rows)) for rows in BAD_FRONTS.values()] + [
+        dict(front=many, ref=(1e3, 1e3)), dict(front=np.zeros((2, 3))), dict(ref=(3.0,)), dict(ref=(3.0, NAN)), dict(ref=(INF, 3.0)),
+        dict(ref="nadir"), dict(ref=None), dict(mu1=np.zeros(9)), dict(sigma2=np.ones(11)), dict(mu2=np.zeros(0), sigma2=np.zeros(0))]
+    for kw in bad_kw:
+        args = dict(mu1=mu, sigma1=sigma, mu2=mu, sigma2=sigma, front=np.array(GOOD), ref=(3.0, 3.0))
+        args.update(kw)
+        with pytest.raises(ValueError):
+            H.ehvi_acq(**args)
+    # the selector classes: the options the call does not serve are named, for the object and for the second objective; bad
+    # parameters come before "call update_surrogate() first"
+    what = "expected_hypervolume_improvement"
+    with pytest.raises(ValueError, match="ard='marginal'"):
+        PointSelector(ard="marginal").expected_hypervolume_improvement(PointSelector())
+    for precision in ("fp32", "i8", "i8c"):
+        with pytest.raises(ValueError, match="precision"):
+            PointSelector(precision=precision).expected_hypervolume_improvement(PointSelector())
+    with pytest.raises(ValueError, match="dense_outputs"):
+        PointSelector(dense_outputs=False).expected_hypervolume_improvement(PointSelector())
+    for bad, msg in ((PointSelector(ard="marginal"), "ard='marginal'"), (PointSelector(precision="i8"), "precision"),
+                     (PointSelector(dense_outputs=False), "dense_outputs"), (host_c, "must be a PointSelector"),
+                     (object(), "must be a PointSelector"), (None, "must be a PointSelector")):
+        with pytest.raises(ValueError, match=msg):
+            PointSelector().expected_hypervolume_improvement(bad)
+    with pytest.raises(ValueError, match="must be a PointSelectorHost"):
+        host.expected_hypervolume_improvement(PointSelector())
+    for ps, other in ((PointSelector(), PointSelector()), (PointSelector(ard="hyper", kernel="matern52"), PointSelector()),
+                      (host, host_c)):
+        for kw in (dict(ref="worst"), dict(ref=(1.0,)), dict(ref=(1.0, NAN)), dict(ref=(INF, 1.0)), dict(ref=None), dict(ref=1.0),
+                   dict(front="pareto"), dict(front=np.array(BAD_FRONTS["equal_a"]), ref=(3.0, 3.0)),
+                   dict(front=np.array(GOOD), ref=(2.0, 3.0)), dict(front=many, ref=(1e3, 1e3)), dict(front=np.zeros((2, 3)), ref=(1.0, 1.0))):
+            with pytest.raises(ValueError):
+                ps.expected_hypervolume_improvement(other, **kw)
+        for kw in (dict(), dict(ref=(3.0, 3.0)), dict(front=np.array(GOOD)), dict(front=np.array(GOOD), ref=(3.0, 3.0))):
+            with pytest.raises(RuntimeError, match="update_surrogate"):
+                ps.expected_hypervolume_improvement(other, **kw)
+        assert ps.pareto_front is None and ps.reference_point is None and ps.hypervolume is None
+        assert hasattr(ps, what)
+    # units: log EHVI moves by log s of EACH objective's fitted model
+    m = SurrogateModel("se", 0.01, 0.0, 5.0, 3.0, True)
+    a = np.array([-1800.0, -0.25, -np.inf])
+    assert np.array_equal(m.acq_to_y("log_ehvi", a), a + np.log(3.0)) and m.acq_to_y("log_ehvi", a)[2] == -np.inf
+    assert SurrogateModel().acq_to_y("log_ehvi", a) is a
+    assert m.best_to_y("log_ehvi", (-2.0, 7, 0)) == (-2.0 + float(np.log(3.0)), 7, 0)
+
+
+def test_new_package_files_do_not_name_the_cpu_reference():
+    word = "ora" + "cle"
+    pkg = os.path.join(REPO, "bayesian_optimisation_amd")
+    for f in ("pareto.py", os.path.join("csrc", "ehvi.hip"), os.path.join("csrc", "ehvi_math.h")):
+        assert word not in open(os.path.join(pkg, f)).read(), f
+
+
+def _kernel_metadata(asm, field):
+    return {re.search(r"\.name:\s+(\S+)", b).group(1): int(re.search(r"\." + field + r":\s+(\d+)", b).group(1))
+            for b in asm.split("  - .agpr_count:")[1:]}
+
+
+@needs_hipcc
+def test_the_kernel_needs_no_scratch_and_no_lds_beyond_the_argmax_slots(tmp_path):
+    """A fresh csrc/ehvi.hip compiles for gfx950 into ONE kernel: the strip loop is a run-time loop over the kernel-argument
+    record (a copy of the front to private memory would show as scratch, a staging of it as LDS), and the only LDS is the four
+    waves' arg-max records.  The record holds 2 x 129 doubles of strips beside the pointers and the hidden arguments."""
+    asm = open(cb.assemble("ehvi", str(tmp_path))).read()
+    scratch = _kernel_metadata(asm, "private_segment_fixed_size")
+    assert len(scratch) == 1 and "ehvi_acq_kernel" in next(iter(scratch)), sorted(scratch)
+    assert max(scratch.values()) == 0, scratch
+    assert max(_kernel_metadata(asm, "group_segment_fixed_size").values()) == 4 * 8 + 4 * 8
+    assert 2 * 129 * 8 < max(_kernel_metadata(asm, "kernarg_segment_size").values()) <= 2560
+
+
+@needs_hipcc
+def test_no_barrier_of_the_unit_is_reachable_with_an_lds_write_in_flight(capsys):
+    assert "ehvi" in cb.UNITS
+    rc = cb.main(["ehvi"])
+    out = capsys.readouterr().out
+    assert rc == 0, out
+    assert "0 reachable" in out
+    src = open(os.path.join(REPO, "bayesian_optimisation_amd", "csrc", "ehvi.hip")).read()
+    code = re.sub(r"//[^\n]*", "", src)
+    assert "__syncthreads" not in code and code.count("gpbo_syncthreads()") == 1   # the barrier is the waited-for one
+    assert "atomic" not in code                                                    # (the NaN counter's is gpbo_count_nan's)

@@ -21,7 +21,7 @@ from concurrent.futures import ThreadPoolExecutor
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bayesian_optimisation_amd", "csrc")
 UNITS = ["kernel_build", "kstar_mfma", "gemm_f64", "factor", "cholinv", "subset", "update", "sigma_acq", "batch", "refine", "thompson", "nei", "mes",
-         "constrained", "ard",
+         "constrained", "ehvi", "ard",
          "ard_wave", "ard_grad", "hyper", "hyper_wave", "ensemble", "posterior_f32", "rescore", "ozaki"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 

@@ -259,6 +259,33 @@ int main() {
         EXPECT(gpbo_constrained_acq_host_f64(pd, pd, 10, GPBO_CONS_BASE_EI, 0.0, 0.0, pd, pd, 10, 3, bad, nullptr, nullptr, &res_c) == GPBO_ERR_ARG);
         EXPECT(gpbo_constrained_acq_host_f64(pd, pd, 10, GPBO_CONS_BASE_NONE, 0.0, 0.0, nullptr, nullptr, 10, 0, nullptr, nullptr, nullptr, &res_c) == GPBO_ERR_ARG);
     }
+    // two-objective expected hypervolume improvement (tests/test_ehvi_abi_cpu.py): the ranges of M and P, the front read on the
+    // host (only its first P rows: finite, ordered, strictly below the reference point), the reference point, the null pointers,
+    // the constant workspace one byte short or misaligned
+    {
+        gpbo_result res_e;
+        const double nan = __builtin_nan(""), inf = __builtin_huge_val();
+        double fr[6] = {0.0, 2.0, 1.0, 1.0, 2.0, 0.0}, big[2 * (GPBO_EHVI_MAX_P + 1)];
+        double nanf[6] = {0.0, 2.0, 1.0, nan, 2.0, 0.0}, asc[6] = {0.0, 2.0, 0.0, 1.0, 2.0, 0.0}, desc[6] = {0.0, 2.0, 1.0, 2.0, 2.0, 0.0};
+        for (int i = 0; i <= GPBO_EHVI_MAX_P; ++i) big[2 * i] = i, big[2 * i + 1] = -i;
+        auto ehvi = [&](int64_t M, const double *f, int32_t Pn, double r1, double r2, void *w, int64_t wbytes) {
+            return gpbo_ehvi_acq_f64(pd, pd, pd, pd, M, f, Pn, r1, r2, 0, nullptr, &res_e, w, wbytes, nullptr);
+        };
+        const int64_t we = GPBO_EHVI_WORK_BYTES;
+        EXPECT(ehvi(0, fr, 3, 3.0, 3.0, p, we) == GPBO_ERR_ARG && ehvi(((int64_t)1 << 40) + 1, fr, 3, 3.0, 3.0, p, we) == GPBO_ERR_ARG);
+        EXPECT(ehvi(1000, fr, -1, 3.0, 3.0, p, we) == GPBO_ERR_ARG && ehvi(1000, big, GPBO_EHVI_MAX_P + 1, 1e3, 1e3, p, we) == GPBO_ERR_ARG);
+        EXPECT(ehvi(1000, big, GPBO_EHVI_MAX_P, 1e3, 1e3, p, we - 1) == GPBO_ERR_WORKSPACE && ehvi((int64_t)1 << 40, fr, 3, 3.0, 3.0, p, we - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(ehvi(1000, nanf, 3, 3.0, 3.0, p, we) == GPBO_ERR_ARG && ehvi(1000, nanf, 1, 3.0, 3.0, p, we - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(ehvi(1000, asc, 3, 3.0, 3.0, p, we) == GPBO_ERR_ARG && ehvi(1000, desc, 3, 3.0, 3.0, p, we) == GPBO_ERR_ARG);
+        EXPECT(ehvi(1000, fr, 3, 2.0, 3.0, p, we) == GPBO_ERR_ARG && ehvi(1000, fr, 3, 3.0, 2.0, p, we) == GPBO_ERR_ARG);
+        EXPECT(ehvi(1000, fr, 3, nan, 3.0, p, we) == GPBO_ERR_ARG && ehvi(1000, fr, 0, 3.0, inf, p, we) == GPBO_ERR_ARG);
+        EXPECT(ehvi(1000, nullptr, 1, 3.0, 3.0, p, we) == GPBO_ERR_ARG && ehvi(1000, nullptr, 0, 3.0, 3.0, p, we - 1) == GPBO_ERR_WORKSPACE);
+        EXPECT(ehvi(1000, fr, 3, 3.0, 3.0, static_cast<char *>(p) + 8, we) == GPBO_ERR_WORKSPACE && ehvi(1000, fr, 3, 3.0, 3.0, nullptr, we) == GPBO_ERR_ARG);
+        EXPECT(gpbo_ehvi_acq_f64(nullptr, pd, pd, pd, 10, fr, 3, 3.0, 3.0, 0, nullptr, &res_e, p, we, nullptr) == GPBO_ERR_ARG);
+        EXPECT(gpbo_ehvi_acq_f64(pd, pd, pd, pd, 10, fr, 3, 3.0, 3.0, 0, nullptr, nullptr, p, we, nullptr) == GPBO_ERR_ARG);
+        EXPECT(gpbo_ehvi_acq_host_f64(pd, pd, pd, pd, 10, nanf, 3, 3.0, 3.0, nullptr, &res_e) == GPBO_ERR_ARG);
+        EXPECT(gpbo_ehvi_acq_host_f64(pd, pd, pd, nullptr, 10, fr, 3, 3.0, 3.0, nullptr, &res_e) == GPBO_ERR_ARG);
+    }
     // the likelihood of many hyperparameter cells and the ensemble pass (tests/test_marginal_abi_cpu.py): the size limits, the
     // model table read on the host (weights, scales, every model's length scales), the workspace one byte short
     {

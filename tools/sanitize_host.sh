@@ -14,7 +14,7 @@ mkdir -p "$OUT"
 cd "$ROOT/bayesian_optimisation_amd/csrc"
 pids=()
 objs=""
-for f in api kernel_build kstar_mfma gemm_f64 factor cholinv subset update sigma_acq batch refine thompson nei mes constrained ard ard_wave ard_grad hyper hyper_wave ensemble posterior_f32 rescore ozaki host_api; do
+for f in api kernel_build kstar_mfma gemm_f64 factor cholinv subset update sigma_acq batch refine thompson nei mes constrained ehvi ard ard_wave ard_grad hyper hyper_wave ensemble posterior_f32 rescore ozaki host_api; do
   $HIPCC $FLAGS -c $f.hip -o "$OUT/$f.o" &
   pids+=($!)
   objs="$objs $OUT/$f.o"
