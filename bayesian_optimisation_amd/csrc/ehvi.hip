@@ -9,90 +9,45 @@
 // The plain sum is exactly 0 wherever both objectives are a few dozen standard deviations from improving - every candidate then
 // ties; the logarithm is finite there and keeps the order.  A function of dense (mu, sigma) arrays alone: no covariance entry,
 // every kernel family, every model record.
-//     ehvi_acq_kernel    the shape of constrained_acq_kernel (constrained.hip): min(ceil(M / 256), 1024) workgroups of 256
-//                        threads, grid-striding; a thread loads its candidate's 4 values (consecutive threads, consecutive
-//                        addresses in every array); the strip edges and ceilings arrive by value in the kernel-argument record
-//                        (uniform, read with a uniform index: scalar loads into scalar registers, no LDS and no vector register
-//                        per front point); G1 at an edge is evaluated once and carried to the next strip; the running-maximum
-//                        logsumexp lives in two registers; the optional dense store; the workgroup's arg-max record, folded by
-//                        gpbo_launch_argmax_finish
+//     EhviScore    an instance of dense_acq_kernel (dense_acq.h: the candidate loop, the NaN count, the arg-max record, the
+//                  launch).  A thread loads its candidate's 4 values (consecutive threads, consecutive addresses in every
+//                  array); the strip edges and ceilings arrive by value in the kernel-argument record (uniform, read with a
+//                  uniform index: scalar loads into scalar registers, no LDS and no vector register per front point); G1 at an
+//                  edge is evaluated once and carried to the next strip; the running-maximum logsumexp lives in two registers;
+//                  the optional dense store
 // Edge rules (restated in tests/ehvi_ref.py): a NaN in any of a candidate's four values gives value NaN, counted once in
 // nan_count and never chosen; sigma == 0 uses max(level - mu, 0); -inf is a legal value that beats the empty record, so an
 // all -inf input returns its lowest index; ties go to the lowest index.
 // No sum crosses candidates; the grid depends on M alone; only the integer NaN counter is atomic: two calls give the same bits.
-#include "gpbo_internal.h"
+#include "dense_acq.h"
 #include "ehvi_math.h"
 
 namespace {
 
-constexpr int EHVI_MAX_BLOCKS = 1024;
-
-struct EhviArgs {   // 2,072 bytes of the kernel-argument record
+struct EhviScore {   // 2,112 bytes of the kernel-argument record
+    const double *__restrict__ mu1, *__restrict__ sigma1, *__restrict__ mu2, *__restrict__ sigma2;
+    double *__restrict__ val_out;
     double edge[GPBO_EHVI_MAX_P + 1];   // a_1 .. a_P, r1: the right edge of strip i
     double ceil[GPBO_EHVI_MAX_P + 1];   // r2, c_1 .. c_P: the ceiling of strip i
     int32_t P, pad;
-};
-
-// grid min(ceil(M / 256), 1024), block 256.  Every trip of the candidate loop is taken by the whole workgroup (gpbo_count_nan is a
-// wave-wide ballot), the tail masked by `valid`.
-__global__ __launch_bounds__(256) void ehvi_acq_kernel(const double *__restrict__ mu1, const double *__restrict__ sigma1,
-                                                       const double *__restrict__ mu2, const double *__restrict__ sigma2, int64_t M,
-                                                       EhviArgs a, int64_t idx_base, double *__restrict__ val_out,
-                                                       double *__restrict__ part_val, int64_t *__restrict__ part_idx,
-                                                       unsigned long long *__restrict__ nan_count) {
-    __shared__ double s_val[4];
-    __shared__ int64_t s_idx[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double bv = gpbo_none::val;
-    int64_t bi = gpbo_none::idx;
-    for (int64_t b = (int64_t)blockIdx.x * 256; b < M; b += (int64_t)gridDim.x * 256) {
-        const int64_t c = b + tid;
-        const bool valid = c < M;
-        double v = 0.0;
-        if (valid) {
-            const double m1 = mu1[c], s1 = sigma1[c], m2 = mu2[c], s2 = sigma2[c];
-            if (m1 != m1 || s1 != s1 || m2 != m2 || s2 != s2) {
-                v = __builtin_nan("");
-            } else {
-                const double ls1 = log(s1), ls2 = log(s2);
-                EhviSum sum;
-                double g1p = 0.0;
-                for (int i = 0; i <= a.P; ++i) {
-                    const double g1n = ehvi_log_g(a.edge[i], m1, s1, ls1);
-                    sum.add(ehvi_strip(i == 0, g1p, g1n, ehvi_log_g(a.ceil[i], m2, s2, ls2)));
-                    g1p = g1n;
-                }
-                v = sum.value();
+    __device__ __forceinline__ double operator()(int64_t c) const {
+        const double m1 = mu1[c], s1 = sigma1[c], m2 = mu2[c], s2 = sigma2[c];
+        double v;
+        if (m1 != m1 || s1 != s1 || m2 != m2 || s2 != s2) {
+            v = __builtin_nan("");
+        } else {
+            const double ls1 = log(s1), ls2 = log(s2);
+            EhviSum sum;
+            double g1p = 0.0;
+            for (int i = 0; i <= P; ++i) {
+                const double g1n = ehvi_log_g(edge[i], m1, s1, ls1);
+                sum.add(ehvi_strip(i == 0, g1p, g1n, ehvi_log_g(ceil[i], m2, s2, ls2)));
+                g1p = g1n;
             }
-            if (val_out) val_out[c] = v;
+            v = sum.value();
         }
-        const bool is_nan = valid && (v != v);
-        gpbo_count_nan(is_nan, lane, nan_count);
-        if (valid && !is_nan && gpbo_better(v, idx_base + c, bv, bi)) {
-            bv = v;
-            bi = idx_base + c;
-        }
-    }
-    gpbo_argmax_post(bv, bi, lane, wave, s_val, s_idx);
-    gpbo_syncthreads();
-    if (tid == 0) {
-        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
-        part_val[blockIdx.x] = bv;
-        part_idx[blockIdx.x] = bi;
-    }
-}
-
-struct EhviLayout {   // the arg-max records of at most 1024 workgroups, then the NaN counter
-    double *pval;
-    int64_t *pidx;
-    unsigned long long *nan;
-    int64_t total;
-    explicit EhviLayout(void *work) {
-        Carver c(work);
-        pval = c.take<double>(EHVI_MAX_BLOCKS);
-        pidx = c.take<int64_t>(EHVI_MAX_BLOCKS);
-        nan = c.take<unsigned long long>(32);   // 256 bytes
-        total = c.total();
+        if (val_out) val_out[c] = v;
+        return v;
     }
 };
 
@@ -103,21 +58,13 @@ extern "C" int gpbo_ehvi_acq_f64(const double *mu1, const double *sigma1, const 
                                  gpbo_result *result, void *work, int64_t work_bytes, void *stream) {
     if (!ehvi_args_ok(mu1, sigma1, mu2, sigma2, M, front_host, P, ref1, ref2) || !result || !work) return GPBO_ERR_ARG;
     static_assert(GPBO_EHVI_WORK_BYTES % 256 == 0, "the workspace is a whole number of 256-byte regions");
-    if (!aligned_to(work, 256) || work_bytes < GPBO_EHVI_WORK_BYTES || EhviLayout(nullptr).total > GPBO_EHVI_WORK_BYTES)
-        return GPBO_ERR_WORKSPACE;
-    const EhviLayout L(work);
-    hipStream_t st = gpbo_stream(stream);
-    EhviArgs a;
+    if (!DenseAcqScratch::fits(work, work_bytes, GPBO_EHVI_WORK_BYTES)) return GPBO_ERR_WORKSPACE;
+    EhviScore sc;
+    sc.mu1 = mu1, sc.sigma1 = sigma1, sc.mu2 = mu2, sc.sigma2 = sigma2, sc.val_out = val_out;
     for (int i = 0; i <= GPBO_EHVI_MAX_P; ++i) {
-        a.edge[i] = i < P ? front_host[2 * i] : (i == P ? ref1 : 0.0);
-        a.ceil[i] = i == 0 ? ref2 : (i <= P ? front_host[2 * (i - 1) + 1] : 0.0);
+        sc.edge[i] = i < P ? front_host[2 * i] : (i == P ? ref1 : 0.0);
+        sc.ceil[i] = i == 0 ? ref2 : (i <= P ? front_host[2 * (i - 1) + 1] : 0.0);
     }
-    a.P = P, a.pad = 0;
-    if (hipMemsetAsync(L.nan, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
-    const int64_t want = (M + 255) / 256;
-    const int nblk = (int)(want > EHVI_MAX_BLOCKS ? EHVI_MAX_BLOCKS : want);
-    hipLaunchKernelGGL(ehvi_acq_kernel, dim3((unsigned)nblk), dim3(256), 0, st, mu1, sigma1, mu2, sigma2, M, a, idx_offset, val_out,
-                       L.pval, L.pidx, L.nan);
-    GPBO_CHECK_LAUNCH();
-    return gpbo_launch_argmax_finish(L.pval, L.pidx, nblk, L.nan, result, st);
+    sc.P = P, sc.pad = 0;
+    return dense_acq_launch(M, sc, idx_offset, DenseAcqScratch(work), result, gpbo_stream(stream));
 }

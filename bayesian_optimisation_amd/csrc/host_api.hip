@@ -23,6 +23,7 @@
 // Every factorising entry reads: own checks, own buffers, Surrogate (below), own calls, own read-backs.
 #include "gpbo_internal.h"
 
+#include <algorithm>
 #include <vector>
 
 namespace {
@@ -94,6 +95,46 @@ struct Surrogate {
         const int rc = factorise(A, ls, jitter1, jitter2);
         if (rc != GPBO_OK) return rc;
         return A.d2h(info_out, info, sizeof(int32_t)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+    }
+};
+
+// What the entries on dense posteriors the caller holds on the HOST open and close with (MES, the constrained acquisitions, EHVI;
+// no factorisation), after their own refusals: the arena; every input as rows of M values, ld apart on the host and packed on the
+// device; every output the caller asked for (dense values, the result record: whatever the device entry writes); the constant
+// workspace.  The entry returns rc unless it is GPBO_OK, calls its device entry on in[] / out[] / work, and returns finish(status).
+struct DenseCall : DeviceArena {
+    struct In { const double *host; int64_t rows, ld; };
+    struct Out { void *host; size_t bytes; };
+    In ins[4] = {};   // (an unused slot is a null host pointer: no buffer, no copy)
+    Out outs[3] = {};
+    double *in[4] = {};
+    void *out[3] = {};
+    char *work = nullptr;
+    int rc = GPBO_ERR_ARG;   // more inputs or outputs than slots
+    DenseCall(int64_t M, std::initializer_list<In> il, std::initializer_list<Out> ol, int64_t work_bytes) {
+        if (il.size() > 4 || ol.size() > 3) return;
+        std::copy(il.begin(), il.end(), ins), std::copy(ol.begin(), ol.end(), outs);
+        rc = open(M, work_bytes);
+    }
+    int open(int64_t M, int64_t work_bytes) {
+        if (!ok) return GPBO_ERR_LAUNCH;
+        for (int k = 0; k < 4; ++k) in[k] = ins[k].host && ins[k].rows > 0 ? alloc<double>(ins[k].rows * M) : nullptr;
+        for (int k = 0; k < 3; ++k) out[k] = outs[k].host ? alloc<char>((int64_t)outs[k].bytes) : nullptr;
+        work = alloc<char>(work_bytes);   // (hipMalloc: 256-byte aligned)
+        if (!ok) return GPBO_ERR_WORKSPACE;   // if ANY allocation failed
+        for (int k = 0; k < 4; ++k)
+            for (int64_t r = 0; in[k] && r < ins[k].rows; ++r)
+                if (!h2d(in[k] + r * M, ins[k].host + r * ins[k].ld, sizeof(double) * M)) return GPBO_ERR_LAUNCH;
+        return GPBO_OK;
+    }
+    template <class T = double>
+    T *o(int k) const { return static_cast<T *>(out[k]); }
+    int finish(int status) {   // the read-backs and the wait
+        if (status != GPBO_OK) return status;
+        bool okc = true;
+        for (int k = 0; k < 3; ++k)
+            if (out[k]) okc = okc && d2h(outs[k].host, out[k], outs[k].bytes);
+        return okc && sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
     }
 };
 
@@ -414,95 +455,52 @@ extern "C" int gpbo_nei_host_f64(const double *X, const double *y, int64_t N, in
     return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
 }
 
-// Max-value entropy search on host arrays (csrc/mes.hip): no factorisation - the two calls work on a dense posterior (mu, sigma)
-// the caller already holds.  The refusals are the device entries' own (mes_values_ok, host_driver.h), made before the arena exists.
+// Max-value entropy search on host arrays (csrc/mes.hip): the two calls work on a dense posterior (mu, sigma) the caller already
+// holds (DenseCall, above).  The refusals are the device entries' own (mes_values_ok, host_driver.h), made before the arena exists.
 extern "C" int gpbo_mes_log_survival_host_f64(const double *mu, const double *sigma, int64_t M, const double *z, int32_t Q,
                                               double *out, int64_t *nan_out) {
     if (!mu || !sigma || !z || !out || !nan_out || !mes_values_ok(M, z, Q, GPBO_MES_MAX_LEVELS)) return GPBO_ERR_ARG;
-    DeviceArena A;
-    if (!A.ok) return GPBO_ERR_LAUNCH;
-    double *dmu = A.alloc<double>(M), *dsig = A.alloc<double>(M), *dout = A.alloc<double>(Q);
-    int64_t *dnan = A.alloc<int64_t>(1);
-    char *dwork = A.alloc<char>(GPBO_MES_WORK_BYTES);   // (hipMalloc: 256-byte aligned)
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    if (!A.h2d(dmu, mu, sizeof(double) * M) || !A.h2d(dsig, sigma, sizeof(double) * M)) return GPBO_ERR_LAUNCH;
-    const int rc = gpbo_mes_log_survival_f64(dmu, dsig, M, z, Q, dout, dnan, dwork, GPBO_MES_WORK_BYTES, A.st());
-    if (rc != GPBO_OK) return rc;
-    return A.d2h(out, dout, sizeof(double) * Q) && A.d2h(nan_out, dnan, sizeof(int64_t)) && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+    DenseCall D(M, {{mu, 1, M}, {sigma, 1, M}}, {{out, sizeof(double) * Q}, {nan_out, sizeof(int64_t)}}, GPBO_MES_WORK_BYTES);
+    if (D.rc != GPBO_OK) return D.rc;
+    return D.finish(gpbo_mes_log_survival_f64(D.in[0], D.in[1], M, z, Q, D.o(0), D.o<int64_t>(1), D.work, GPBO_MES_WORK_BYTES,
+                                              D.st()));
 }
 
 extern "C" int gpbo_mes_acq_host_f64(const double *mu, const double *sigma, int64_t M, const double *ystar, int32_t S,
                                      double *acq_out, gpbo_result *result) {
     if (!mu || !sigma || !ystar || !result || !mes_values_ok(M, ystar, S, GPBO_MES_MAX_S)) return GPBO_ERR_ARG;
-    DeviceArena A;
-    if (!A.ok) return GPBO_ERR_LAUNCH;
-    double *dmu = A.alloc<double>(M), *dsig = A.alloc<double>(M);
-    double *dacq = acq_out ? A.alloc<double>(M) : nullptr;
-    gpbo_result *dres = A.alloc<gpbo_result>(1);
-    char *dwork = A.alloc<char>(GPBO_MES_WORK_BYTES);   // (hipMalloc: 256-byte aligned)
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    if (!A.h2d(dmu, mu, sizeof(double) * M) || !A.h2d(dsig, sigma, sizeof(double) * M)) return GPBO_ERR_LAUNCH;
-    const int rc = gpbo_mes_acq_f64(dmu, dsig, M, ystar, S, 0, dacq, dres, dwork, GPBO_MES_WORK_BYTES, A.st());
-    if (rc != GPBO_OK) return rc;
-    bool okc = A.d2h(result, dres, sizeof(gpbo_result));
-    if (acq_out) okc = okc && A.d2h(acq_out, dacq, sizeof(double) * M);
-    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+    DenseCall D(M, {{mu, 1, M}, {sigma, 1, M}}, {{acq_out, sizeof(double) * M}, {result, sizeof(gpbo_result)}}, GPBO_MES_WORK_BYTES);
+    if (D.rc != GPBO_OK) return D.rc;
+    return D.finish(gpbo_mes_acq_f64(D.in[0], D.in[1], M, ystar, S, 0, D.o(0), D.o<gpbo_result>(1), D.work, GPBO_MES_WORK_BYTES,
+                                     D.st()));
 }
 
-// The constrained acquisitions on host arrays (csrc/constrained.hip): no factorisation - the call works on the dense posteriors
-// the caller already holds, the objective's and the C constraints' [C x ldc].  The refusals are the device entry's own
-// (cons_args_ok, host_driver.h), made before the arena exists; the rows are uploaded without their padding (ldc = M on the device).
+// The constrained acquisitions on host arrays (csrc/constrained.hip): the objective's dense posterior (read only with a base) and
+// the C constraints' [C x ldc].  The refusals are the device entry's own (cons_args_ok, host_driver.h), made before the arena
+// exists; the rows are uploaded without their padding (ldc = M on the device).
 extern "C" int gpbo_constrained_acq_host_f64(const double *mu, const double *sigma, int64_t M, int32_t base, double f_best,
                                              double xi, const double *cons_mu, const double *cons_sigma, int64_t ldc, int32_t C,
                                              const double *upper, double *val_out, double *feas_out, gpbo_result *result) {
     if (!cons_args_ok(mu, sigma, M, base, f_best, xi, cons_mu, cons_sigma, ldc, C, upper) || !result) return GPBO_ERR_ARG;
-    DeviceArena A;
-    if (!A.ok) return GPBO_ERR_LAUNCH;
-    const bool reads = base != GPBO_CONS_BASE_NONE;
-    double *dmu = reads ? A.alloc<double>(M) : nullptr, *dsig = reads ? A.alloc<double>(M) : nullptr;
-    double *dcm = C > 0 ? A.alloc<double>(C * M) : nullptr, *dcs = C > 0 ? A.alloc<double>(C * M) : nullptr;
-    double *dval = val_out ? A.alloc<double>(M) : nullptr, *dfeas = feas_out ? A.alloc<double>(M) : nullptr;
-    gpbo_result *dres = A.alloc<gpbo_result>(1);
-    char *dwork = A.alloc<char>(GPBO_CONS_WORK_BYTES);   // (hipMalloc: 256-byte aligned)
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    bool okc = !reads || (A.h2d(dmu, mu, sizeof(double) * M) && A.h2d(dsig, sigma, sizeof(double) * M));
-    for (int32_t c = 0; c < C && okc; ++c)
-        okc = A.h2d(dcm + c * M, cons_mu + c * ldc, sizeof(double) * M) && A.h2d(dcs + c * M, cons_sigma + c * ldc, sizeof(double) * M);
-    if (!okc) return GPBO_ERR_LAUNCH;
-    const int rc = gpbo_constrained_acq_f64(dmu, dsig, M, base, f_best, xi, dcm, dcs, M, C, upper, 0, dval, dfeas, dres, dwork,
-                                            GPBO_CONS_WORK_BYTES, A.st());
-    if (rc != GPBO_OK) return rc;
-    okc = A.d2h(result, dres, sizeof(gpbo_result));
-    if (val_out) okc = okc && A.d2h(val_out, dval, sizeof(double) * M);
-    if (feas_out) okc = okc && A.d2h(feas_out, dfeas, sizeof(double) * M);
-    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+    const int64_t own = base != GPBO_CONS_BASE_NONE;
+    DenseCall D(M, {{mu, own, M}, {sigma, own, M}, {cons_mu, C, ldc}, {cons_sigma, C, ldc}},
+                {{val_out, sizeof(double) * M}, {feas_out, sizeof(double) * M}, {result, sizeof(gpbo_result)}}, GPBO_CONS_WORK_BYTES);
+    if (D.rc != GPBO_OK) return D.rc;
+    return D.finish(gpbo_constrained_acq_f64(D.in[0], D.in[1], M, base, f_best, xi, D.in[2], D.in[3], M, C, upper, 0, D.o(0), D.o(1),
+                                             D.o<gpbo_result>(2), D.work, GPBO_CONS_WORK_BYTES, D.st()));
 }
 
-// Two-objective expected hypervolume improvement on host arrays (csrc/ehvi.hip): no factorisation - the call works on the two
-// dense posteriors the caller already holds.  The refusals are the device entry's own (ehvi_args_ok, host_driver.h), made before
-// the arena exists.
+// Two-objective expected hypervolume improvement on host arrays (csrc/ehvi.hip): the two objectives' dense posteriors.  The
+// refusals are the device entry's own (ehvi_args_ok, host_driver.h), made before the arena exists.
 extern "C" int gpbo_ehvi_acq_host_f64(const double *mu1, const double *sigma1, const double *mu2, const double *sigma2, int64_t M,
                                       const double *front, int32_t P, double ref1, double ref2, double *val_out,
                                       gpbo_result *result) {
     if (!ehvi_args_ok(mu1, sigma1, mu2, sigma2, M, front, P, ref1, ref2) || !result) return GPBO_ERR_ARG;
-    DeviceArena A;
-    if (!A.ok) return GPBO_ERR_LAUNCH;
-    const double *src[4] = {mu1, sigma1, mu2, sigma2};
-    double *dev[4];
-    for (double *&p : dev) p = A.alloc<double>(M);
-    double *dval = val_out ? A.alloc<double>(M) : nullptr;
-    gpbo_result *dres = A.alloc<gpbo_result>(1);
-    char *dwork = A.alloc<char>(GPBO_EHVI_WORK_BYTES);   // (hipMalloc: 256-byte aligned)
-    if (!A.ok) return GPBO_ERR_WORKSPACE;
-    bool okc = true;
-    for (int k = 0; k < 4 && okc; ++k) okc = A.h2d(dev[k], src[k], sizeof(double) * M);
-    if (!okc) return GPBO_ERR_LAUNCH;
-    const int rc = gpbo_ehvi_acq_f64(dev[0], dev[1], dev[2], dev[3], M, front, P, ref1, ref2, 0, dval, dres, dwork,
-                                     GPBO_EHVI_WORK_BYTES, A.st());
-    if (rc != GPBO_OK) return rc;
-    okc = A.d2h(result, dres, sizeof(gpbo_result));
-    if (val_out) okc = okc && A.d2h(val_out, dval, sizeof(double) * M);
-    return okc && A.sync() ? GPBO_OK : GPBO_ERR_LAUNCH;
+    DenseCall D(M, {{mu1, 1, M}, {sigma1, 1, M}, {mu2, 1, M}, {sigma2, 1, M}},
+                {{val_out, sizeof(double) * M}, {result, sizeof(gpbo_result)}}, GPBO_EHVI_WORK_BYTES);
+    if (D.rc != GPBO_OK) return D.rc;
+    return D.finish(gpbo_ehvi_acq_f64(D.in[0], D.in[1], D.in[2], D.in[3], M, front, P, ref1, ref2, 0, D.o(0), D.o<gpbo_result>(1),
+                                      D.work, GPBO_EHVI_WORK_BYTES, D.st()));
 }
 
 // Off-grid refinement on host arrays: factorisation + gpbo_refine_f64 (csrc/refine.hip).

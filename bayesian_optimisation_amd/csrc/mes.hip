@@ -9,31 +9,27 @@
 // numbers, bayesian_optimisation_amd/mes.py): under an independence approximation
 //     log S(z) = log Pr[m* > z] = sum_c log Phi((mu_c - z) / sigma_c)
 // at Q <= 64 levels z in ONE pass over the candidates:
-//     mes_log_survival_kernel   min(ceil(M / 256), 1024) workgroups of 256 threads, grid-striding; a thread loads (mu_c, sigma_c)
+//     mes_log_survival_kernel   dense_acq_blocks(M) workgroups of 256 threads, grid-striding; a thread loads (mu_c, sigma_c)
 //                               once and adds its term to one fp64 accumulator PER LEVEL, all in registers; the levels arrive by
 //                               value in the kernel-argument record (uniform: scalar registers)
 //     mes_survival_finish_kernel  adds the workgroups' partial sums in index order and publishes the NaN count
 // gpbo_mes_acq_f64:
-//     mes_acq_kernel            the shape of acq_argmax_kernel (sigma_acq.hip): per candidate the S terms in index order, divided by
-//                               S, the optional dense store, the workgroup's arg-max record; gpbo_launch_argmax_finish folds them
+//     MesScore                  an instance of dense_acq_kernel (dense_acq.h: the candidate loop, the NaN count, the arg-max
+//                               record, the launch): per candidate the S terms in index order, divided by S, the optional dense
+//                               store; the sampled minima arrive by value in the kernel-argument record (uniform: scalar registers)
 // Edge rules (restated in tests/mes_ref.py):
 //     mu or sigma NaN   log S: the candidate is skipped and counted.  Acquisition: NaN, counted once in nan_count, never chosen.
 //     sigma == 0        log S: the term is 0 where mu > z and -inf otherwise.  Acquisition: 0 (nothing to learn there).
 // Sums run in a fixed order - a thread's candidates ascending, the xor butterfly inside a wave, the four waves in wave order, the
 // workgroups in index order - and the grid depends on M alone: two calls give the same bits.  No floating-point atomics; only the
 // integer NaN counter is atomic (gpbo_count_nan).
-#include "gpbo_internal.h"
+#include "dense_acq.h"
 #include "mes_math.h"
 
 namespace {
 
-constexpr int MES_MAX_BLOCKS = 1024;
-
 struct MesLevels {
     double z[GPBO_MES_MAX_LEVELS];
-};
-struct MesSamples {
-    double y[GPBO_MES_MAX_S];
 };
 
 // One candidate's term of log S(z).  NOT inlined: the level loop of mes_log_survival_kernel is unrolled (its accumulators are
@@ -48,7 +44,7 @@ __device__ __attribute__((noinline)) double mes_survival_term(double mu, double 
 // part[blockIdx.x * Q + q] = sum over this workgroup's candidates of log Phi((mu_c - z_q) / sigma_c), q < Q <= QCAP = 64.
 // ONE instance: instances with 8 and 32 accumulators (67 / 103 registers against 169) were measured at 0.88 and 1.11 x 10^11 terms
 // per second against 1.05 here - the kernel is bound by fp64 issue at every occupancy, fewer accumulators buy nothing.
-// grid min(ceil(M / 256), 1024), block 256.  Every trip of the candidate loop is taken by the whole workgroup (gpbo_count_nan
+// grid dense_acq_blocks(M), block 256.  Every trip of the candidate loop is taken by the whole workgroup (gpbo_count_nan
 // is a wave-wide ballot), the tail masked by `valid`.
 __global__ __launch_bounds__(256) void mes_log_survival_kernel(const double *__restrict__ mu, const double *__restrict__ sigma,
                                                                int64_t M, MesLevels lv, int Q, double *__restrict__ part,
@@ -97,70 +93,39 @@ __global__ __launch_bounds__(64) void mes_survival_finish_kernel(const double *_
     if (q == 0) nan_out[0] = (int64_t)nan_count[0];
 }
 
-// MES + arg-max over dense mu / sigma.  grid min(ceil(M / 256), 1024), block 256; the candidate loop as above.
-__global__ __launch_bounds__(256) void mes_acq_kernel(const double *__restrict__ mu, const double *__restrict__ sigma, int64_t M,
-                                                      MesSamples ys, int S, int64_t idx_base, double *__restrict__ acq_out,
-                                                      double *__restrict__ part_val, int64_t *__restrict__ part_idx,
-                                                      unsigned long long *__restrict__ nan_count) {
-    __shared__ double s_val[4];
-    __shared__ int64_t s_idx[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double bv = gpbo_none::val;
-    int64_t bi = gpbo_none::idx;
-    for (int64_t b = (int64_t)blockIdx.x * 256; b < M; b += (int64_t)gridDim.x * 256) {
-        const int64_t c = b + tid;
-        const bool valid = c < M;
-        const double m = valid ? mu[c] : 0.0;
-        const double sg = valid ? sigma[c] : 0.0;
+// MES of one candidate over dense mu / sigma.
+struct MesScore {
+    const double *__restrict__ mu, *__restrict__ sigma;
+    double *__restrict__ acq_out;
+    double y[GPBO_MES_MAX_S];
+    int32_t S, pad;
+    __device__ __forceinline__ double operator()(int64_t c) const {
+        const double m = mu[c], sg = sigma[c];
         double a = 0.0;
         if (m != m || sg != sg) {
             a = __builtin_nan("");
         } else if (sg != 0.0) {
             double sum = 0.0;
-            for (int s = 0; s < S; ++s) sum += mes_term((m - ys.y[s]) / sg);
+            for (int s = 0; s < S; ++s) sum += mes_term((m - y[s]) / sg);
             a = sum / (double)S;
         }
-        if (valid && acq_out) acq_out[c] = a;
-        const bool is_nan = valid && (a != a);
-        gpbo_count_nan(is_nan, lane, nan_count);
-        if (valid && !is_nan && gpbo_better(a, idx_base + c, bv, bi)) {
-            bv = a;
-            bi = idx_base + c;
-        }
-    }
-    gpbo_argmax_post(bv, bi, lane, wave, s_val, s_idx);
-    gpbo_syncthreads();
-    if (tid == 0) {
-        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
-        part_val[blockIdx.x] = bv;
-        part_idx[blockIdx.x] = bi;
-    }
-}
-
-struct MesLayout {   // the partial sums of at most 1024 workgroups x 64 levels, then the arg-max records
-    double *part, *pval;
-    int64_t *pidx;
-    unsigned long long *nan;
-    int64_t total;
-    explicit MesLayout(void *work) {
-        Carver c(work);
-        part = c.take<double>((int64_t)MES_MAX_BLOCKS * GPBO_MES_MAX_LEVELS);
-        pval = c.take<double>(MES_MAX_BLOCKS);
-        pidx = c.take<int64_t>(MES_MAX_BLOCKS);
-        nan = c.take<unsigned long long>(32);   // 256 bytes
-        total = c.total();
+        if (acq_out) acq_out[c] = a;
+        return a;
     }
 };
 
-int mes_blocks(int64_t M) {
-    const int64_t nblk = (M + 255) / 256;
-    return (int)(nblk > MES_MAX_BLOCKS ? MES_MAX_BLOCKS : nblk);
-}
+struct MesLayout {   // the partial sums of at most DENSE_ACQ_MAX_BLOCKS workgroups x 64 levels, then the arg-max scratch
+    Carver carve;
+    double *part;
+    DenseAcqScratch acq;
+    explicit MesLayout(void *work)
+        : carve(work), part(carve.take<double>((int64_t)DENSE_ACQ_MAX_BLOCKS * GPBO_MES_MAX_LEVELS)), acq(carve) {}
+};
 
 int mes_workspace(const void *work, int64_t work_bytes) {
     static_assert(GPBO_MES_WORK_BYTES % 256 == 0, "the workspace is a whole number of 256-byte regions");
     if (!aligned_to(work, 256) || work_bytes < GPBO_MES_WORK_BYTES) return GPBO_ERR_WORKSPACE;
-    return MesLayout(nullptr).total <= GPBO_MES_WORK_BYTES ? GPBO_OK : GPBO_ERR_WORKSPACE;
+    return MesLayout(nullptr).carve.total() <= GPBO_MES_WORK_BYTES ? GPBO_OK : GPBO_ERR_WORKSPACE;
 }
 
 }  // namespace
@@ -175,11 +140,11 @@ extern "C" int gpbo_mes_log_survival_f64(const double *mu, const double *sigma, 
     hipStream_t st = gpbo_stream(stream);
     MesLevels lv;
     for (int q = 0; q < GPBO_MES_MAX_LEVELS; ++q) lv.z[q] = q < Q ? z_host[q] : 0.0;
-    if (hipMemsetAsync(L.nan, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
-    const int nblk = mes_blocks(M);
-    hipLaunchKernelGGL(mes_log_survival_kernel, dim3((unsigned)nblk), dim3(256), 0, st, mu, sigma, M, lv, (int)Q, L.part, L.nan);
+    if (hipMemsetAsync(L.acq.nan, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
+    const int nblk = dense_acq_blocks(M);
+    hipLaunchKernelGGL(mes_log_survival_kernel, dim3((unsigned)nblk), dim3(256), 0, st, mu, sigma, M, lv, (int)Q, L.part, L.acq.nan);
     GPBO_CHECK_LAUNCH();
-    hipLaunchKernelGGL(mes_survival_finish_kernel, dim3(1), dim3(64), 0, st, L.part, nblk, (int)Q, L.nan, out, nan_out);
+    hipLaunchKernelGGL(mes_survival_finish_kernel, dim3(1), dim3(64), 0, st, L.part, nblk, (int)Q, L.acq.nan, out, nan_out);
     GPBO_CHECK_LAUNCH();
     return GPBO_OK;
 }
@@ -191,14 +156,9 @@ extern "C" int gpbo_mes_acq_f64(const double *mu, const double *sigma, int64_t M
     if (!mes_values_ok(M, ystar_host, S, GPBO_MES_MAX_S)) return GPBO_ERR_ARG;
     const int rc = mes_workspace(work, work_bytes);
     if (rc != GPBO_OK) return rc;
-    const MesLayout L(work);
-    hipStream_t st = gpbo_stream(stream);
-    MesSamples ys;
-    for (int s = 0; s < GPBO_MES_MAX_S; ++s) ys.y[s] = s < S ? ystar_host[s] : 0.0;
-    if (hipMemsetAsync(L.nan, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
-    const int nblk = mes_blocks(M);
-    hipLaunchKernelGGL(mes_acq_kernel, dim3((unsigned)nblk), dim3(256), 0, st, mu, sigma, M, ys, (int)S, idx_offset, acq_out,
-                       L.pval, L.pidx, L.nan);
-    GPBO_CHECK_LAUNCH();
-    return gpbo_launch_argmax_finish(L.pval, L.pidx, nblk, L.nan, result, st);
+    MesScore sc;
+    sc.mu = mu, sc.sigma = sigma, sc.acq_out = acq_out;
+    for (int s = 0; s < GPBO_MES_MAX_S; ++s) sc.y[s] = s < S ? ystar_host[s] : 0.0;
+    sc.S = S, sc.pad = 0;
+    return dense_acq_launch(M, sc, idx_offset, MesLayout(work).acq, result, gpbo_stream(stream));
 }

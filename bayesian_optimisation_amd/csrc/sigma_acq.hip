@@ -19,6 +19,7 @@
 // diagonal (where tiles below U's diagonal are skipped) both always have nearly the same amount of work and
 // keep hiding each other's LDS / branch / DMA-issue latencies.
 #include "cov_entry.h"
+#include "dense_acq.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -452,37 +453,6 @@ __global__ __launch_bounds__(256) void split_finish_kernel(const double *__restr
     for (int q = 0; q < S; ++q) ssq += ss_part[(int64_t)q * ldk + c];
     gpbo_candidate_epilogue(ssq, mu_part, nsl, ldk, c, valid, prior_var, var_pad, acq_kind, p0, p1, idx_base, mu_out, sigma_out,
                             acq_out, var_out, lane, nan_count, bv, bi);
-    gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
-    __syncthreads();
-    if (tid == 0) {
-        gpbo_argmax_fold(s_val, s_idx, 4, bv, bi);
-        part_val[blockIdx.x] = bv;
-        part_idx[blockIdx.x] = bi;
-    }
-}
-
-// Acquisition + arg-max over dense mu / sigma that are already on the device (used when the caller asks
-// for a second acquisition on the same posterior, e.g. lower_confidence_bound(explore != 4)).
-__global__ __launch_bounds__(256) void acq_argmax_kernel(const double *__restrict__ mu, const double *__restrict__ sigma,
-                                                         int64_t M, int acq_kind, double p0, double p1, int64_t idx_base,
-                                                         double *__restrict__ acq_out, double *__restrict__ part_val,
-                                                         int64_t *__restrict__ part_idx,
-                                                         unsigned long long *__restrict__ nan_count) {
-    __shared__ double s_val[4];
-    __shared__ int64_t s_idx[4];
-    const int tid = threadIdx.x, lane = tid & 63;
-    double bv = gpbo_none::val;
-    int64_t bi = gpbo_none::idx;
-    unsigned long long nans = 0;
-    for (int64_t c = (int64_t)blockIdx.x * 256 + tid; c < M; c += (int64_t)gridDim.x * 256) {
-        const double a = gpbo_acquisition(acq_kind, mu[c], sigma[c], p0, p1);
-        if (acq_out) acq_out[c] = a;
-        if (a != a) ++nans;
-        else if (gpbo_better(a, idx_base + c, bv, bi)) { bv = a; bi = idx_base + c; }
-    }
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) nans += __shfl_xor(nans, off);
-    if (lane == 0 && nans) atomicAdd(nan_count, nans);
     gpbo_argmax_post(bv, bi, lane, tid >> 6, s_val, s_idx);
     __syncthreads();
     if (tid == 0) {
@@ -1020,39 +990,31 @@ int gpbo_posterior_acq_f64_split(const double *Xs, int64_t M, const GpModel &gp,
 }
 
 namespace {
-struct AcqLayout {   // partial records of at most 1024 workgroups
-    double *pval;
-    int64_t *pidx;
-    unsigned long long *nan;
-    int64_t total;
-    explicit AcqLayout(void *work) {
-        Carver c(work);
-        pval = c.take<double>(1024);
-        pidx = c.take<int64_t>(1024);
-        nan = c.take<unsigned long long>(32);   // 256 bytes
-        total = c.total();
+// Acquisition over dense mu / sigma that are already on the device (used when the caller asks for a second acquisition on the
+// same posterior, e.g. lower_confidence_bound(explore != 4)): an instance of dense_acq_kernel (dense_acq.h).
+struct AcqScore {
+    const double *__restrict__ mu, *__restrict__ sigma;
+    double *__restrict__ acq_out;
+    double p0, p1;
+    int32_t kind, pad;
+    __device__ __forceinline__ double operator()(int64_t c) const {
+        const double a = gpbo_acquisition(kind, mu[c], sigma[c], p0, p1);
+        if (acq_out) acq_out[c] = a;
+        return a;
     }
 };
 }  // namespace
 
-extern "C" int64_t gpbo_acq_workspace_bytes(void) { return AcqLayout(nullptr).total; }
+extern "C" int64_t gpbo_acq_workspace_bytes(void) { return DenseAcqScratch::bytes(); }
 
 extern "C" int gpbo_acq_argmax_f64(const double *mu, const double *sigma, int64_t M, int32_t acq_kind, double p0,
                                    double p1, int64_t idx_offset, double *acq_out, gpbo_result *result, void *work,
                                    int64_t work_bytes, void *stream) {
     if (!mu || !sigma || !result || !work || M < 1) return GPBO_ERR_ARG;
     if (!acq_kind_ok(acq_kind)) return GPBO_ERR_ARG;
-    const AcqLayout L(work);
-    if (work_bytes < L.total) return GPBO_ERR_WORKSPACE;
-    hipStream_t st = gpbo_stream(stream);
-    if (hipMemsetAsync(L.nan, 0, sizeof(unsigned long long), st) != hipSuccess) return GPBO_ERR_LAUNCH;
-    int64_t nblk = (M + 255) / 256;
-    if (nblk > 1024) nblk = 1024;
-    hipLaunchKernelGGL(acq_argmax_kernel, dim3((unsigned)nblk), dim3(256), 0, st, mu, sigma, M, (int)acq_kind, p0, p1,
-                       idx_offset, acq_out, L.pval, L.pidx, L.nan);
-    hipLaunchKernelGGL(argmax_finish_kernel, dim3(1), dim3(256), 0, st, L.pval, L.pidx, nblk, L.nan, result);
-    GPBO_CHECK_LAUNCH();
-    return GPBO_OK;
+    if (work_bytes < DenseAcqScratch::bytes()) return GPBO_ERR_WORKSPACE;
+    const AcqScore sc = {mu, sigma, acq_out, p0, p1, acq_kind, 0};
+    return dense_acq_launch(M, sc, idx_offset, DenseAcqScratch(work), result, gpbo_stream(stream));
 }
 
 extern "C" int64_t gpbo_qei_workspace_bytes(int64_t Np, int64_t chunk, int64_t M) {

@@ -9,7 +9,8 @@ import os
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bayesian_optimisation_amd", "csrc")
 COMMON = ["kernel_build.hip", "cov_entry.h", "exp_neg.h", "gpbo_internal.h"]
-SOURCES = {"f64": ["sigma_acq.hip"] + COMMON, "f64b": ["sigma_acq.hip", "kstar_mfma.hip", "rescore.hip"] + COMMON,
+SOURCES = {"f64": ["sigma_acq.hip", "dense_acq.h"] + COMMON,
+           "f64b": ["sigma_acq.hip", "dense_acq.h", "kstar_mfma.hip", "rescore.hip"] + COMMON,
            "f32": ["posterior_f32.hip"] + COMMON, "i8": ["ozaki.hip"] + COMMON, "i8c": ["ozaki.hip"] + COMMON,
            "ard": ["ard.hip", "potrf_diag64.h", "cov_entry.h", "exp_neg.h", "gpbo_internal.h"],
            "ard_wave": ["ard_wave.hip", "wave_cell.h", "potrf_diag64.h", "cov_entry.h", "exp_neg.h", "gpbo_internal.h"]}

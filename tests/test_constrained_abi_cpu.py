@@ -209,7 +209,7 @@ def test_the_kernel_needs_no_scratch_and_no_lds_beyond_the_argmax_slots(tmp_path
     arg-max records."""
     asm = open(cb.assemble("constrained", str(tmp_path))).read()
     scratch = _kernel_metadata(asm, "private_segment_fixed_size")
-    assert len(scratch) == 1 and "constrained_acq_kernel" in next(iter(scratch)), sorted(scratch)
+    assert len(scratch) == 1 and "dense_acq_kernel" in next(iter(scratch)) and "ConsScore" in next(iter(scratch)), sorted(scratch)
     assert max(scratch.values()) == 0, scratch
     assert max(_kernel_metadata(asm, "group_segment_fixed_size").values()) == 4 * 8 + 4 * 8
 
@@ -221,7 +221,8 @@ def test_no_barrier_of_the_unit_is_reachable_with_an_lds_write_in_flight(capsys)
     out = capsys.readouterr().out
     assert rc == 0, out
     assert "0 reachable" in out
-    src = open(os.path.join(REPO, "bayesian_optimisation_amd", "csrc", "constrained.hip")).read()
+    csrc = os.path.join(REPO, "bayesian_optimisation_amd", "csrc")   # the unit and the frame of its kernel (dense_acq.h)
+    src = open(os.path.join(csrc, "constrained.hip")).read() + open(os.path.join(csrc, "dense_acq.h")).read()
     code = re.sub(r"//[^\n]*", "", src)
     assert "__syncthreads" not in code and code.count("gpbo_syncthreads()") == 1   # the barrier is the waited-for one
     assert "atomic" not in code                                                    # (the NaN counter's is gpbo_count_nan's)

@@ -946,7 +946,7 @@ def test_large_call_column_groups_break_ties_to_the_lowest_index_and_count_nan()
 
 
 def test_second_acquisition_breaks_ties_to_the_lowest_index_and_counts_nan():
-    """acq_argmax_kernel on dense mu / sigma (no factorisation needed): M = 805 is four workgroups, the last wave partial.
+    """dense_acq_kernel<AcqScore> on dense mu / sigma (no factorisation needed): M = 805 is four workgroups, the last wave partial.
     The values are the two roundings of NumPy's line, the maximum planted in three workgroups is reported at its lowest
     row, NaN rows are counted and skipped; with nothing but NaN the result is the empty record."""
     M, rng = 805, np.random.default_rng(11)

@@ -191,7 +191,7 @@ def test_no_kernel_of_the_unit_needs_scratch(tmp_path):
     sizes = _kernel_sizes(open(cb.assemble("mes", str(tmp_path))).read())
     surv = {k: v for k, v in sizes.items() if "mes_log_survival_kernel" in k}
     assert len(surv) == 1, sorted(sizes)
-    assert any("mes_acq_kernel" in k for k in sizes) and any("mes_survival_finish_kernel" in k for k in sizes)
+    assert any("dense_acq_kernel" in k and "MesScore" in k for k in sizes) and any("mes_survival_finish_kernel" in k for k in sizes)
     assert max(sizes.values()) == 0, sizes
 
 
@@ -202,6 +202,7 @@ def test_no_barrier_of_the_unit_is_reachable_with_an_lds_write_in_flight(capsys)
     out = capsys.readouterr().out
     assert rc == 0, out
     assert "0 reachable" in out
-    src = open(os.path.join(REPO, "bayesian_optimisation_amd", "csrc", "mes.hip")).read()
+    csrc = os.path.join(REPO, "bayesian_optimisation_amd", "csrc")   # the unit and the frame of its kernel (dense_acq.h)
+    src = open(os.path.join(csrc, "mes.hip")).read() + open(os.path.join(csrc, "dense_acq.h")).read()
     code = re.sub(r"//[^\n]*", "", src)
     assert "__syncthreads" not in code and code.count("gpbo_syncthreads()") == 2   # every barrier is the waited-for one
